@@ -13,8 +13,8 @@ top-k select -> certification [-> all-gather + host merge when N > 1]).
 Scaling definition (STRONG): the database (`--rows`, 10M in total) is row-sharded over the N
 ranks and already resident in HBM, and EVERY N -- N = 1 included -- answers the same
 `--queries` queries per step, so `value` at N GPUs over `value` at 1 GPU is the speed-up of
-the same job.  (Round 1 grew the batch with N; that compared different jobs.)  Larger total
-batches are measured after the timed region and reported as `other_batches` at every N.
+the same job.  (Round 1 grew the batch with N; that compared different jobs.)  With `--full`, larger
+total batches are measured after the timed region and reported as `other_batches` at every N.
 
 Searches are pipelined (`sq_dense_search` with SQ_MEM_DEVICE_ASYNC, include/smqtk_hip.h):
 the kernels of step i + 1 are enqueued while step i runs and the status words of step i are
@@ -27,6 +27,16 @@ right after enqueueing (`--async-wait 0`: the gather / merge bookkeeping overlap
 steps share one all-gather (`--gather-every`: the collective's fixed cost is that of a whole step on
 a 1.25 M-row shard) and the library's timing events are taken on every 4th search; results come
 back a group at a time, all inside the timed region.
+
+A plain run sets up, warms up, times the `--steps` steps and prints the result line (`metric`, `value`,
+`unit`, `higher_is_better`, `dtype`, `ms_per_step`, the run's configuration).  Everything else the
+benchmark measures or checks runs only with `--full`: the kernel's own duration and the roofline figures
+(blocking calls after the timed region), the parity check against the oracle, the other batch sizes,
+the ITQ / Hamming timings and the CPU baselines.
+
+    --dump-outputs DIR       after the timed steps, write what the last timed step returned to its caller
+                             as DIR/distances.npy (float32; float64 for cosine) and DIR/indices.npy (float64):
+                             the inputs are seeded, so two builds can be compared output for output
 
 Other workloads (reported with the same contract, not the driver's default):
     --workload lsh_c3        BASELINE config 3: 10M x 128 -> 64-bit ITQ codes -> Hamming top-n
@@ -105,6 +115,11 @@ def parse_args():
     ap.add_argument("--fit", action="store_true",
                     help="lsh_c3: hash with a model TRAINED on the data (HipItqFunctor.fit on the device) instead of the fixed "
                          "random rotation of SURVEY 8d; with --data clustered the recall then says something about the method")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure: roofline, parity check, other "
+                         "batch sizes, ITQ / Hamming timings, CPU baselines (the --no-* options above still turn parts off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the last timed step's results as DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--launch-selftest", action="store_true",
                     help="no GPU work: the ranks rendezvous over gloo, all-reduce one integer and rank 0 prints a line "
                          "(tests/test_host_logic.py checks the --gpus N self-launch with it)")
@@ -217,7 +232,7 @@ def bruteforce(args, torch, dist, _lib, world, rank, dev, use_dist, emit):
     if use_async:
         index.set_option("dense_async_depth", depth)
 
-    scan_ms, rerank_ms, cands, fallbacks, mids = [], [], [], [], []
+    scan_ms, rerank_ms, cands, fallbacks, mids, scanned = [], [], [], [], [], []
 
     def note_stats():
         st = index.stats()
@@ -225,6 +240,7 @@ def bruteforce(args, torch, dist, _lib, world, rank, dev, use_dist, emit):
             if st["scan_ms"] > 0:          # (0: a call that was not timed, see the profile option above)
                 scan_ms.append(st["scan_ms"])
                 rerank_ms.append(st["rerank_ms"])
+            scanned.append(st["bytes_scanned"])
             cands.append(st["candidates"])
             fallbacks.append(st["fallback_queries"])
             mids.append(st["mid_tier_queries"])
@@ -299,7 +315,7 @@ def bruteforce(args, torch, dist, _lib, world, rank, dev, use_dist, emit):
         run.step()
     run.drain()
     run.n = 0
-    scan_ms.clear(), rerank_ms.clear(), cands.clear(), fallbacks.clear(), mids.clear()
+    scan_ms.clear(), rerank_ms.clear(), cands.clear(), fallbacks.clear(), mids.clear(), scanned.clear()
     fence()
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -311,7 +327,16 @@ def bruteforce(args, torch, dist, _lib, world, rank, dev, use_dist, emit):
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        # what the caller of the last timed step received: (nq, k) distances and row ids
+        if result is None:
+            raise SystemExit("bench.py: --dump-outputs: the last timed step returned no result")
+        rd_, ri_ = (x.cpu().numpy() if torch.is_tensor(x) else np.asarray(x) for x in result)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "distances.npy"), rd_.astype(np.float64 if rd_.dtype == np.float64 else np.float32))
+        np.save(os.path.join(args.dump_outputs, "indices.npy"), ri_.astype(np.float64))
     n_stats = len(scan_ms)
+    lib_bytes = float(min(scanned)) if scanned else 0.0     # (--full: the blocking calls below set it, as they always did)
     pipe_scan_ms = float(np.mean(scan_ms)) if scan_ms else 0.0
     pipe_rerank_ms = float(np.mean(rerank_ms)) if rerank_ms else 0.0
     gather_ms = merge_ms = None
@@ -327,31 +352,33 @@ def bruteforce(args, torch, dist, _lib, world, rank, dev, use_dist, emit):
     # above the scan of one call shares the device with the short kernels of its neighbours (and runs on 3/4 of the
     # CUs to leave them room), so its bracketed duration there is longer than its own streaming time -- it can exceed
     # ms_per_step -- and is reported separately as kernel_ms_in_pipeline.  roofline.achieved / frac use THIS one.
-    index.sync() if use_async else None
-    index.set_option("profile", 1)
-    # (the fused int8 call re-ranks inside the full-pass kernel: its per-workgroup clocks split the kernel's duration into
-    # the stream and the tail -- sq_stats_t.rerank_ms then is the tail; measurement bit of option dense_debug)
-    index.set_option("dense_debug", lib_opts.get("dense_debug", 0) | 8192)
-    od1 = torch.empty((nq, k), dtype=ddt, device=dev)
-    oi1 = torch.empty((nq, k), dtype=torch.int64, device=dev)
-    al, al_rr = [], []
-    for j in range(4 + 2 * nbatch):
-        qb_ = batches[j % nbatch]
-        index.search_device(qb_.data_ptr(), nq, k, od1.data_ptr(), oi1.data_ptr(), stream)
-        st_ = index.stats()
-        al.append(st_["scan_ms"])
-        al_rr.append(st_["rerank_ms"])
-        lib_bytes = float(st_["bytes_scanned"])
-    head_scan_ms = float(np.mean(al[4:]))
-    alone_rerank_ms = float(np.mean(al_rr[4:]))
-    index.set_option("profile", prof_every)
-    index.set_option("dense_debug", lib_opts.get("dense_debug", 0))
+    head_scan_ms = alone_rerank_ms = None
+    if args.full:
+        index.sync() if use_async else None
+        index.set_option("profile", 1)
+        # (the fused int8 call re-ranks inside the full-pass kernel: its per-workgroup clocks split the kernel's duration into
+        # the stream and the tail -- sq_stats_t.rerank_ms then is the tail; measurement bit of option dense_debug)
+        index.set_option("dense_debug", lib_opts.get("dense_debug", 0) | 8192)
+        od1 = torch.empty((nq, k), dtype=ddt, device=dev)
+        oi1 = torch.empty((nq, k), dtype=torch.int64, device=dev)
+        al, al_rr = [], []
+        for j in range(4 + 2 * nbatch):
+            qb_ = batches[j % nbatch]
+            index.search_device(qb_.data_ptr(), nq, k, od1.data_ptr(), oi1.data_ptr(), stream)
+            st_ = index.stats()
+            al.append(st_["scan_ms"])
+            al_rr.append(st_["rerank_ms"])
+            lib_bytes = float(st_["bytes_scanned"])
+        head_scan_ms = float(np.mean(al[4:]))
+        alone_rerank_ms = float(np.mean(al_rr[4:]))
+        index.set_option("profile", prof_every)
+        index.set_option("dense_debug", lib_opts.get("dense_debug", 0))
     head_cands = float(np.mean(cands)) / nq if cands else None
     head_fb = int(np.sum(fallbacks)) if fallbacks else 0
     head_mid = int(np.sum(mids)) if mids else 0
 
     # ---- one rank through the collective path: the merged answer must be the shard's own answer
-    if use_dist and world == 1 and result is not None:
+    if args.full and use_dist and world == 1 and result is not None:
         md, mi = result
         od = torch.empty((nq, k), dtype=ddt, device=dev)
         oi = torch.empty((nq, k), dtype=torch.int64, device=dev)
@@ -363,7 +390,7 @@ def bruteforce(args, torch, dist, _lib, world, rank, dev, use_dist, emit):
 
     # ---- parity spot check against the oracle (outside the timed region)
     parity = None
-    if not args.no_parity_check and world == 1:
+    if args.full and not args.no_parity_check and world == 1:
         from oracle import cpu_ref as O
         sub = min(n_local, max(20_000, 2_000_000 * 128 // max(d, 128)))   # (1 GB of rows through the oracle)
         idx_sub = _lib.DenseIndex(db.data_ptr(), n=sub, d=d, metric=metric, device_ptr=True, keepalive=db)
@@ -395,7 +422,7 @@ def bruteforce(args, torch, dist, _lib, world, rank, dev, use_dist, emit):
 
     # ---- other total batch sizes, same shards, after the timed region (every N: the N = 1 run gives the reference)
     extra = {}
-    for b in [int(x) for x in args.extra_batches.split(",") if x]:
+    for b in ([int(x) for x in args.extra_batches.split(",") if x] if args.full else []):
         if b == nq:
             continue
         qb = all_q[:b].contiguous()
@@ -429,7 +456,7 @@ def bruteforce(args, torch, dist, _lib, world, rank, dev, use_dist, emit):
     # ---- the other two kernels of the hot path on the same resident matrix (BASELINE config C3):
     # ITQ codes of all rows, then Hamming top-k over the unique codes.  Outside the timed region.
     other_paths = None
-    if world == 1 and not args.no_other_paths and d % 4 == 0:
+    if args.full and world == 1 and not args.no_other_paths and d % 4 == 0:
         def timed(fn, reps=5):
             fn()
             torch.cuda.synchronize()
@@ -491,13 +518,13 @@ def bruteforce(args, torch, dist, _lib, world, rank, dev, use_dist, emit):
         f32_bytes = float(n_local) * d * 4
         replay = None
         tpath = os.path.join(ROOT, "profiles", "latest_traffic.json")
-        if os.path.isfile(tpath) and n_local == 10_000_000 and d == 128 and not cosine:
+        if args.full and os.path.isfile(tpath) and n_local == 10_000_000 and d == 128 and not cosine:
             tj = json.load(open(tpath))
             replay = {"hbm_bytes_per_launch": tj.get("dense8_body_full_pass_hbm_bytes" if (int8_filter and nq <= 32 and lib_opts.get("dense_fused", 1) != 0)
                                                      else "dense8_scan_full_pass_hbm_bytes" if int8_filter else "dense_scan_full_pass_hbm_bytes"),
                       "file": "profiles/latest_traffic.json",
                       "note": "NOT measured in this run: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of the committed profile"}
-        achieved = streamed / (head_scan_ms * 1e-3) / 1e9 if head_scan_ms > 0 else 0.0
+        achieved = streamed / (head_scan_ms * 1e-3) / 1e9 if head_scan_ms else 0.0
         qp = 2.0 if nq <= 32 else 1.0
         gather_every = (args.gather_every if args.gather_every > 0 else 4) if use_dist else None
         fused_call = int8_filter and nq <= 32 and lib_opts.get("dense_fused", 1) != 0
@@ -553,7 +580,9 @@ def bruteforce(args, torch, dist, _lib, world, rank, dev, use_dist, emit):
                 "mid_tier_queries": head_mid,
                 "steps_with_stats": n_stats,
             },
-            "roofline": {
+        }
+        if args.full:      # (the kernel's own duration: blocking calls of their own after the timed region)
+            line["roofline"] = {
                 "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                 "frac": achieved / HBM_PEAK_GBS,
                 "traffic": None,
@@ -590,15 +619,14 @@ def bruteforce(args, torch, dist, _lib, world, rank, dev, use_dist, emit):
                 "frac_step_note": "streamed bytes / ms_per_step / peak: the whole search step (sample pass, threshold, re-rank, select, launch gaps) priced as if it were the scan",
                 "mfma_TFLOPs_executed": 2 * qp * n_pad * d_pad * (-(-nq // 32) * 32) / (head_scan_ms * 1e-3) / 1e12 if head_scan_ms > 0 else None,
                 "mfma_peak_TFLOPs": 2 * MFMA_BF16_PEAK_TF if int8_filter else MFMA_BF16_PEAK_TF,
-            },
-        }
+            }
         if parity is not None:
             line["parity_check"] = parity
         if extra:
             line["other_batches"] = extra
         if other_paths:
             line["other_paths"] = other_paths
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             rows, cq, dt = cpu_baseline(d, k, 7)
             line["cpu_baseline"] = {
                 "value": cq / dt * rows / n_total, "unit": "queries/s", "cores": 1, "kind": "port",
@@ -641,7 +669,7 @@ def bruteforce(args, torch, dist, _lib, world, rank, dev, use_dist, emit):
     index.close()
 
 
-def spawn_ranks(n: int) -> int:
+def spawn_ranks(n: int, dump_dir: str = "") -> int:
     """`python bench.py --gpus N` without a launcher: start the N ranks ourselves, as CHILD processes of a parent
     that never touches the GPU (torch is not even imported here), exactly the way the driver would
     (`python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py
@@ -656,6 +684,8 @@ def spawn_ranks(n: int) -> int:
     env.setdefault("OMP_NUM_THREADS", "4")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
+    if dump_dir:
+        cmd += ["--dump-outputs", os.path.abspath(dump_dir)]     # (the ranks run in the repository root)
     proc = subprocess.Popen(cmd, stdout=subprocess.PIPE, env=env, cwd=ROOT)
     line = None
     for raw in proc.stdout:                                  # children write everything but the line to stderr
@@ -675,8 +705,12 @@ def spawn_ranks(n: int) -> int:
 
 def main() -> None:
     args = parse_args()
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be at least 1")
+    if args.dump_outputs and args.workload in ("lsh_c3", "c5_hamming_shard"):
+        raise SystemExit("bench.py: --dump-outputs is implemented for the bruteforce and c4_cosine_shard workloads")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        sys.exit(spawn_ranks(args.gpus))
+        sys.exit(spawn_ranks(args.gpus, args.dump_outputs))
     # Only the one JSON line may reach stdout: libraries (RCCL prints a version banner) write to
     # fd 1 too, so fd 1 is pointed at stderr for the run and the line goes to the saved descriptor.
     sys.stdout.flush()

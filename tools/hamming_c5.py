@@ -108,7 +108,7 @@ def run(args, torch, dist, _lib, world, rank, dev, use_dist, emit):
     steps = max(1, args.steps if args.steps != 100 else 40)
     ms, kernel_ms, fb, lag = measure(nq, steps, args.warmup)
     extra = {}
-    for b in (1, 16):
+    for b in ((1, 16) if args.full else ()):
         if b != nq:
             m2, k2, f2, _ = measure(b, 40, 3)
             extra[f"batch_{b}"] = {"ms_per_step": m2, "queries_per_s": b * world / (m2 * 1e-3), "scan_kernel_ms": k2,
@@ -119,7 +119,7 @@ def run(args, torch, dist, _lib, world, rank, dev, use_dist, emit):
 
     # parity spot check (one rank): integer exact against torch's top-k of (distance, row) keys over the whole shard
     parity = None
-    if world == 1 and not args.no_parity_check:
+    if args.full and world == 1 and not args.no_parity_check:
         q = all_q[:2].contiguous()
         od = torch.empty((2, k), dtype=torch.int32, device=dev)
         oi = torch.empty((2, k), dtype=torch.int64, device=dev)
@@ -163,7 +163,7 @@ def run(args, torch, dist, _lib, world, rank, dev, use_dist, emit):
         }
         if parity is not None:
             line["parity_check"] = parity
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             from oracle import cpu_ref as O
             rng = np.random.default_rng(7)
             m = 4_000_000

@@ -105,10 +105,11 @@ def run(args, torch, dist, _lib, world, rank, dev, use_dist, emit, make_rows):
 
     head = measure(nq, args.lsh_n or k, args.steps, args.warmup)
     others = {}
-    for nc in (1000, 10000):
+    for nc in ((1000, 10000) if args.full else ()):
         if nc != (args.lsh_n or k):
             others[f"n_codes_{nc}"] = measure(nq, nc, max(3, args.steps // 4), 1)
-    others["batch_256_n_codes_%d" % (args.lsh_n or k)] = measure(256, args.lsh_n or k, max(3, args.steps // 4), 1)
+    if args.full:
+        others["batch_256_n_codes_%d" % (args.lsh_n or k)] = measure(256, args.lsh_n or k, max(3, args.steps // 4), 1)
 
     line = {
         "metric": "queries/sec + recall@k=100, LSH pipeline (10Mx128 -> 64-bit ITQ codes -> Hamming top-n -> bucket expansion -> exact re-rank)",
@@ -133,7 +134,7 @@ def run(args, torch, dist, _lib, world, rank, dev, use_dist, emit, make_rows):
                              "compaction, select, expansion, re-rank, select), which is why queries are batched"},
         "other_code_counts": others,
     }
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         from oracle import cpu_ref as O
         sub = 200_000
         dbh = db[:sub].cpu().numpy().astype(np.float64)           # the reference works on float64 descriptors by default

@@ -5,7 +5,7 @@ pre=$1; shift
 i=0
 for o in "$@"; do
   [ "$o" = "-" ] && o=""
-  python bench.py --gpus 1 --rows ${ROWS:-1000000} --dim ${DIM:-4096} --steps 20 --warmup 3 --no-other-paths --no-cpu-baseline --extra-batches "${EXTRA:-}" --lib-options "$o" > ${pre}_$i.json 2> ${pre}_$i.err || { tail -3 ${pre}_$i.err; exit 1; }
+  python bench.py --gpus 1 --rows ${ROWS:-1000000} --dim ${DIM:-4096} --steps 20 --warmup 3 --full --no-other-paths --no-cpu-baseline --extra-batches "${EXTRA:-}" --lib-options "$o" > ${pre}_$i.json 2> ${pre}_$i.err || { tail -3 ${pre}_$i.err; exit 1; }
   python - "$o" ${pre}_$i.json <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[2]).read().strip().splitlines()[-1]); r=d['roofline']
