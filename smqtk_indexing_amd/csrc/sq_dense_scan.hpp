@@ -323,6 +323,17 @@ __device__ __forceinline__ void mfma_fence_out(f32x16 (&acc)[QT]) {
     else
         asm volatile("s_nop 15" : "+v"(acc[0]));
 }
+// the pad of ONE accumulator in front of the skewed epilogue's first read of it (SKEW in dense_scan_kernel), for an
+// epilogue that starts N MFMAs after the last MFMA of the accumulator.  hipcc counts an MFMA as one wait state and a
+// path may hold nothing else between them (one that branches over the previous half's survivor block), so
+// N + (12 - N) reaches the 12 states an MFMA result needs before a VALU reads it whatever hipcc places around.  The
+// accumulator is an input of the pad (it waits for the MFMAs), not an output: a redefinition raises the register pressure
+// until hipcc parks A fragments in AGPRs and copies them back unpadded in front of the next MFMAs.
+template <int N>
+__device__ __forceinline__ void mfma_fence_acc(const f32x16& acc) {
+    static_assert(N >= 1 && N <= 12, "MFMAs between the accumulator's last MFMA and the read");
+    if constexpr (N < 12) asm volatile("s_nop %0" ::"n"(11 - N), "v"(acc));
+}
 // min of the 16 scores of a lane as eight VALU instructions that stay where they are written (asm volatile): the
 // skewed epilogue below places them between hand-issued MFMAs.  NaN scores lose (IEEE min), as with fminf.
 __device__ __forceinline__ float min16_pinned(const f32x16& v) {
@@ -808,8 +819,12 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void dense_scan_kernel(Dense
         // fragments stay in registers for the whole unit, so the order is free) -- and the epilogue of a half sits
         // between the MFMAs of the next one (tiles 0,1 of this unit under its tiles 2,3; tiles 2,3 under tiles 0,1 of
         // the following unit): with one wave per SIMD nothing else would keep the matrix pipe busy during the ~50-100
-        // vector instructions of the four epilogues.  An epilogue starts four MFMAs (128 cycles) after the last MFMA
-        // of its accumulators, which also covers the MFMA -> VALU read hazard hipcc does not know about.
+        // vector instructions of the four epilogues.  An epilogue starts five MFMAs after the last MFMA of its
+        // accumulators.  That distance alone does not cover the MFMA -> VALU read hazard hipcc does not see: hipcc
+        // counts an MFMA as one wait state, and where a path branches over the previous half's survivor block the five
+        // MFMAs are all that lies between (5 of the 12 states).  Each epilogue's first read therefore follows its own
+        // pad on that accumulator (mfma_fence_acc, sized by the MFMAs in between), a dependency rather than a position; tools/mfma_hazard_lint.py
+        // checks every path in the assembly.
 #ifdef SQ_NO_SKEW
         constexpr bool SKEW = false;  // measurement build
 #else
@@ -870,7 +885,11 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void dense_scan_kernel(Dense
                 if constexpr (SKEW) {
                     // minima + ballots in the shadow of the MFMAs; the (rare) survivors are written out where the
                     // MFMA stream has a seam anyway: before the half that overwrites their accumulators
+                    // each epilogue's first read sits behind a pad of its accumulator (mfma_fence_acc<MFMAs since the
+                    // accumulator's last one>)
+                    if (slot == 3) mfma_fence_acc<5>(acc[2]);   // MFMAs 31, 0 .. 3
                     if (slot == 3 && prev_valid) hit2 = finish_q(prev_sel, std::integral_constant<int, 2>{}, std::true_type{}, acc[2], std::integral_constant<int, (SL + 3) % 4>{});
+                    if (slot == 9) mfma_fence_acc<10>(acc[3]);  // MFMAs 0 .. 9
                     if (slot == 9 && prev_valid) hit3 = finish_q(prev_sel, std::integral_constant<int, 3>{}, std::true_type{}, acc[3], std::integral_constant<int, (SL + 3) % 4>{});
                     if (slot == 15 && prev_valid) {
                         if constexpr (!SAMPLE) {
@@ -878,8 +897,14 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void dense_scan_kernel(Dense
                             emit_q(prev_sel, std::integral_constant<int, 3>{}, acc[3], hit3);
                         }
                     }
-                    if (slot == 19) hit0 = finish_q(cur_sel, std::integral_constant<int, 0>{}, std::true_type{}, acc[0], std::integral_constant<int, SL % 4>{});
-                    if (slot == 25) hit1 = finish_q(cur_sel, std::integral_constant<int, 1>{}, std::true_type{}, acc[1], std::integral_constant<int, SL % 4>{});
+                    if (slot == 19) {
+                        mfma_fence_acc<5>(acc[0]);   // MFMAs 15 .. 19
+                        hit0 = finish_q(cur_sel, std::integral_constant<int, 0>{}, std::true_type{}, acc[0], std::integral_constant<int, SL % 4>{});
+                    }
+                    if (slot == 25) {
+                        mfma_fence_acc<10>(acc[1]);  // MFMAs 16 .. 25
+                        hit1 = finish_q(cur_sel, std::integral_constant<int, 1>{}, std::true_type{}, acc[1], std::integral_constant<int, SL % 4>{});
+                    }
                     if (slot == 31) {
                         if constexpr (!SAMPLE) {
                             emit_q(cur_sel, std::integral_constant<int, 0>{}, acc[0], hit0);

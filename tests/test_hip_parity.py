@@ -1358,11 +1358,39 @@ def test_k_beyond_the_one_workgroup_select():
         m.close()
 
 
+def _check_all_queries_f64(db, qs, dd, ii, k, metric, block=64):
+    """Each query's answer against float64 distances to all rows: the returned distances match the float64 value of
+    their own row (float32 L2: within the float32 rounding; cosine within 1e-7), no row outside the answer is nearer than its
+    k-th distance beyond that rounding, and ids are distinct."""
+    x = db.astype(np.float64)
+    xn = np.einsum("ij,ij->i", x, x)
+    for q0 in range(0, len(qs), block):
+        q = qs[q0:q0 + block].astype(np.float64)
+        if metric == "euclidean":
+            d2 = xn[None, :] - 2.0 * (q @ x.T) + np.einsum("ij,ij->i", q, q)[:, None]
+            full = np.sqrt(np.maximum(d2, 0.0))
+            tol = 1e-5 * (np.sqrt(xn.max()) + np.sqrt(np.einsum("ij,ij->i", q, q)).max())
+        else:
+            sim = (q @ x.T) / np.sqrt(xn)[None, :] / np.linalg.norm(q, axis=1)[:, None]
+            full = 2.0 * np.arccos(np.clip(sim, -1.0, 1.0)) / np.pi     # (metrics.py: angular distance, positive vectors)
+            tol = 1e-7                                                  # (arccos near sim = 1 amplifies the product's rounding)
+        for j in range(len(q)):
+            qi = q0 + j
+            ids, dist = ii[qi], dd[qi].astype(np.float64)
+            assert len(np.unique(ids)) == len(ids), "query %d: repeated ids" % qi
+            np.testing.assert_allclose(dist, full[j, ids], rtol=0, atol=tol, err_msg="query %d" % qi)
+            assert np.all(np.diff(dist) >= 0), "query %d: distances not ascending" % qi
+            out = np.ones(full.shape[1], bool)
+            out[ids] = False
+            assert full[j, out].min() >= full[j, ids].max() - 2 * tol, "query %d: a nearer row is missing" % qi
+
+
 @pytest.mark.parametrize("metric", ["euclidean", "cosine"])
 @pytest.mark.parametrize("nq,d", [(300, 128), (513, 100), (1024, 128)])
 def test_dense_large_batches(metric, nq, d):
     """Batches of several hundred queries (many groups of four query tiles per scan wave, a partial last group, a
-    partial last row tile): ids and float32 distances bit-identical to the oracle, no query on the exact path."""
+    partial last row tile): every query against a float64 reference, ids and float32 distances bit-identical to the
+    oracle on a sample, no query on the exact path."""
     rng = np.random.default_rng(nq + d)
     n = 200_000 + 17
     db = rng.standard_normal((n, d)).astype(np.float32)
@@ -1374,6 +1402,10 @@ def test_dense_large_batches(metric, nq, d):
     k = 20
     dd, ii = idx.search(qs, k)
     assert idx.stats()["fallback_queries"] == 0 and idx.stats()["scan_launches"] == 2
+    # every query against a float64 evaluation of all distances (one matrix product per block of queries): the ids
+    # of the k nearest (ties by row id, up to the float32 rounding of the reference) and their distances
+    _check_all_queries_f64(db, qs, dd, ii, k, metric)
+    # bit-exact oracle comparison on a sample
     for qi in list(range(0, nq, 37)) + [nq - 1]:
         rd, ri = O.dense_topk(db, qs[qi], k, metric)
         if metric == "euclidean":
