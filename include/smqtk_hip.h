@@ -135,7 +135,9 @@ int sq_itq_hash(const void* x, int x_dtype, int64_t n, int d,
  * The O(n) products of ItqFunctor.fit (impls/lsh_functor/itq.py:291-387) and
  * _find_itq_rotation (itq.py:239-289) with the descriptor matrix resident on
  * the device; the d x d eigen-decomposition and the b x b SVD per iteration stay
- * with the caller (numpy, as in the reference).  d <= 512, bits <= 256 (the outputs are tiled 128 x 128).
+ * with the caller (numpy, as in the reference).  d <= SQ_ITQFIT_MAX_D, bits <= SQ_ITQFIT_MAX_BITS (the outputs are
+ * tiled 128 x 128; beyond 512 dimensions the projection stages its basis slice by slice).  A covariance that the
+ * device cannot hold (d = 8192: 512 MB of float64) is refused with SQ_ERR_NOMEM.
  *   create:   x [n][d] of dtype; norm_ord as sq_itq_hash; out_mean[d] = column
  *             means of norm(x) (itq.py:330)
  *   set_mean: the mean values the model keeps (numpy stores them in x's dtype)
@@ -144,6 +146,8 @@ int sq_itq_hash(const void* x, int x_dtype, int64_t n, int d,
  *                                                                  (itq.py:362)
  *   iterate:  ux = sign(v . r), out_c[bits][bits] = ux^T . v   (itq.py:271-275)
  */
+#define SQ_ITQFIT_MAX_D 8192
+#define SQ_ITQFIT_MAX_BITS 256
 int sq_itqfit_create(const void* x, int dtype, int64_t n, int d, int norm_ord, int mem,
                      double* out_mean, sq_handle_t* out);
 int sq_itqfit_set_mean(sq_handle_t h, const double* mean);
@@ -279,7 +283,18 @@ int sq_dense_distances(const void* query, const void* rows, int dtype, int64_t n
 /* The same hashing with the MODEL resident: mean (values as f64, `mean_dtype` = the model's dtype, see above) and
  * rotation [d][bits] f64 are uploaded once; sq_itq_model_hash then moves only the rows and the codes (small
  * batches through pinned staging).  What ItqFunctor.get_hash costs per query vector in
- * LSHNearestNeighborIndex._nn (impls/nn_index/lsh.py:473): without this every call re-uploads the rotation. */
+ * LSHNearestNeighborIndex._nn (impls/nn_index/lsh.py:473): without this every call re-uploads the rotation.
+ * Rows of 513 .. 8192 elements (whole 16-byte pieces, normalize None / 2, codes up to 256 bits, at least 32 rows) go
+ * through the extra-wide certified filter; the model keeps that filter's image of the rotation from the first such
+ * call on.
+ * sq_get_stats on a model handle describes the last sq_itq_model_hash, in the fields of sq_stats_t:
+ *   scan_launches     filter kernels that streamed the rows (0: the float64 kernel hashed them)
+ *   candidates        bits the filter left undecided, evaluated in float64 (-1 after a SQ_MEM_DEVICE call, which is
+ *                     asynchronous: the device counter is not read back)
+ *   fallback_queries  rows hashed by the float64 kernel (all n with option "itq_exact", for fewer than 32 rows, for
+ *                     shapes no filter takes)
+ *   bytes_scanned     n * d * sizeof(element)
+ * the other fields are 0. */
 int sq_itq_model_create(const double* mean, int mean_dtype, const double* rotation, int d, int bits,
                         int norm_ord, sq_handle_t* out);
 int sq_itq_model_hash(sq_handle_t model, const void* x, int x_dtype, int64_t n, uint64_t* out_codes,

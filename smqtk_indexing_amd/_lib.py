@@ -32,6 +32,8 @@ SQ_NORM_L2 = 2
 SQ_NORM_INF = 1000
 SQ_NORM_NEG_INF = -1000
 SQ_MAX_K = 16384
+SQ_ITQFIT_MAX_D = 8192      # sq_itqfit_*: widest descriptor / longest code the device fit takes (smqtk_hip.h)
+SQ_ITQFIT_MAX_BITS = 256
 
 LIB_NAME = "libsmqtk_hip.so"
 # SMQTK_HIP_LIBRARY: another build of the same library (measurement: kernel variants side by side)
@@ -322,6 +324,12 @@ class ItqModel(_Handle):
             _check(load().sq_itq_model_hash(self.handle, _ptr(x), dt, int(x.shape[0]), _ptr(out), SQ_MEM_HOST, None),
                    "sq_itq_model_hash")
         return out
+
+    def stats(self) -> dict:
+        """Which path the last ``hash`` took (``sq_get_stats`` on a model handle): ``scan_launches`` filter kernels
+        that streamed the rows (0: the float64 kernel hashed them), ``candidates`` bits the filter left to float64,
+        ``fallback_queries`` rows hashed by the float64 kernel, ``bytes_scanned`` = n * d * itemsize."""
+        return get_stats(self.handle)
 
 
 class HammingIndex(_Handle):

@@ -170,6 +170,7 @@ extern "C" int sq_get_stats(sq_handle_t hid, sq_stats_t* out) {
     if (!out) return fail(SQ_ERR_INVALID, "sq_get_stats: null argument");
     HandleBase* h = lookup_handle(hid, H_DENSE);
     if (!h) h = lookup_handle(hid, H_HAMMING);
+    if (!h) h = lookup_handle(hid, H_ITQ);   // (the last sq_itq_model_hash: which path hashed the rows, smqtk_hip.h)
     if (!h) return fail(SQ_ERR_INVALID, "sq_get_stats: unknown handle");
     std::lock_guard<std::mutex> l(h->mu);
     *out = h->stats;

@@ -160,18 +160,24 @@ __global__ __launch_bounds__(256) void fit_gram_kernel(const T* __restrict__ x, 
 // v[row][c0..c0+bc) = (norm(x_row) - mean) . pc[:, c0..c0+bc): the columns of pc go through LDS a chunk at a time
 // (grid.y = chunk: [d][bc] doubles), the rows 32 at a time in k-slices of FIT_KC elements ([32][FIT_KC] doubles); a thread
 // owns one row and up to 16 of the chunk's columns (bc <= 128), accumulated in registers across the k-slices.
+// pck = d: all d rows of the column chunk stay in LDS (d <= 512: the geometry those shapes always had).  pck = FIT_KC:
+// only the k-slice that the staged rows meet is in LDS, reloaded per slice (d up to FIT_MAX_D: d * 8 columns stop
+// fitting the LDS at d ~ 2300).  Either way a (row, column) sum runs over k in ascending order in one accumulator.
 static constexpr int FIT_KC = 128;
 template <class T>
 __global__ __launch_bounds__(256) void fit_project_kernel(const T* __restrict__ x, const double* __restrict__ nrm,
                                                            const double* __restrict__ mean, const double* __restrict__ pc,
-                                                           long long n, int d, int b, int bc, double* __restrict__ v) {
-    extern __shared__ double s_pc[];  // [d][bc] then [32][FIT_KC]
-    double* s_x = s_pc + (size_t)d * bc;
+                                                           long long n, int d, int b, int bc, int pck, double* __restrict__ v) {
+    extern __shared__ double s_pc[];  // [pck][bc] then [32][FIT_KC]
+    double* s_x = s_pc + (size_t)pck * bc;
     const int c0 = blockIdx.y * bc;
     const int cw = b - c0 < bc ? b - c0 : bc;
-    for (int e = threadIdx.x; e < d * cw; e += 256) {
-        const int k = e / cw, j = e - k * cw;
-        s_pc[k * bc + j] = pc[(long long)k * b + c0 + j];
+    const bool sliced = pck < d;
+    if (!sliced) {
+        for (int e = threadIdx.x; e < d * cw; e += 256) {
+            const int k = e / cw, j = e - k * cw;
+            s_pc[k * bc + j] = pc[(long long)k * b + c0 + j];
+        }
     }
     const int r = threadIdx.x >> 3, c8 = threadIdx.x & 7;
     for (long long rb = (long long)blockIdx.x * 32; rb < n; rb += (long long)gridDim.x * 32) {
@@ -185,13 +191,20 @@ __global__ __launch_bounds__(256) void fit_project_kernel(const T* __restrict__ 
                 const int rr = e / kw, k = e - rr * kw;
                 s_x[rr * FIT_KC + k] = rb + rr < n ? fit_elem(x, rb + rr, d, k0 + k, nrm) - mean[k0 + k] : 0.0;
             }
+            if (sliced) {
+                for (int e = threadIdx.x; e < kw * cw; e += 256) {
+                    const int k = e / cw, j = e - k * cw;
+                    s_pc[k * bc + j] = pc[(long long)(k0 + k) * b + c0 + j];
+                }
+            }
+            const int kp = sliced ? 0 : k0;   // first staged row of pc
             __syncthreads();
 #pragma unroll
             for (int t = 0; t < 16; ++t) {
                 const int j = c8 + 8 * t;
                 if (j < cw) {
                     double a = acc[t];
-                    for (int k = 0; k < kw; ++k) a = fma(s_x[r * FIT_KC + k], s_pc[(k0 + k) * bc + j], a);
+                    for (int k = 0; k < kw; ++k) a = fma(s_x[r * FIT_KC + k], s_pc[(kp + k) * bc + j], a);
                     acc[t] = a;
                 }
             }
@@ -206,7 +219,8 @@ __global__ __launch_bounds__(256) void fit_project_kernel(const T* __restrict__ 
     }
 }
 
-static constexpr int FIT_MAX_D = 512, FIT_MAX_BITS = 256;
+static constexpr int FIT_MAX_D = SQ_ITQFIT_MAX_D, FIT_MAX_BITS = SQ_ITQFIT_MAX_BITS;
+static constexpr int FIT_PC_RESIDENT_D = 512;   // up to here all d rows of a column chunk of pc stay in LDS
 
 template <class T>
 static int fit_gram_cov(FitHandle* h, double* out_dev) {
@@ -265,7 +279,7 @@ extern "C" int sq_itqfit_create(const void* x, int dtype, int64_t n, int d, int 
     }
     int rc;
     if ((rc = h->mean.reserve((size_t)d * 8)) != SQ_OK) return bail(rc);
-    if ((rc = h->acc.reserve((size_t)std::max(d * d, FIT_MAX_BITS * FIT_MAX_BITS) * 8)) != SQ_OK) return bail(rc);
+    if ((rc = h->acc.reserve(std::max((size_t)d * d, (size_t)FIT_MAX_BITS * FIT_MAX_BITS) * 8)) != SQ_OK) return bail(rc);
     if (norm_ord == SQ_NORM_L2) {
         if ((rc = h->nrm.reserve((size_t)n * 8)) != SQ_OK) return bail(rc);
         const unsigned g = (unsigned)((n + 31) / 32);
@@ -329,11 +343,12 @@ extern "C" int sq_itqfit_project(sq_handle_t hid, const double* pc, int bits) {
     SQ_TRY(h->small.reserve((size_t)std::max(d, bits) * bits * 8));
     SQ_HIP(hipMemcpy(h->small.p, pc, (size_t)d * bits * 8, hipMemcpyHostToDevice));
     // columns of pc per pass: as many as fit the LDS beside the 32 staged rows (multiples of 8)
-    int bc = (int)((150 * 1024 / 8 - 32 * FIT_KC) / d) / 8 * 8;
+    const int pck = d <= FIT_PC_RESIDENT_D ? d : FIT_KC;
+    int bc = (int)((150 * 1024 / 8 - 32 * FIT_KC) / pck) / 8 * 8;
     if (bc > 128) bc = 128;
     if (bc > (bits + 7) / 8 * 8) bc = (bits + 7) / 8 * 8;
     if (bc < 8) return fail(SQ_ERR_UNSUPPORTED, "sq_itqfit_project: d=%d exceeds the LDS", d);
-    const size_t lds = ((size_t)d * bc + (size_t)32 * FIT_KC) * 8;
+    const size_t lds = ((size_t)pck * bc + (size_t)32 * FIT_KC) * 8;
     const unsigned chunks = (unsigned)((bits + bc - 1) / bc);
     const double* nrm = h->norm == SQ_NORM_L2 ? h->nrm.as<double>() : nullptr;
     const unsigned g = (unsigned)std::min<long long>((h->n + 31) / 32, 4ll * cu_count(h->device));
@@ -341,12 +356,12 @@ extern "C" int sq_itqfit_project(sq_handle_t hid, const double* pc, int bits) {
         SQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&fit_project_kernel<float>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         hipLaunchKernelGGL((fit_project_kernel<float>), dim3(g, chunks), dim3(256), lds, 0, (const float*)h->x, nrm,
-                           h->mean.as<double>(), h->small.as<double>(), h->n, d, bits, bc, h->v.as<double>());
+                           h->mean.as<double>(), h->small.as<double>(), h->n, d, bits, bc, pck, h->v.as<double>());
     } else {
         SQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&fit_project_kernel<double>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         hipLaunchKernelGGL((fit_project_kernel<double>), dim3(g, chunks), dim3(256), lds, 0, (const double*)h->x, nrm,
-                           h->mean.as<double>(), h->small.as<double>(), h->n, d, bits, bc, h->v.as<double>());
+                           h->mean.as<double>(), h->small.as<double>(), h->n, d, bits, bc, pck, h->v.as<double>());
     }
     SQ_HIP(hipDeviceSynchronize());
     return SQ_OK;

@@ -391,7 +391,10 @@ static int itq_launch_t(const ItqArgs& a0, hipStream_t st, int device) {
     ItqArgs a = a0;
     constexpr int NCOL = CT * 16, RSTRIDE = NCOL + 4, RT = 16 / CT;
     const size_t fixed = (size_t)a.d16 * 8;
-    const size_t budget = 76 * 1024;  // two workgroups per CU: one hides the other's load + conversion phase
+    size_t budget = 76 * 1024;  // two workgroups per CU: one hides the other's load + conversion phase
+    // (8192-d rows with 256-bit codes: the mean alone is 64 KB -- one workgroup per CU rather than a refusal; the
+    // chunking does not touch the order of a sum)
+    if (fixed + (size_t)16 * RSTRIDE * 8 > budget) budget = 156 * 1024;
     if (fixed + (size_t)16 * RSTRIDE * 8 > budget)
         return fail(SQ_ERR_UNSUPPORTED, "sq_itq_hash: d=%d too large for the LDS mean vector", a.d);
     int dk = (int)((budget - fixed) / ((size_t)RSTRIDE * 8));
@@ -525,8 +528,40 @@ static hipError_t scratch_alloc(void** p, size_t bytes, hipStream_t st, int devi
 
 static size_t align256(size_t v) { return (v + 255) / 256 * 256; }
 
+// Bits the filter left to float64: the set mask bits of every segment's entries (statistics of a model handle).
+static __global__ __launch_bounds__(256) void itq_count_undecided_kernel(const u64* __restrict__ seg, const u32* __restrict__ seg_cnt,
+                                                                          long long seg_cap, unsigned long long* __restrict__ total) {
+    const long long w = blockIdx.x;
+    const long long cnt_raw = seg_cnt[w];
+    const u32 cnt = (u32)(cnt_raw < seg_cap ? cnt_raw : seg_cap);
+    u32 c = 0;
+    for (u32 e = threadIdx.x; e < cnt; e += 256) c += (u32)__popc((u32)seg[w * seg_cap + e]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
+    if ((threadIdx.x & 63) == 0 && c) atomicAdd(total, (unsigned long long)c);
+}
+
+// What a resident model (sq_itq_model_*) hands to a launch: where the statistics of the call go, and a home for the
+// extra-wide filter's image of R, which depends on the model alone (8 MB of float16 planes plus 16 MB of float64
+// columns at 8192 x 256 bits: built once per model, not once per call).  The one-shot sq_itq_hash passes none.
+struct ItqCallCtx {
+    DevBuf* prep = nullptr;        // the model part of the extra-wide filter's scratch
+    bool* prep_valid = nullptr;
+    unsigned long long* cand_dev = nullptr;   // device counter: bits left to float64 (zeroed by the caller)
+    long long filter_launches = 0;            // filter kernels that streamed the rows
+    long long fallback_rows = 0;              // rows hashed by the float64 kernel
+};
+
+static void itq_count_undecided(ItqCallCtx* ctx, const u64* seg, const u32* seg_cnt, long long seg_cap, long long nwaves,
+                                hipStream_t st) {
+    if (!ctx) return;
+    ctx->filter_launches += 1;
+    if (ctx->cand_dev)
+        hipLaunchKernelGGL(itq_count_undecided_kernel, dim3((unsigned)nwaves), dim3(256), 0, st, seg, seg_cnt, seg_cap, ctx->cand_dev);
+}
+
 // float32 rows through the filter; the rows it cannot decide through the float64 kernel.
-static int itq_fast_path(const ItqArgs& a, const ItqFastGeom& g, hipStream_t st, int device) {
+static int itq_fast_path(const ItqArgs& a, const ItqFastGeom& g, hipStream_t st, int device, ItqCallCtx* ctx) {
     const int pc = a.words * 64;
     const bool l2 = a.norm == SQ_NORM_L2;
     const long long n_tiles = (a.n + 31) / 32;
@@ -587,6 +622,7 @@ static int itq_fast_path(const ItqArgs& a, const ItqFastGeom& g, hipStream_t st,
     // the undecided bits, one float64 dot product each, straight from the per-wave segments
     hipLaunchKernelGGL(itq_fix_bits_kernel, dim3((unsigned)nwaves, ITQ_FIX_PARTS), dim3(256), 0, st, a, fa.seg, fa.seg_cnt, seg_cap,
                        reinterpret_cast<const double*>(base + o_rt));
+    itq_count_undecided(ctx, fa.seg, fa.seg_cnt, seg_cap, nwaves, st);
     return done(rc);
 }
 
@@ -602,7 +638,7 @@ static bool itq_wide_applies(const ItqArgs& a) {
 }
 
 template <class T>
-static int itq_wide_path(const ItqArgs& a, hipStream_t st, int device) {
+static int itq_wide_path(const ItqArgs& a, hipStream_t st, int device, ItqCallCtx* ctx) {
     const int pc = a.words * 64, ct = a.words * 2;
     const bool l2 = a.norm == SQ_NORM_L2;
     const long long n_tiles = (a.n + 31) / 32;
@@ -698,19 +734,148 @@ static int itq_wide_path(const ItqArgs& a, hipStream_t st, int device) {
     }
     hipLaunchKernelGGL((itq_fix_bits_wide_kernel<T>), dim3((unsigned)nwaves, ITQ_FIX_PARTS), dim3(256), 0, st, a, wa.seg, wa.seg_cnt, seg_cap,
                        reinterpret_cast<const double*>(base + o_rt));
+    itq_count_undecided(ctx, wa.seg, wa.seg_cnt, seg_cap, nwaves, st);
+    return done(SQ_OK);
+}
+
+}  // namespace sq
+#include "sq_itq_xwide.hpp"   // (needs ItqArgs, f64x4 and the numpy-order helpers above)
+namespace sq {
+
+// The extra-wide filter (sq_itq_xwide.hpp): 512 < d <= 8192, float32 or float64 rows of whole 16-byte pieces.
+template <class T>
+static bool itq_xwide_applies(const ItqArgs& a) {
+    return a.d >= ITQX_MIN_D && a.d <= ITQX_MAX_D && a.words <= 4 && a.n >= 32 && a.n < (1ll << 29) &&
+           (reinterpret_cast<uintptr_t>(a.x) & 15u) == 0 && ((size_t)a.d * sizeof(T)) % 16 == 0 && !a.exact &&
+           (a.norm == SQ_NORM_NONE || a.norm == SQ_NORM_L2);
+}
+
+template <class T, bool NORMED, int CT>
+static int itq_xwide_launch_t(const ItqXwideArgs& xa, int nrb, hipStream_t st) {
+    constexpr size_t lds = 2 * (size_t)CT * 8192 + 3 * (size_t)CT * 32 * 4;
+    static std::atomic<unsigned long long> attr_done{0};
+    SQ_TRY(ensure_dyn_lds(reinterpret_cast<const void*>(&itq_xwide_kernel<T, NORMED, CT>), 160 * 1024, attr_done));
+    hipLaunchKernelGGL((itq_xwide_kernel<T, NORMED, CT>), dim3((unsigned)nrb), dim3(ITQX_WAVES * 64), lds, st, xa);
+    SQ_HIP(hipGetLastError());
+    return SQ_OK;
+}
+
+template <class T>
+static int itq_xwide_path(const ItqArgs& a, hipStream_t st, int device, ItqCallCtx* ctx) {
+    const int pc = a.words * 64, ct = a.words * 2;
+    const bool l2 = a.norm == SQ_NORM_L2;
+    const long long n_tiles = (a.n + 31) / 32;
+    int nrb = cu_count(device) * (ct <= 2 ? 2 : 1);   // (two workgroups per CU fit 256 registers only with two column tiles)
+    if ((long long)nrb * ITQX_WAVES > n_tiles) nrb = (int)((n_tiles + ITQX_WAVES - 1) / ITQX_WAVES);
+    const long long nwaves = (long long)nrb * ITQX_WAVES;
+    const long long rounds = (n_tiles + nwaves - 1) / nwaves;
+    const long long seg_cap = rounds * 32 * ct;   // every (row, column tile) of a wave's tiles
+    const int dp = (a.d + 127) / 128 * 128;
+    const size_t img_bytes = (size_t)pc * dp * 4;
+    // the model part: colnorm | c_b | c_b error | cabs | slab image | R^T float64
+    size_t moff = 0;
+    auto mtake = [&](size_t bytes) {
+        const size_t at = moff;
+        moff += align256(bytes);
+        return at;
+    };
+    const size_t o_cn = mtake((size_t)pc * 4), o_cb = mtake((size_t)pc * 4), o_cbe = mtake((size_t)pc * 4);
+    const size_t o_cabs = mtake((size_t)pc * 4), o_ximg = mtake(img_bytes), o_rt = mtake((size_t)pc * a.d * 8);
+    // the call part: segments | counts [| prep's image, while the model part is built]
+    const bool cached = ctx && ctx->prep && *ctx->prep_valid;
+    const bool keep = ctx && ctx->prep;
+    size_t coff = 0;
+    auto ctake = [&](size_t bytes) {
+        const size_t at = coff;
+        coff += align256(bytes);
+        return at;
+    };
+    const size_t o_seg = ctake((size_t)nwaves * seg_cap * 8), o_cnt = ctake((size_t)nwaves * 4);
+    const size_t o_img = cached ? 0 : ctake(img_bytes);
+    const size_t o_model = keep ? 0 : ctake(moff);
+    unsigned char* cbase = nullptr;
+    unsigned char* mbase = nullptr;
+    if (keep) {
+        SQ_TRY(ctx->prep->reserve(moff));
+        mbase = ctx->prep->as<unsigned char>();
+    }
+    SQ_HIP(scratch_alloc(reinterpret_cast<void**>(&cbase), coff, st, device));
+    if (!keep) mbase = cbase + o_model;
+    auto done = [&](int rc) {
+        (void)hipFreeAsync(cbase, st);
+        return rc;
+    };
+    if (!cached) {
+        // relative error of x . R_b per unit |x||R_b| (sq_itq_xwide.hpp): the split, the dropped x_lo R_lo, the float32
+        // accumulation flushed per 64-k slab (192 products each, then ceil(d / 64) additions), the float32 scale /
+        // subtract [+ 2^-18: |x|^2, normalize=2]
+        const double u24 = 5.9604644775390625e-08;
+        const int nslab = (a.d + ITQX_SLAB_K - 1) / ITQX_SLAB_K;
+        const double eps_rel = ((9.5367431640625e-07 + 4.76837158203125e-07) * 1.001 +
+                                (1.5 * (3.0 * ITQX_SLAB_K + 8.0) + 1.5 * (nslab + 1.0)) * u24 * (1.0 + 1.0 / 512.0) +
+                                9.5367431640625e-07 + (l2 ? 3.814697265625e-06 : 0.0)) * 1.001;
+        SQ_HIP(hipMemsetAsync(cbase + o_img, 0, img_bytes, st));   // (k beyond d: finite zeros under zero row fragments)
+        hipLaunchKernelGGL(itq_fast_prep_kernel, dim3((unsigned)pc), dim3(256), 0, st, a.mean, a.rot, a.d, a.bits, a.pad,
+                           reinterpret_cast<unsigned short*>(cbase + o_img), reinterpret_cast<float*>(mbase + o_cn),
+                           reinterpret_cast<float*>(mbase + o_cb), reinterpret_cast<float*>(mbase + o_cbe),
+                           reinterpret_cast<double*>(mbase + o_rt), eps_rel, reinterpret_cast<float*>(mbase + o_cabs));
+        const long long chunks = (long long)(img_bytes / 16);
+        hipLaunchKernelGGL(itq_xwide_relayout_kernel, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, st,
+                           reinterpret_cast<const uint4*>(cbase + o_img), reinterpret_cast<uint4*>(mbase + o_ximg), dp, ct, chunks);
+        SQ_HIP(hipGetLastError());
+        if (keep) *ctx->prep_valid = true;
+    }
+    ItqXwideArgs xa{};
+    xa.x = a.x;
+    xa.n = a.n;
+    xa.d = a.d;
+    xa.ximage = reinterpret_cast<const uint4*>(mbase + o_ximg);
+    xa.colnorm = reinterpret_cast<const float*>(mbase + o_cn);
+    xa.cb32 = reinterpret_cast<const float*>(mbase + o_cb);
+    xa.cberr = reinterpret_cast<const float*>(mbase + o_cbe);
+    xa.cabs = reinterpret_cast<const float*>(mbase + o_cabs);
+    xa.out = a.out;
+    xa.words = a.words;
+    xa.pad = a.pad;
+    xa.bits = a.bits;
+    xa.seg = reinterpret_cast<u64*>(cbase + o_seg);
+    xa.seg_cnt = reinterpret_cast<u32*>(cbase + o_cnt);
+    xa.seg_cap = seg_cap;
+    xa.n_tiles = n_tiles;
+    xa.nslab = (a.d + ITQX_SLAB_K - 1) / ITQX_SLAB_K;
+    int rc;
+#define SQ_ITQX_CASE(CTv)                                                                              \
+    case CTv:                                                                                          \
+        rc = l2 ? itq_xwide_launch_t<T, true, CTv>(xa, nrb, st) : itq_xwide_launch_t<T, false, CTv>(xa, nrb, st); \
+        break;
+    switch (ct) {
+        SQ_ITQX_CASE(2)
+        SQ_ITQX_CASE(4)
+        SQ_ITQX_CASE(6)
+        default:
+        SQ_ITQX_CASE(8)
+    }
+#undef SQ_ITQX_CASE
+    if (rc != SQ_OK) return done(rc);
+    hipLaunchKernelGGL((itq_fix_bits_xwide_kernel<T>), dim3((unsigned)nwaves, ITQ_FIX_PARTS), dim3(256), 0, st, a, xa.seg, xa.seg_cnt,
+                       seg_cap, reinterpret_cast<const double*>(mbase + o_rt));
+    SQ_HIP(hipGetLastError());
+    itq_count_undecided(ctx, xa.seg, xa.seg_cnt, seg_cap, nwaves, st);
     return done(SQ_OK);
 }
 
 template <class T>
-static int itq_launch(const ItqArgs& a0, hipStream_t st, int device) {
+static int itq_launch(const ItqArgs& a0, hipStream_t st, int device, ItqCallCtx* ctx = nullptr) {
     ItqArgs a = a0;
     if constexpr (sizeof(T) == 4) {
         const ItqFastGeom g = itq_fast_geometry(a.d, a.words);
         if (g.stages >= 2 && a.n >= 32 && a.n < (1ll << 30) && (reinterpret_cast<uintptr_t>(a.x) & 15u) == 0 &&
             !a.exact && (a.norm == SQ_NORM_NONE || a.norm == SQ_NORM_L2))  // (the other orders: float64 kernel)
-            return itq_fast_path(a, g, st, device);
+            return itq_fast_path(a, g, st, device, ctx);
     }
-    if (itq_wide_applies<T>(a)) return itq_wide_path<T>(a, st, device);
+    if (itq_wide_applies<T>(a)) return itq_wide_path<T>(a, st, device, ctx);
+    if (itq_xwide_applies<T>(a)) return itq_xwide_path<T>(a, st, device, ctx);
+    if (ctx) ctx->fallback_rows += a.n;
     void* nrm = nullptr;
     if (a.norm != SQ_NORM_NONE) {  // stream-ordered scratch: [n] norms in x's dtype
         SQ_HIP(scratch_alloc(&nrm, (size_t)a.n * sizeof(T), st, device));
@@ -802,11 +967,16 @@ extern "C" int sq_itq_hash(const void* x, int x_dtype, int64_t n, int d, const d
 namespace sq {
 struct ItqModelHandle : HandleBase {
     DevBuf mean, rot, x_dev, out_dev;
+    DevBuf xprep;            // the extra-wide filter's image of the model (sq_itq_xwide.hpp), built by the first call that needs it
+    bool xprep_valid = false;
+    DevBuf cand;             // one device counter: bits the last call's filter left to float64
     HostPinned stage;   // [rows | codes] of one small batch
+    HostPinned cand_host;
     int d = 0, bits = 0, norm = SQ_NORM_NONE, mean_dtype = SQ_DTYPE_F64;
     ~ItqModelHandle() override {
-        for (DevBuf* b : {&mean, &rot, &x_dev, &out_dev}) b->release();
+        for (DevBuf* b : {&mean, &rot, &x_dev, &out_dev, &xprep, &cand}) b->release();
         stage.release();
+        cand_host.release();
     }
 };
 }  // namespace sq
@@ -831,6 +1001,8 @@ extern "C" int sq_itq_model_create(const double* mean, int mean_dtype, const dou
     if (hipGetDevice(&h->device) != hipSuccess) return bail(fail(SQ_ERR_HIP, "sq_itq_model_create: no HIP device"));
     int rc = h->mean.reserve((size_t)d * 8);
     if (rc == SQ_OK) rc = h->rot.reserve((size_t)d * bits * 8);
+    if (rc == SQ_OK) rc = h->cand.reserve(8);
+    if (rc == SQ_OK) rc = h->cand_host.reserve(8);
     if (rc != SQ_OK) return bail(rc);
     if (hipMemcpy(h->mean.p, mean, (size_t)d * 8, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(h->rot.p, rotation, (size_t)d * bits * 8, hipMemcpyHostToDevice) != hipSuccess)
@@ -864,10 +1036,25 @@ extern "C" int sq_itq_model_hash(sq_handle_t hid, const void* x, int x_dtype, in
     a.d16 = (h->d + 15) / 16 * 16;
     a.mean = h->mean.as<double>();
     a.rot = h->rot.as<double>();
+    // statistics of this call (sq_get_stats on the model handle, smqtk_hip.h)
+    ItqCallCtx ctx;
+    ctx.prep = &h->xprep;
+    ctx.prep_valid = &h->xprep_valid;
+    ctx.cand_dev = h->cand.as<unsigned long long>();
+    if (n >= 32) SQ_HIP(hipMemsetAsync(h->cand.p, 0, 8, st));   // (no filter takes fewer rows: one query vector pays nothing)
+    auto record = [&](long long candidates) {
+        h->stats = sq_stats_t{};
+        h->stats.scan_launches = ctx.filter_launches;
+        h->stats.fallback_queries = ctx.fallback_rows;
+        h->stats.candidates = candidates;
+        h->stats.bytes_scanned = (int64_t)((size_t)n * h->d * esz);
+    };
     if (mem == SQ_MEM_DEVICE) {
         a.x = x;
         a.out = reinterpret_cast<u64*>(out_codes);
-        return x_dtype == SQ_DTYPE_F32 ? itq_launch<float>(a, st, h->device) : itq_launch<double>(a, st, h->device);
+        const int rc = x_dtype == SQ_DTYPE_F32 ? itq_launch<float>(a, st, h->device, &ctx) : itq_launch<double>(a, st, h->device, &ctx);
+        if (rc == SQ_OK) record(-1);   // (the call is asynchronous: the device counter is not read back)
+        return rc;
     }
     const size_t xb = (size_t)n * h->d * esz, ob = (size_t)n * words * 8;
     SQ_TRY(h->x_dev.reserve(xb));
@@ -885,10 +1072,12 @@ extern "C" int sq_itq_model_hash(sq_handle_t hid, const void* x, int x_dtype, in
     SQ_HIP(hipMemcpyAsync(h->x_dev.p, src, xb, hipMemcpyHostToDevice, st));
     a.x = h->x_dev.p;
     a.out = h->out_dev.as<u64>();
-    SQ_TRY(x_dtype == SQ_DTYPE_F32 ? itq_launch<float>(a, st, h->device) : itq_launch<double>(a, st, h->device));
+    SQ_TRY(x_dtype == SQ_DTYPE_F32 ? itq_launch<float>(a, st, h->device, &ctx) : itq_launch<double>(a, st, h->device, &ctx));
     SQ_HIP(hipMemcpyAsync(dst, h->out_dev.p, ob, hipMemcpyDeviceToHost, st));
+    if (ctx.filter_launches) SQ_HIP(hipMemcpyAsync(h->cand_host.p, h->cand.p, 8, hipMemcpyDeviceToHost, st));
     SQ_HIP(stream_wait(st));
     if (staged) memcpy(out_codes, dst, ob);
+    record(ctx.filter_launches ? (long long)*static_cast<unsigned long long*>(h->cand_host.p) : 0);
     return SQ_OK;
 }
 
