@@ -234,6 +234,34 @@ int sq_dense_info(sq_handle_t h, int64_t* out, int n_out);
  * (impls/nn_index/faiss.py:561-640), in place of a rebuild, when no existing descriptor is replaced.
  * SQ_ERR_UNSUPPORTED for an index that borrows a device matrix (the caller owns that allocation). */
 int sq_dense_append(sq_handle_t h, const float* rows, int64_t n_add, int mem);
+/* Take rows out of the resident index in place: what FaissNearestNeighborsIndex._remove_from_index does with
+ * remove_ids (impls/nn_index/faiss.py:644-694, :675), instead of asking every search for k + removed neighbours and
+ * filtering on the host.  ids[m] (host memory) are ids as searches return them (id_base + row).  All or nothing: an id
+ * out of range, already removed, or listed twice gives SQ_ERR_INVALID and changes nothing (so does a call that would
+ * leave no row: an index holds at least one, as at create).  The call first finishes the asynchronous searches in
+ * flight, as sq_dense_append does.  It works for an index that owns its matrix and for one that borrows the caller's
+ * device matrix: only the library's own copies are written (a bitmap of n / 8 bytes, allocated at the first removal,
+ * and the per-row term of each scan copy that says "never emitted"), the float32 rows are not.
+ * Afterwards a search returns, bit for bit, what an index created from the remaining rows returns, with the original
+ * ids: ids stay stable, sq_dense_append appends behind the old rows (holes are not reused) until sq_dense_compact.
+ * k is clamped to the rows that are left: when k exceeds them the tail is id -1 / distance +inf, exactly as for k
+ * beyond the number of rows (Conventions above).  The search costs what it cost before: the same bytes are streamed and a
+ * removed row is never a candidate. */
+int sq_dense_remove(sq_handle_t h, const int64_t* ids, int64_t m);
+/* Drop the removed rows for good (faiss.py:644-694: what remove_ids leaves behind): the remaining float32 rows are
+ * gathered on the device in their order -- into a second buffer when memory allows (the old one is then freed and the
+ * matrix shrinks), else in place, front to back through a 64 MB bounce buffer; nothing crosses PCIe -- and renumbered
+ * id_base + 0 ...; old_to_new[n] (host memory, n = rows before the call; may be NULL) receives the new id of each old
+ * row, -1 for a removed one.  Statistics and scan copies are then rebuilt from the gathered rows by the kernels of
+ * sq_dense_create: the result is the index sq_dense_create would build from them, with BOTH the L2 filter's origin
+ * (column means) and the int8 clamp chosen afresh from the remaining rows.  Captured call graphs of the old shape are
+ * dropped; asynchronous calls in flight are finished first.  With nothing removed the call changes nothing.
+ * SQ_ERR_UNSUPPORTED for an index that borrows the caller's device matrix.  A failure to allocate after the gather has
+ * begun leaves the handle fit for sq_dense_destroy only. */
+int sq_dense_compact(sq_handle_t h, int64_t* old_to_new);
+/* Rows the index holds (removed ones included: the next appended row gets id_base + *n_rows) and rows not removed
+ * (faiss.py:644-694 keeps the same two numbers: the next index and ntotal).  Either pointer may be NULL. */
+int sq_dense_count(sq_handle_t h, int64_t* n_rows, int64_t* n_live);
 
 /* queries: [nq][d] f32.  out_dist: float32 [nq][k] for SQ_METRIC_L2,
  * float64 [nq][k] for SQ_METRIC_COSINE.  out_idx int64 [nq][k]. */
@@ -242,7 +270,7 @@ int sq_dense_search(sq_handle_t h, const float* queries, int nq, int k,
 /* mem = SQ_MEM_DEVICE_ASYNC: the call enqueues its kernels and returns without waiting for them; `queries`
  * are read in the order of `stream`.  The results of call i are final -- certified, uncertified queries redone,
  * complete in out_dist / out_idx -- when the NEXT call on the handle (another search, sq_dense_sync,
- * sq_dense_append, sq_dense_destroy) returns; until then the call's `queries`, `out_dist` and `out_idx` must
+ * sq_dense_append, sq_dense_remove, sq_dense_compact, sq_dense_destroy) returns; until then the call's `queries`, `out_dist` and `out_idx` must
  * stay valid and untouched (so consecutive asynchronous calls alternate between two output buffers).  The device
  * never idles between calls, and with option "dense_async_streams" = 2 (default) consecutive calls run on two
  * internal streams so that the short kernels ending call i overlap those starting call i + 1.  sq_get_stats

@@ -45,7 +45,8 @@ EXPORTS = (
     "sq_set_option", "sq_handle_set_option", "sq_handle_reset_options", "sq_get_stats", "sq_itq_hash",
     "sq_itq_model_create", "sq_itq_model_hash", "sq_itq_model_destroy",
     "sq_hamming_create", "sq_hamming_search", "sq_hamming_sync", "sq_hamming_append", "sq_hamming_remove", "sq_hamming_info", "sq_hamming_destroy",
-    "sq_dense_create", "sq_dense_create_opts", "sq_dense_info", "sq_dense_append", "sq_dense_search", "sq_dense_sync", "sq_dense_destroy",
+    "sq_dense_create", "sq_dense_create_opts", "sq_dense_info", "sq_dense_append", "sq_dense_remove", "sq_dense_compact", "sq_dense_count",
+    "sq_dense_search", "sq_dense_sync", "sq_dense_destroy",
     "sq_dense_distances", "sq_merge_topk", "sq_merge_topk_strided",
     "sq_rows_create", "sq_rows_append", "sq_rows_rerank", "sq_rows_set_buckets", "sq_lsh_query", "sq_rows_destroy",
     "sq_itqfit_create", "sq_itqfit_set_mean", "sq_itqfit_cov", "sq_itqfit_project", "sq_itqfit_iterate",
@@ -101,6 +102,9 @@ def _declare(lib: ctypes.CDLL) -> None:
                                          ctypes.POINTER(c_i64)]
     lib.sq_dense_info.argtypes = [c_i64, ctypes.POINTER(c_i64), c_int]
     lib.sq_dense_append.argtypes = [c_i64, c_vp, c_i64, c_int]
+    lib.sq_dense_remove.argtypes = [c_i64, c_vp, c_i64]
+    lib.sq_dense_compact.argtypes = [c_i64, c_vp]
+    lib.sq_dense_count.argtypes = [c_i64, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]
     lib.sq_dense_search.argtypes = [c_i64, c_vp, c_int, c_int, c_vp, c_vp, c_int, c_vp]
     lib.sq_dense_sync.argtypes = [c_i64]
     lib.sq_dense_destroy.argtypes = [c_i64]
@@ -477,6 +481,30 @@ class DenseIndex(_Handle):
             return
         _check(load().sq_dense_append(self.handle, ptr, m, mem), "sq_dense_append")
         self.n += m
+
+    def remove(self, ids) -> None:
+        """Take the rows with these ids (as searches return them: ``id_base`` + row) out of the index in place
+        (``sq_dense_remove``).  All or nothing: an id out of range, already removed or listed twice raises and
+        changes nothing.  Ids stay stable until :meth:`compact`."""
+        ids = np.ascontiguousarray(np.asarray(ids, dtype=np.int64).reshape(-1))
+        if ids.size == 0:
+            return
+        _check(load().sq_dense_remove(self.handle, _ptr(ids), int(ids.size)), "sq_dense_remove")
+
+    def compact(self) -> np.ndarray:
+        """Drop the removed rows on the device and renumber the rest ``id_base + 0 ...`` in their order
+        (``sq_dense_compact``).  Returns ``old_to_new``: the new id of every old row, ``-1`` for a removed one."""
+        rows, _ = self.count()
+        old_to_new = np.empty(rows, dtype=np.int64)
+        _check(load().sq_dense_compact(self.handle, _ptr(old_to_new)), "sq_dense_compact")
+        self.n = self.count()[0]
+        return old_to_new
+
+    def count(self) -> Tuple[int, int]:
+        """``(rows, live)``: rows the index holds, removed ones included, and rows not removed (``sq_dense_count``)."""
+        rows, live = ctypes.c_int64(0), ctypes.c_int64(0)
+        _check(load().sq_dense_count(self.handle, ctypes.byref(rows), ctypes.byref(live)), "sq_dense_count")
+        return int(rows.value), int(live.value)
 
     def search_device(self, q_ptr: int, nq: int, k: int, out_dist_ptr: int, out_idx_ptr: int, stream: int = 0) -> None:
         _check(load().sq_dense_search(self.handle, _ptr(q_ptr), int(nq), int(k), _ptr(out_dist_ptr),

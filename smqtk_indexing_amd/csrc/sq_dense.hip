@@ -34,6 +34,7 @@
 #include "sq_dense_i8.hpp"
 #include "sq_dense_wide.hpp"
 #include "sq_dense_tighten.hpp"
+#include "sq_dense_remove.hpp"
 
 namespace sq {
 
@@ -114,6 +115,13 @@ struct DenseHandle : HandleBase {
     long long build_us = 0, build8_us = 0;   // sq_dense_info: wall time of sq_dense_create / of its int8 part
     long long n8_built = 0;     // rows the clamp was chosen from (an index twice that size chooses again)
     DevBuf norms1;  // L2: |x|^2 (1 - alpha) for one query plane (`norms`: two planes)
+    // rows taken out by sq_dense_remove (sq_dense_remove.hpp): a bitmap over the n rows, allocated at the first removal
+    // (null until then: every kernel that takes it does exactly what it did).  Ids stay stable: removed rows keep their
+    // place until sq_dense_compact.
+    DevBuf dead;
+    long long dead_words = 0;   // 32-bit words of `dead` in use (zero behind the rows)
+    long long n_live = 0;       // rows not removed: what k is clamped to
+    const u32* deadp() const { return dead.as<u32>(); }
     DevBuf zeros;   // cosine: the 32 zero "norms" every tile of an AGPR-configuration scan starts from (norm_step 0)
     static constexpr int kMaxDepth = 6;
     DenseSlot slot[kMaxDepth];
@@ -137,7 +145,7 @@ struct DenseHandle : HandleBase {
     hipEvent_t ev_ref = nullptr;   // SQ_TRACE (measurement aid): the origin of the printed call timelines
     ~DenseHandle() override {
         if (ev_ref) (void)hipEventDestroy(ev_ref);
-        for (DevBuf* b : {&owned, &scan, &scan8, &nrow8, &norms, &norms1, &zeros, &center, &cos_nx, &q_dev, &out_dist_dev, &out_idx_dev, &big_keys,
+        for (DevBuf* b : {&dead, &owned, &scan, &scan8, &nrow8, &norms, &norms1, &zeros, &center, &cos_nx, &q_dev, &out_dist_dev, &out_idx_dev, &big_keys,
                           &fb_sample, &fb_keys, &fb_out, &scratch, &fb_cnt, &fb_sort, &mid_q, &mid_planes, &mid_small, &mid_qal,
                           &mid_wave_out, &mid_wave_cnt, &mid_keys, &mid_out, &mid_sample, &mid_cos_center, &mid_cos_rows})
             b->release();
@@ -162,6 +170,38 @@ struct HostProf {
 static HostProf g_hostprof;
 
 // -------------------------------------------------------------- host driver
+template <class F>
+static F with_dead(F f, const u32* dead) {   // a finalisation whose keys may hold removed rows (the exact paths)
+    f.dead = dead;
+    return f;
+}
+// The per-row terms of the handle's copies that say "never emitted" (sq_dense_remove.hpp)
+static DenseDeadTerms dense_dead_terms(const DenseHandle* h) {
+    const bool cosine = h->metric == SQ_METRIC_COSINE;
+    DenseDeadTerms t{};
+    if (!cosine) {
+        t.norms = h->norms.as<float>();
+        t.norms1 = h->norms1.as<float>();
+    }
+    if (h->use8 && h->nrow8.p) t.nrow8 = h->nrow8.as<float>();
+    if (cosine && h->scan.p) {
+        t.scan = h->scan.as<uint4>();
+        t.scan_cpr = h->d_pad / 8;
+    }
+    if (cosine && h->mid_cos_rows.p && h->mid_cos_n == h->n) {
+        t.mid_cos = h->mid_cos_rows.as<float>();
+        t.mid_cos_ld = h->mid_cos_ld;
+    }
+    return t;
+}
+// ... written again for the removed rows from `row_from` on, after a build kernel has rewritten the terms there
+static int dense_dead_reapply(DenseHandle* h, long long row_from, hipStream_t st) {
+    if (!h->dead.p || row_from >= h->n) return SQ_OK;
+    hipLaunchKernelGGL(dense_dead_reapply_kernel, dim3((unsigned)((h->n - row_from + 255) / 256)), dim3(256), 0, st, h->deadp(), row_from,
+                       h->n, dense_dead_terms(h));
+    SQ_HIP(hipGetLastError());
+    return SQ_OK;
+}
 static constexpr int kSelectLdsKeys64 = 16384;
 static constexpr int kSelectLdsKeys128 = 7168;
 
@@ -411,7 +451,7 @@ static int dense_enqueue(DenseHandle* h, DenseSlot& s, const float* q, int nq, i
                          hipStream_t st, bool use_event) {
     const long long n = h->n;
     const int d = h->d, d_pad = h->d_pad;
-    const int kk = (int)(k < n ? k : n);
+    const int kk = (int)(k < h->n_live ? k : h->n_live);   // (removed rows are no neighbours: sq_dense_remove)
     const bool cosine = h->metric == SQ_METRIC_COSINE;
     // (profile = N > 1: every N-th asynchronous call only -- four event records per call weigh on a small shard's step)
     const bool prof = h->opt.profile == 1 || (h->opt.profile > 1 && (!use_event || h->async_calls % (unsigned)h->opt.profile == 0));
@@ -497,22 +537,22 @@ static int dense_enqueue(DenseHandle* h, DenseSlot& s, const float* q, int nq, i
         if (prof) SQ_HIP(hipEventRecord(s.ev[1], st));
         if (cosine)
             hipLaunchKernelGGL(dense_exact_cos_kernel, dim3(gx, nq), dim3(256), 0, st, h->db, h->ld, d, q, nullptr, cnt,
-                               (u32)n, n, 0ll, s.keys.as<K128>(), key_stride, cnx, cnq, nullptr, 0);
+                               (u32)n, n, 0ll, s.keys.as<K128>(), key_stride, cnx, cnq, nullptr, 0, h->deadp());
         else
             hipLaunchKernelGGL(dense_exact_l2_kernel, dim3(gx, nq), dim3(256), l2_lds, st, h->db, h->ld, d, q, nullptr,
-                               cnt, (u32)n, n, 0ll, s.keys.as<u64>(), key_stride, nullptr, 0);
+                               cnt, (u32)n, n, 0ll, s.keys.as<u64>(), key_stride, nullptr, 0, h->deadp());
         if (prof) SQ_HIP(hipEventRecord(s.ev[2], st));
         c.stats.scan_launches = 1;
         c.stats.bytes_scanned = n * (long long)d * 4;
         if (cosine) {
             SQ_TRY(select_launch_t<K128>(s.keys.as<K128>(), cnt, (u32)n, key_stride, k, nq, s.out_keys.as<K128>(),
-                                         DenseFinalizeCos{cnt, (u32)n, kk, h->id_base, thr, 0.0, 0, (double*)out_dist, out_idx,
-                                                          hs_dev, hs_raw_dev, nullptr, 0},
+                                         with_dead(DenseFinalizeCos{cnt, (u32)n, kk, h->id_base, thr, 0.0, 0, (double*)out_dist, out_idx,
+                                                                    hs_dev, hs_raw_dev, nullptr, 0}, h->deadp()),
                                          st, s.sort_tmp));
         } else {
             SQ_TRY(select_launch_t<u64>(s.keys.as<u64>(), cnt, (u32)n, key_stride, k, nq, s.out_keys.as<u64>(),
-                                        DenseFinalizeL2{cnt, (u32)n, kk, h->id_base, thr, qn2, 0.0, 0,
-                                                        (float*)out_dist, out_idx, hs_dev, hs_raw_dev, nullptr, 0},
+                                        with_dead(DenseFinalizeL2{cnt, (u32)n, kk, h->id_base, thr, qn2, 0.0, 0,
+                                                                  (float*)out_dist, out_idx, hs_dev, hs_raw_dev, nullptr, 0}, h->deadp()),
                                         st, s.sort_tmp));
         }
     } else if (scan_ok && h->first_suspended && h->opt.dense_mid_tier != 0 && !h->opt.force_fallback && dense_mid_shape_ok(h) &&
@@ -742,7 +782,7 @@ static int dense_enqueue(DenseHandle* h, DenseSlot& s, const float* q, int nq, i
             // everything the captured launches were given by value: shapes, the slot's and the handle's buffers
             u64 key = 0xcbf29ce484222325ull;
             auto mix = [&key](u64 v) { key = (key ^ v) * 0x100000001b3ull; };
-            for (u64 v : {(u64)(fused ? 1 : 0), (u64)(tighten ? 1 : 0), (u64)(uintptr_t)s.wave_score.p, (u64)(uintptr_t)s.hist8.p, (u64)lane_m, (u64)nq, (u64)k, (u64)row8, (u64)qt, (u64)nqt, (u64)wpb, (u64)stride, (u64)nrb, (u64)nrb_sample, (u64)ns, (u64)a.nt, (u64)a.nt_from_row, (u64)n, (u64)cap,
+            for (u64 v : {(u64)(fused ? 1 : 0), (u64)(tighten ? 1 : 0), (u64)(uintptr_t)s.wave_score.p, (u64)(uintptr_t)s.hist8.p, (u64)lane_m, (u64)nq, (u64)k, (u64)row8, (u64)qt, (u64)nqt, (u64)wpb, (u64)stride, (u64)nrb, (u64)nrb_sample, (u64)ns, (u64)a.nt, (u64)a.nt_from_row, (u64)n, (u64)h->n_live, (u64)cap,
                           (u64)h->opt.dense_debug, (u64)h->id_base, (u64)(uintptr_t)st, (u64)(uintptr_t)h->db, (u64)(uintptr_t)centerp,
                           (u64)(uintptr_t)h->scan8.p, (u64)(uintptr_t)h->nrow8.p, (u64)(uintptr_t)s.q8.p, (u64)(uintptr_t)s.par8.p,
                           (u64)(uintptr_t)s.sample.p, (u64)(uintptr_t)s.keys.p, (u64)(uintptr_t)s.wave_out.p, (u64)(uintptr_t)s.wave_cnt.p,
@@ -1014,10 +1054,11 @@ static int dense_resolve(DenseHandle* h, DenseSlot& s) {
     const long long n = h->n;
     const int d = h->d;
     const int nq = c.nq, k = c.k;
-    const int kk = (int)(k < n ? k : n);
+    const int kk = (int)(k < h->n_live ? k : h->n_live);
     const bool cosine = h->metric == SQ_METRIC_COSINE;
     const size_t key_bytes = cosine ? sizeof(K128) : sizeof(u64);
     const u32 cap = c.cap;
+    const u32* deadp = h->deadp();
     const bool force_fb = h->opt.force_fallback != 0;
     const bool small = c.small, all_fallback = c.all_fallback;
     hipStream_t st = c.st;
@@ -1198,6 +1239,7 @@ static int dense_resolve(DenseHandle* h, DenseSlot& s) {
                                h->mid_cos_rows.as<float>(), h->mid_cos_ld);
             SQ_HIP(hipGetLastError());
             h->mid_cos_n = n;
+            SQ_TRY(dense_dead_reapply(h, 0, st));   // (the terms just built are those of every row: removed ones leave again)
         }
         // sample of true scores: every mid_stride-th row (about 64 k candidates per query pass the bound it gives)
         long long mid_stride = std::min<long long>(64, std::min<long long>((long long)cap / (8ll * kk), n / (8ll * kk)));
@@ -1222,7 +1264,7 @@ static int dense_resolve(DenseHandle* h, DenseSlot& s) {
                 hipLaunchKernelGGL(dense_cos_qnorm_kernel, dim3(1), dim3(64), 0, st, (const float*)h->mid_q.as<float>(), sel.count, d, m_cnq);
                 hipLaunchKernelGGL(dense_mid_cos_sample_kernel, dim3((unsigned)((mid_ns + 7) / 8)), dim3(256), mid_sample_lds, st, h->db, h->ld,
                                    d, n, mid_stride, mid_ns, (const float*)h->mid_q.as<float>(), (const double*)m_qn2,
-                                   (const double*)h->cos_nx.as<double>(), h->mid_sample.as<float>());
+                                   (const double*)h->cos_nx.as<double>(), h->mid_sample.as<float>(), deadp);
                 hipLaunchKernelGGL((kth_threshold_f32_kernel<DenseMidCosThrPost>), dim3(sel.count), dim3(1024), 0, st,
                                    h->mid_sample.as<float>(), mid_ns, kk, m_thr,
                                    DenseMidCosThrPost{m_map, (const double*)out_dist, (const u32*)hs_dev, k, kk, (const float2*)m_lin});
@@ -1231,7 +1273,7 @@ static int dense_resolve(DenseHandle* h, DenseSlot& s) {
                                    h->metric, h->mid_planes.as<uint4>(), m_qn2, m_thr, m_cnt, m_oflag, h->mid_qal.as<float>(), ldq,
                                    h->center.p ? h->center.as<float>() : nullptr);
                 hipLaunchKernelGGL(dense_mid_sample_kernel, dim3((unsigned)((mid_ns + 7) / 8)), dim3(256), mid_sample_lds, st, h->db, h->ld, d, n,
-                                   mid_stride, mid_ns, (const float*)h->mid_q.as<float>(), (const double*)m_qn2, h->mid_sample.as<float>());
+                                   mid_stride, mid_ns, (const float*)h->mid_q.as<float>(), (const double*)m_qn2, h->mid_sample.as<float>(), deadp);
                 hipLaunchKernelGGL((kth_threshold_f32_kernel<DenseMidThrPost>), dim3(sel.count), dim3(1024), 0, st, h->mid_sample.as<float>(),
                                    mid_ns, kk, m_thr,
                                    DenseMidThrPost{m_map, (const float*)out_dist, (const u32*)hs_dev, k, kk, m_qn2, fb_mid.beta});
@@ -1333,20 +1375,20 @@ static int dense_resolve(DenseHandle* h, DenseSlot& s) {
         if (grp_ok) {
             if (cosine)
                 hipLaunchKernelGGL((dense_exact_group_kernel<true, K128>), dim3(gx), dim3(256), grp_lds, st, h->db, h->ld, d, q,
-                                   grp, n, h->big_keys.as<K128>(), fb_sample, fb_ns, (int)fb_stride, cnx, cnq);
+                                   grp, n, h->big_keys.as<K128>(), fb_sample, fb_ns, (int)fb_stride, cnx, cnq, deadp);
             else
                 hipLaunchKernelGGL((dense_exact_group_kernel<false, u64>), dim3(gx), dim3(256), grp_lds, st, h->db, h->ld, d, q,
-                                   grp, n, h->big_keys.as<u64>(), fb_sample, fb_ns, (int)fb_stride, nullptr, nullptr);
+                                   grp, n, h->big_keys.as<u64>(), fb_sample, fb_ns, (int)fb_stride, nullptr, nullptr, deadp);
         } else {  // one query per pass (gmax == 1 here)
             const int qi = grp.idx[0];
             if (cosine)
                 hipLaunchKernelGGL(dense_exact_cos_kernel, dim3(gx, 1), dim3(256), 0, st, h->db, h->ld, d,
                                    q + (long long)qi * d, nullptr, full_cnt + qi, (u32)n, n, 0ll, h->big_keys.as<K128>(), n, cnx,
-                                   cnq + qi, fb_sample, (int)fb_stride);
+                                   cnq + qi, fb_sample, (int)fb_stride, deadp);
             else
                 hipLaunchKernelGGL(dense_exact_l2_kernel, dim3(gx, 1), dim3(256), l2_lds, st, h->db, h->ld, d,
                                    q + (long long)qi * d, nullptr, full_cnt + qi, (u32)n, n, 0ll, h->big_keys.as<u64>(), n,
-                                   fb_sample, (int)fb_stride);
+                                   fb_sample, (int)fb_stride, deadp);
         }
         h->stats.scan_launches++;
         h->stats.bytes_scanned += n * (long long)d * 4;
@@ -1361,16 +1403,16 @@ static int dense_resolve(DenseHandle* h, DenseSlot& s) {
                                    fb_thr, h->fb_keys.as<K128>(), cap, fb_cnt);
                 SQ_TRY(h->fb_out.reserve((size_t)gn * k * key_bytes));
                 SQ_TRY(select_launch_t<K128>(h->fb_keys.as<K128>(), fb_cnt, cap, (long long)cap, k, gn, h->fb_out.as<K128>(),
-                                             DenseFinalizeCos{fb_cnt, cap, kk, h->id_base, thr, 0.0, 2, (double*)out_dist, out_idx,
-                                                              hs_dev, nullptr, nullptr, 0, grp},
+                                             with_dead(DenseFinalizeCos{fb_cnt, cap, kk, h->id_base, thr, 0.0, 2, (double*)out_dist, out_idx,
+                                                                        hs_dev, nullptr, nullptr, 0, grp}, deadp),
                                              st, h->fb_sort));
             } else {
                 hipLaunchKernelGGL((dense_compact_keys_kernel<u64>), dim3(gc, gn), dim3(256), 0, st, h->big_keys.as<u64>(), n,
                                    fb_thr, h->fb_keys.as<u64>(), cap, fb_cnt);
                 SQ_TRY(h->fb_out.reserve((size_t)gn * k * key_bytes));
                 SQ_TRY(select_launch_t<u64>(h->fb_keys.as<u64>(), fb_cnt, cap, (long long)cap, k, gn, h->fb_out.as<u64>(),
-                                            DenseFinalizeL2{fb_cnt, cap, kk, h->id_base, thr, qn2, 0.0, 2,
-                                                            (float*)out_dist, out_idx, hs_dev, nullptr, nullptr, 0, grp},
+                                            with_dead(DenseFinalizeL2{fb_cnt, cap, kk, h->id_base, thr, qn2, 0.0, 2,
+                                                                      (float*)out_dist, out_idx, hs_dev, nullptr, nullptr, 0, grp}, deadp),
                                             st, h->fb_sort));
             }
             SQ_HIP(stream_wait(st));  // the status words of the group are in hs now
@@ -1385,14 +1427,14 @@ static int dense_resolve(DenseHandle* h, DenseSlot& s) {
             if (cosine) {
                 SQ_TRY(select_launch_t<K128>(h->big_keys.as<K128>() + (long long)g * n, full_cnt + qi, (u32)n, n, k, 1,
                                              h->fb_out.as<K128>(),
-                                             DenseFinalizeCos{full_cnt, (u32)n, kk, h->id_base, thr, 0.0, 0, (double*)out_dist, out_idx,
-                                                              hs_dev, nullptr, nullptr, qi},
+                                             with_dead(DenseFinalizeCos{full_cnt, (u32)n, kk, h->id_base, thr, 0.0, 0, (double*)out_dist, out_idx,
+                                                                        hs_dev, nullptr, nullptr, qi}, deadp),
                                              st, h->fb_sort));
             } else {
                 SQ_TRY(select_launch_t<u64>(h->big_keys.as<u64>() + (long long)g * n, full_cnt + qi, (u32)n, n, k, 1,
                                             h->fb_out.as<u64>(),
-                                            DenseFinalizeL2{full_cnt, (u32)n, kk, h->id_base, thr, qn2, 0.0, 0,
-                                                            (float*)out_dist, out_idx, hs_dev, nullptr, nullptr, qi},
+                                            with_dead(DenseFinalizeL2{full_cnt, (u32)n, kk, h->id_base, thr, qn2, 0.0, 0,
+                                                                      (float*)out_dist, out_idx, hs_dev, nullptr, nullptr, qi}, deadp),
                                             st, h->fb_sort));
             }
         }
@@ -1639,6 +1681,50 @@ static int dense8_build(DenseHandle* h) {
     return quit(SQ_OK);
 }
 
+// Everything an index derives from its float32 rows, built from scratch: the L2 filter's origin, the row statistics, the
+// bfloat16 scan copy, the int8 copy.  sq_dense_create, and sq_dense_compact over the rows that are left.
+static int dense_build_all(DenseHandle* h) {
+    const long long n = h->n;
+    const int d = h->d, d_pad = h->d_pad, metric = h->metric;
+    // the filter's origin (L2): the column means (float64 sums over row blocks); rows appended later keep it
+    if (metric == SQ_METRIC_L2 && d_pad <= MAX_DPAD && !h->opt.dense_no_center) {
+        SQ_TRY(h->center.reserve((size_t)d_pad * 4));
+        DevBuf colsum;
+        SQ_TRY(colsum.reserve((size_t)d * 8));
+        if (hipMemset(colsum.p, 0, (size_t)d * 8) != hipSuccess) {
+            colsum.release();
+            return fail(SQ_ERR_HIP, "memset failed");
+        }
+        const long long rpb = 512;
+        hipLaunchKernelGGL(dense_colsum_kernel, dim3((unsigned)((n + rpb - 1) / rpb)), dim3(256), 0, 0, h->db,
+                           (long long)n, h->ld, d, rpb, colsum.as<double>());
+        hipLaunchKernelGGL(dense_center_kernel, dim3((d_pad + 255) / 256), dim3(256), 0, 0, colsum.as<double>(),
+                           (long long)n, d, d_pad, h->center.as<float>());
+        if (hipDeviceSynchronize() != hipSuccess) {
+            colsum.release();
+            return fail(SQ_ERR_HIP, "dense index build: column means failed");
+        }
+        colsum.release();
+    }
+    // row statistics, then the bfloat16 scan copy (skipped for rows wider than the scan kernel covers)
+    int rc = h->norms.reserve((size_t)h->n_pad * 4);
+    if (rc == SQ_OK && metric == SQ_METRIC_L2) rc = h->norms1.reserve((size_t)h->n_pad * 4);
+    if (rc == SQ_OK && metric == SQ_METRIC_COSINE) rc = h->cos_nx.reserve((size_t)n * 8);
+    if (rc == SQ_OK && metric == SQ_METRIC_COSINE) {
+        rc = h->zeros.reserve(256);
+        if (rc == SQ_OK && hipMemset(h->zeros.p, 0, 256) != hipSuccess) rc = fail(SQ_ERR_HIP, "dense index build: memset failed");
+    }
+    if (rc == SQ_OK && d_pad <= MAX_DPAD) rc = h->scan.reserve((size_t)h->n_pad * d_pad * 2);
+    if (rc == SQ_OK) rc = dense_build_rows(h, 0);
+    if (rc == SQ_OK && hipDeviceSynchronize() != hipSuccess) rc = fail(SQ_ERR_HIP, "dense index build failed");
+    const auto t8 = std::chrono::steady_clock::now();
+    if (rc == SQ_OK) rc = dense8_build(h);
+    if (rc == SQ_OK && hipDeviceSynchronize() != hipSuccess) rc = fail(SQ_ERR_HIP, "dense index build: int8 copy failed");
+    if (rc != SQ_OK) return rc;
+    h->build8_us = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t8).count();
+    return SQ_OK;
+}
+
 // Room for `n_new` rows in every per-row buffer, contents kept (grown by half again at least, so a stream of
 // small appends copies the matrix O(log) times).
 static int grow_keep(DevBuf& b, size_t used, size_t need) {
@@ -1809,6 +1895,7 @@ static int dense_create_impl(const float* db, int64_t n, int d, int metric, int 
     auto* h = new DenseHandle();
     h->kind = H_DENSE;
     h->n = n;
+    h->n_live = n;
     h->n_pad = (n + TILE_ROWS - 1) / TILE_ROWS * TILE_ROWS;
     h->d = d;
     h->d_pad = d_pad;
@@ -1846,45 +1933,9 @@ static int dense_create_impl(const float* db, int64_t n, int d, int metric, int 
         h->db = h->owned.as<float>();
         h->ld = ldo;
     }
-    // the filter's origin (L2): the column means (float64 sums over row blocks); rows appended later keep it
-    if (metric == SQ_METRIC_L2 && d_pad <= MAX_DPAD && !h->opt.dense_no_center) {
-        int rc = h->center.reserve((size_t)d_pad * 4);
-        if (rc != SQ_OK) return bail(rc);
-        DevBuf colsum;
-        rc = colsum.reserve((size_t)d * 8);
-        if (rc != SQ_OK) return bail(rc);
-        if (hipMemset(colsum.p, 0, (size_t)d * 8) != hipSuccess) {
-            colsum.release();
-            return bail(fail(SQ_ERR_HIP, "memset failed"));
-        }
-        const long long rpb = 512;
-        hipLaunchKernelGGL(dense_colsum_kernel, dim3((unsigned)((n + rpb - 1) / rpb)), dim3(256), 0, 0, h->db,
-                           (long long)n, h->ld, d, rpb, colsum.as<double>());
-        hipLaunchKernelGGL(dense_center_kernel, dim3((d_pad + 255) / 256), dim3(256), 0, 0, colsum.as<double>(),
-                           (long long)n, d, d_pad, h->center.as<float>());
-        if (hipDeviceSynchronize() != hipSuccess) {
-            colsum.release();
-            return bail(fail(SQ_ERR_HIP, "sq_dense_create: column means failed"));
-        }
-        colsum.release();
-    }
-    // row statistics, then the bfloat16 scan copy (skipped for rows wider than the scan kernel covers)
     {
-        int rc = h->norms.reserve((size_t)h->n_pad * 4);
-        if (rc == SQ_OK && metric == SQ_METRIC_L2) rc = h->norms1.reserve((size_t)h->n_pad * 4);
-        if (rc == SQ_OK && metric == SQ_METRIC_COSINE) rc = h->cos_nx.reserve((size_t)n * 8);
-        if (rc == SQ_OK && metric == SQ_METRIC_COSINE) {
-            rc = h->zeros.reserve(256);
-            if (rc == SQ_OK && hipMemset(h->zeros.p, 0, 256) != hipSuccess) rc = fail(SQ_ERR_HIP, "sq_dense_create: memset failed");
-        }
-        if (rc == SQ_OK && d_pad <= MAX_DPAD) rc = h->scan.reserve((size_t)h->n_pad * d_pad * 2);
-        if (rc == SQ_OK) rc = dense_build_rows(h, 0);
-        if (rc == SQ_OK && hipDeviceSynchronize() != hipSuccess) rc = fail(SQ_ERR_HIP, "sq_dense_create: build failed");
-        const auto t8 = std::chrono::steady_clock::now();
-        if (rc == SQ_OK) rc = dense8_build(h);
-        if (rc == SQ_OK && hipDeviceSynchronize() != hipSuccess) rc = fail(SQ_ERR_HIP, "sq_dense_create: int8 build failed");
+        const int rc = dense_build_all(h);
         if (rc != SQ_OK) return bail(rc);
-        h->build8_us = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t8).count();
     }
     h->build_us = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t_create).count();
     *out = register_handle(h);
@@ -1904,6 +1955,12 @@ extern "C" int sq_dense_append(sq_handle_t hid, const float* rows, int64_t n_add
     if (n_new >= (1ll << 32)) return fail(SQ_ERR_UNSUPPORTED, "sq_dense_append: more than 2^32-1 rows per shard");
     SQ_HIP(hipSetDevice(h->device));
     SQ_TRY(dense_grow(h, n_new));
+    if (h->dead.p) {   // the bitmap of removed rows follows the matrix (new rows are live; holes are not reused)
+        const long long words = (n_new + 31) / 32;
+        SQ_TRY(grow_keep(h->dead, (size_t)h->dead_words * 4, (size_t)words * 4));
+        SQ_HIP(hipMemset(h->dead.as<u32>() + h->dead_words, 0, h->dead.cap - (size_t)h->dead_words * 4));
+        h->dead_words = words;
+    }
     float* dst = h->owned.as<float>() + n_old * h->ld;
     const hipMemcpyKind kind = mem == SQ_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     hipError_t e;
@@ -1917,8 +1974,179 @@ extern "C" int sq_dense_append(sq_handle_t hid, const float* rows, int64_t n_add
     h->n = n_new;
     h->n_pad = (n_new + TILE_ROWS - 1) / TILE_ROWS * TILE_ROWS;
     // the tile the old rows ended in is rebuilt together with the new ones (its padding rows become real rows)
+    h->n_live += n_add;
     SQ_TRY(dense_build_rows(h, n_old / TILE_ROWS * TILE_ROWS));
-    return dense8_append(h, n_old);
+    SQ_TRY(dense8_append(h, n_old));
+    // the tile and the int8 unit the old rows ended in were rebuilt from their rows (an index that has doubled rebuilds its
+    // whole int8 copy): the removed rows among them leave again
+    if (h->dead.p) {
+        SQ_TRY(dense_dead_reapply(h, 0, nullptr));
+        SQ_HIP(hipDeviceSynchronize());
+    }
+    return SQ_OK;
+}
+
+// ---- removal and compaction (sq_dense_remove.hpp; impls/nn_index/faiss.py:644-694)
+extern "C" int sq_dense_count(sq_handle_t hid, int64_t* n_rows, int64_t* n_live) {
+    auto* h = static_cast<DenseHandle*>(lookup_handle(hid, H_DENSE));
+    if (!h) return fail(SQ_ERR_INVALID, "sq_dense_count: unknown handle");
+    std::lock_guard<std::mutex> l(h->mu);
+    if (n_rows) *n_rows = h->n;
+    if (n_live) *n_live = h->n_live;
+    return SQ_OK;
+}
+
+extern "C" int sq_dense_remove(sq_handle_t hid, const int64_t* ids, int64_t m) {
+    auto* h = static_cast<DenseHandle*>(lookup_handle(hid, H_DENSE));
+    if (!h) return fail(SQ_ERR_INVALID, "sq_dense_remove: unknown handle");
+    if (!ids || m <= 0) return fail(SQ_ERR_INVALID, "sq_dense_remove: bad argument");
+    std::lock_guard<std::mutex> l(h->mu);
+    h->refresh_options();
+    SQ_HIP(hipSetDevice(h->device));
+    SQ_TRY(dense_sync_all(h));
+    // (more ids than live rows: one of them is dead or listed twice; as many: the index would be left without a row,
+    // which sq_dense_create does not build either)
+    if (m >= h->n_live)
+        return fail(SQ_ERR_INVALID, "sq_dense_remove: %lld ids for %lld live rows (an index keeps at least one row: destroy it instead)",
+                    (long long)m, h->n_live);
+    const bool fresh = h->dead.p == nullptr;
+    DevBuf ids_dev, won, status;
+    auto done = [&](int rc) {
+        ids_dev.release();
+        won.release();
+        status.release();
+        if (rc != SQ_OK && fresh) {   // a refused first removal leaves no bitmap behind
+            h->dead.release();
+            h->dead_words = 0;
+        }
+        return rc;
+    };
+    if (fresh) {
+        const long long words = (h->n + 31) / 32;
+        if (const int rc = h->dead.reserve((size_t)words * 4)) return done(rc);
+        if (hipMemset(h->dead.p, 0, h->dead.cap) != hipSuccess) return done(fail(SQ_ERR_HIP, "sq_dense_remove: memset failed"));
+        h->dead_words = words;
+    }
+    if (const int rc = ids_dev.reserve((size_t)m * 8)) return done(rc);
+    if (const int rc = won.reserve((size_t)m * 4)) return done(rc);
+    if (const int rc = status.reserve(4)) return done(rc);
+    if (hipMemcpy(ids_dev.p, ids, (size_t)m * 8, hipMemcpyHostToDevice) != hipSuccess || hipMemset(status.p, 0, 4) != hipSuccess)
+        return done(fail(SQ_ERR_HIP, "sq_dense_remove: copy of the ids failed"));
+    const dim3 grid((unsigned)((m + 255) / 256)), blk(256);
+    // pass 1: validate and mark
+    hipLaunchKernelGGL(dense_remove_kernel, grid, blk, 0, 0, ids_dev.as<long long>(), (long long)m, h->id_base, h->n, h->dead.as<u32>(),
+                       won.as<u32>(), status.as<u32>());
+    u32 st = 0;
+    if (hipMemcpy(&st, status.p, 4, hipMemcpyDeviceToHost) != hipSuccess)
+        return done(fail(SQ_ERR_HIP, "sq_dense_remove: %s", hipGetErrorString(hipGetLastError())));
+    if (st != 0) {
+        // pass 2, refused: the bits this call set are cleared again; nothing else was written
+        hipLaunchKernelGGL(dense_remove_undo_kernel, grid, blk, 0, 0, ids_dev.as<long long>(), (long long)m, h->id_base, h->dead.as<u32>(),
+                           won.as<u32>());
+        if (hipDeviceSynchronize() != hipSuccess) return done(fail(SQ_ERR_HIP, "sq_dense_remove: undo failed"));
+        return done(fail(SQ_ERR_INVALID, "sq_dense_remove: %s%s%s; nothing was removed", (st & DENSE_REMOVE_RANGE) ? "an id is out of range" : "",
+                         st == 3u ? ", " : "", (st & DENSE_REMOVE_DEAD) ? "an id is already removed or listed twice" : ""));
+    }
+    // pass 2: the per-row terms of every copy the handle keeps
+    hipLaunchKernelGGL(dense_remove_apply_kernel, grid, blk, 0, 0, ids_dev.as<long long>(), (long long)m, h->id_base, dense_dead_terms(h));
+    if (hipDeviceSynchronize() != hipSuccess) return done(fail(SQ_ERR_HIP, "sq_dense_remove: %s", hipGetErrorString(hipGetLastError())));
+    h->n_live -= m;
+    return done(SQ_OK);
+}
+
+extern "C" int sq_dense_compact(sq_handle_t hid, int64_t* old_to_new) {
+    auto* h = static_cast<DenseHandle*>(lookup_handle(hid, H_DENSE));
+    if (!h) return fail(SQ_ERR_INVALID, "sq_dense_compact: unknown handle");
+    std::lock_guard<std::mutex> l(h->mu);
+    h->refresh_options();
+    if (!h->owned.p) return fail(SQ_ERR_UNSUPPORTED, "sq_dense_compact: the index borrows the caller's device matrix");
+    SQ_HIP(hipSetDevice(h->device));
+    SQ_TRY(dense_sync_all(h));
+    const long long n_old = h->n;
+    if (!h->dead.p || h->n_live == n_old) {   // nothing to drop: the index stays as it is
+        if (old_to_new)
+            for (long long i = 0; i < n_old; ++i) old_to_new[i] = h->id_base + i;
+        return SQ_OK;
+    }
+    const long long cpr = h->ld / 4;   // (the owned matrix: rows of whole 16-byte chunks)
+    const long long words = (n_old + 31) / 32;
+    DevBuf prefix, total, map, fresh_rows, bounce;
+    auto done = [&](int rc) {
+        for (DevBuf* b : {&prefix, &total, &map, &fresh_rows, &bounce}) b->release();
+        return rc;
+    };
+    if (const int rc = prefix.reserve((size_t)words * 8)) return done(rc);
+    if (const int rc = total.reserve(8)) return done(rc);
+    hipLaunchKernelGGL(dense_compact_scan_kernel, dim3(1), dim3(1024), 0, 0, h->deadp(), n_old, words, prefix.as<unsigned long long>(),
+                       total.as<unsigned long long>());
+    unsigned long long live_dev = 0;
+    if (hipMemcpy(&live_dev, total.p, 8, hipMemcpyDeviceToHost) != hipSuccess)
+        return done(fail(SQ_ERR_HIP, "sq_dense_compact: %s", hipGetErrorString(hipGetLastError())));
+    const long long live = (long long)live_dev;
+    if (live != h->n_live) return done(fail(SQ_ERR_INTERNAL, "sq_dense_compact: the bitmap holds %lld live rows, the handle counts %lld", live, h->n_live));
+    if (old_to_new) {   // before anything changes: a failure here leaves the index as it was
+        if (const int rc = map.reserve((size_t)n_old * 8)) return done(rc);
+        hipLaunchKernelGGL(dense_compact_map_kernel, dim3((unsigned)((n_old + 255) / 256)), dim3(256), 0, 0, h->deadp(),
+                           prefix.as<unsigned long long>(), n_old, h->id_base, map.as<long long>());
+        if (hipMemcpy(old_to_new, map.p, (size_t)n_old * 8, hipMemcpyDeviceToHost) != hipSuccess)
+            return done(fail(SQ_ERR_HIP, "sq_dense_compact: %s", hipGetErrorString(hipGetLastError())));
+        map.release();
+    }
+    // every copy derived from the rows is rebuilt below: their memory goes first, so that the gather finds room
+    for (DevBuf* b : {&h->scan, &h->scan8, &h->nrow8, &h->norms, &h->norms1, &h->cos_nx, &h->center, &h->mid_cos_center, &h->mid_cos_rows})
+        b->release();
+    h->use8 = false;
+    const size_t row_bytes = (size_t)h->ld * 4;
+    // rows of one gather launch: its grid stays below 2^30 workgroups
+    const long long launch_rows = std::max<long long>(32, ((1ll << 30) * 256 / cpr) / 32 * 32);
+    auto gather = [&](uint4* dst, long long r0, long long r1, long long dst_row0) {
+        hipLaunchKernelGGL(dense_compact_gather_kernel, dim3((unsigned)(((r1 - r0) * cpr + 255) / 256)), dim3(256), 0, 0, h->owned.as<uint4>(), dst,
+                           cpr, r0, r1, dst_row0, h->deadp(), prefix.as<unsigned long long>());
+    };
+    if (fresh_rows.reserve((size_t)live * row_bytes) == SQ_OK) {
+        // a second buffer: one pass, and the matrix shrinks to the rows that are left
+        for (long long r0 = 0; r0 < n_old; r0 += launch_rows) gather(fresh_rows.as<uint4>(), r0, std::min(n_old, r0 + launch_rows), 0);
+        if (hipDeviceSynchronize() != hipSuccess) return done(fail(SQ_ERR_HIP, "sq_dense_compact: gather failed: %s", hipGetErrorString(hipGetLastError())));
+        h->owned.release();
+        h->owned = fresh_rows;
+        fresh_rows = DevBuf{};
+    } else {
+        // No room for a second matrix: in place, front to back, a piece of rows at a time through a bounce buffer.  Piece j
+        // lands at rows [new(r0), new(r1)) with new(r1) <= r1: below every row a later piece has yet to read, and the piece
+        // itself has been read into the bounce buffer completely (stream order) before it is written.
+        (void)hipGetLastError();
+        long long piece = std::min<long long>(launch_rows, std::max<long long>(32, (long long)(((size_t)64 << 20) / row_bytes) / 32 * 32));
+        if (const int rc = bounce.reserve((size_t)piece * row_bytes)) return done(fail(rc, "sq_dense_compact: no memory for the gather; the index must be built again"));
+        std::vector<unsigned long long> pre((size_t)words);
+        if (hipMemcpy(pre.data(), prefix.p, (size_t)words * 8, hipMemcpyDeviceToHost) != hipSuccess)
+            return done(fail(SQ_ERR_HIP, "sq_dense_compact: %s", hipGetErrorString(hipGetLastError())));
+        for (long long r0 = 0; r0 < n_old; r0 += piece) {
+            const long long r1 = std::min(n_old, r0 + piece);
+            const long long d0 = (long long)pre[(size_t)(r0 >> 5)], d1 = r1 < n_old ? (long long)pre[(size_t)(r1 >> 5)] : live;
+            if (d1 == d0) continue;
+            gather(bounce.as<uint4>(), r0, r1, d0);
+            if (hipMemcpyAsync(h->owned.as<char>() + (size_t)d0 * row_bytes, bounce.p, (size_t)(d1 - d0) * row_bytes, hipMemcpyDeviceToDevice, 0) != hipSuccess)
+                return done(fail(SQ_ERR_HIP, "sq_dense_compact: copy failed: %s", hipGetErrorString(hipGetLastError())));
+        }
+        if (hipDeviceSynchronize() != hipSuccess) return done(fail(SQ_ERR_HIP, "sq_dense_compact: gather failed: %s", hipGetErrorString(hipGetLastError())));
+    }
+    h->db = h->owned.as<float>();
+    h->n = h->n_live = live;
+    h->n_pad = (live + TILE_ROWS - 1) / TILE_ROWS * TILE_ROWS;
+    h->dead.release();
+    h->dead_words = 0;
+    // the index sq_dense_create would build from these rows: origin, statistics, scan copies, filter state
+    h->xn2_max = 0.0;
+    h->mid_cos_n = -1;
+    h->overflow16 = 0;
+    h->first_suspended = false;
+    h->direct_calls = 0;
+    h->probe_interval = 16;
+    for (auto& sl : h->slot) {   // captured call graphs hold the old shape and the old buffers
+        if (sl.gexec) (void)hipGraphExecDestroy(sl.gexec), sl.gexec = nullptr;
+        sl.gkey = sl.seen_key = 0;
+    }
+    return done(dense_build_all(h));
 }
 
 extern "C" int sq_dense_search(sq_handle_t hid, const float* queries, int nq, int k, void* out_dist, int64_t* out_idx,

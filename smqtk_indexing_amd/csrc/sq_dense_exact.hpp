@@ -146,6 +146,18 @@ static __global__ void dense_cos_qnorm_kernel(const float* __restrict__ q, int n
     if (qi < nq) nq64[qi] = cosine_sumsq_f64(q + (long long)qi * d, d);
 }
 
+// ------------------------------------------------------------- removed rows
+// Bitmap of the rows sq_dense_remove took out (sq_dense_remove.hpp): bit (row & 31) of word (row >> 5); a null pointer
+// -- no removal was ever made on the index -- costs the kernels below one uniform branch.  The filters never emit a
+// removed row (its per-row terms say so); the kernels that score every row from the float32 matrix ask the bitmap.
+// A removed row's key sorts behind every distance, NaN included, and carries its row so that the keys stay distinct
+// (the select counts keys at or below the k-th: a run of equal keys would overflow its gather list).
+__device__ __forceinline__ bool dense_row_dead(const u32* __restrict__ dead, long long row) {
+    return dead != nullptr && ((dead[row >> 5] >> (u32)(row & 31)) & 1u) != 0u;
+}
+__device__ __forceinline__ u64 dense_dead_key(u64, long long row) { return 0xffffffff00000000ull | (u64)(u32)row; }
+__device__ __forceinline__ K128 dense_dead_key(K128, long long row) { return K128{~0ull, (u64)(u32)row}; }
+
 // ------------------------------------------------------ exact distance keys
 // One lane per row: numpy's eight interleaved accumulators are eight registers,
 // fed by two 16-byte row loads and two 16-byte LDS (query) reads per 8 elements.
@@ -203,7 +215,8 @@ static __global__ __launch_bounds__(256) void dense_exact_l2_kernel(const float*
                                                               const u32* __restrict__ cand, const u32* __restrict__ cnt,
                                                               u32 cap, long long implicit_n, long long row_offset,
                                                               u64* __restrict__ keys, long long key_stride,
-                                                              float* __restrict__ sample, int sample_stride) {
+                                                              float* __restrict__ sample, int sample_stride,
+                                                              const u32* __restrict__ dead = nullptr) {
     extern __shared__ __attribute__((aligned(16))) float s_q[];
     const int q = blockIdx.y;
     const long long M = cand ? (long long)(cnt[q] < cap ? cnt[q] : cap) : implicit_n;
@@ -212,6 +225,11 @@ static __global__ __launch_bounds__(256) void dense_exact_l2_kernel(const float*
     __syncthreads();
     for (long long j = (long long)blockIdx.x * 256 + threadIdx.x; j < M; j += (long long)gridDim.x * 256) {
         const long long row = cand ? (long long)cand[(long long)q * cap + j] : row_offset + j;
+        if (dense_row_dead(dead, row)) {   // a removed row: no distance, no sample
+            keys[(long long)q * key_stride + j] = dense_dead_key(u64{}, row);
+            if (sample && j % sample_stride == 0) sample[j / sample_stride] = __builtin_inff();
+            continue;
+        }
         const SqLeafLane w{db + row * ld, s_q};
         const float dist = sqrt_rn_f32(w.sum(d));
         keys[(long long)q * key_stride + j] = ((u64)ordered_f32(dist) << 32) | (u64)(u32)row;
@@ -227,13 +245,19 @@ static __global__ __launch_bounds__(256) void dense_exact_cos_kernel(const float
                                                                K128* __restrict__ keys, long long key_stride,
                                                                const double* __restrict__ nx64,
                                                                const double* __restrict__ nq64,
-                                                               float* __restrict__ sample, int sample_stride) {
+                                                               float* __restrict__ sample, int sample_stride,
+                                                               const u32* __restrict__ dead = nullptr) {
     const int q = blockIdx.y;
     const long long M = cand ? (long long)(cnt[q] < cap ? cnt[q] : cap) : implicit_n;
     const float* qv = q_orig + (long long)q * d;
     const double qq = nq64[q];
     for (long long j = (long long)blockIdx.x * 256 + threadIdx.x; j < M; j += (long long)gridDim.x * 256) {
         const long long row = cand ? (long long)cand[(long long)q * cap + j] : row_offset + j;
+        if (dense_row_dead(dead, row)) {
+            keys[(long long)q * key_stride + j] = dense_dead_key(K128{}, row);
+            if (sample && j % sample_stride == 0) sample[j / sample_stride] = __builtin_inff();
+            continue;
+        }
         const double dist = cosine_dist_f64(cosine_dot_f64(db + row * ld, qv, d), nx64[row], qq);
         keys[(long long)q * key_stride + j] = K128{ordered_f64(dist), (u64)(u32)row};
         if (sample && j % sample_stride == 0) sample[j / sample_stride] = dist == dist ? __double2float_ru(dist) : __builtin_inff();
@@ -260,7 +284,8 @@ static __global__ __launch_bounds__(256) void dense_exact_group_kernel(const flo
                                                                        long long n, K* __restrict__ keys,
                                                                        float* __restrict__ sample, long long ns,
                                                                        int sample_stride, const double* __restrict__ nx64,
-                                                                       const double* __restrict__ nq64) {
+                                                                       const double* __restrict__ nq64,
+                                                                       const u32* __restrict__ dead = nullptr) {
     constexpr int G = EXACT_GROUP;
     extern __shared__ __attribute__((aligned(16))) float s_qg[];
     const int dq = (d + 3) / 4 * 4;
@@ -271,6 +296,16 @@ static __global__ __launch_bounds__(256) void dense_exact_group_kernel(const flo
     __syncthreads();
     for (long long j = (long long)blockIdx.x * 256 + threadIdx.x; j < n; j += (long long)gridDim.x * 256) {
         const float* x = db + j * ld;
+        if (dense_row_dead(dead, j)) {   // a removed row: the row is not read
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                if (g < grp.count) {
+                    keys[(long long)g * n + j] = dense_dead_key(K{}, j);
+                    if (sample && j % sample_stride == 0) sample[(long long)g * ns + j / sample_stride] = __builtin_inff();
+                }
+            }
+            continue;
+        }
         if constexpr (!COSINE) {
             float acc[G];
             auto leaf = [&](int off, int m, float (&v)[G]) {
@@ -962,6 +997,7 @@ struct DenseFinalizeL2 {
     const u32* thr2k = nullptr;   // the int8 full pass's tightened thresholds: ordered keys, the largest any workgroup applied (0: none did); 1 << cnt_shift words apart
     int cnt_shift = 0;            // cnt (and thr2k) entries are 1 << cnt_shift words apart (the fused int8 call: a cache line each)
     const DenseCallPtrs* ind = nullptr;  // captured call graph: the outputs of THIS launch
+    const u32* dead = nullptr;    // removed rows (the exact paths' keys hold them, behind every distance): never an id, padding instead
     __device__ __forceinline__ void operator()(int ql, const u64* sorted, int k) const {
         const int q = qmap ? qmap[ql] : (sel.count ? sel.idx[ql] : q0 + ql);
         const int qa = qmap ? ql : q;  // index into thr / qn2
@@ -969,7 +1005,8 @@ struct DenseFinalizeL2 {
         long long* out_idx = ind ? ind->out_idx : this->out_idx;
         for (int j = threadIdx.x; j < k; j += blockDim.x) {
             const u64 key = sorted[j];
-            const bool pad = key == ~0ull;
+            // (a live row's NaN distance may share the removed rows' high word: the bitmap tells them apart)
+            const bool pad = key == ~0ull || ((u32)(key >> 32) == 0xffffffffu && dense_row_dead(dead, (long long)(key & 0xffffffffull)));
             out_dist[(long long)q * k + j] = pad ? __builtin_inff() : unordered_f32((u32)(key >> 32));
             out_idx[(long long)q * k + j] = pad ? -1ll : id_base + (long long)(key & 0xffffffffull);
         }
@@ -1014,6 +1051,7 @@ struct DenseFinalizeCos {
     int cnt_shift = 0;
     const DenseCallPtrs* ind = nullptr;   // captured call graph: the outputs of THIS launch
     const int* qmap = nullptr;            // the middle tier: query ql of the launch is qmap[ql]; cnt, thr and lin are the launch's own arrays
+    const u32* dead = nullptr;            // as DenseFinalizeL2::dead
     __device__ __forceinline__ void operator()(int ql, const K128* sorted, int k) const {
         const int q = qmap ? qmap[ql] : (sel.count ? sel.idx[ql] : q0 + ql);
         const int qa = qmap ? ql : q;  // index into thr / lin
@@ -1021,7 +1059,7 @@ struct DenseFinalizeCos {
         long long* out_idx = ind ? ind->out_idx : this->out_idx;
         for (int j = threadIdx.x; j < k; j += blockDim.x) {
             const K128 key = sorted[j];
-            const bool pad = key.hi == ~0ull && key.lo == ~0ull;
+            const bool pad = key.hi == ~0ull && (key.lo == ~0ull || dense_row_dead(dead, (long long)(key.lo & 0xffffffffull)));
             out_dist[(long long)q * k + j] = pad ? (double)__builtin_inff() : unordered_f64(key.hi);
             out_idx[(long long)q * k + j] = pad ? -1ll : id_base + (long long)(key.lo & 0xffffffffull);
         }

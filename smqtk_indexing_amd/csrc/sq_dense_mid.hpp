@@ -268,7 +268,8 @@ static __global__ __launch_bounds__(256) void dense_mid_sample_kernel(const floa
                                                                        long long stride, long long ns,
                                                                        const float* __restrict__ q_mid,   // [32][d]
                                                                        const double* __restrict__ qn2_mid,
-                                                                       float* __restrict__ sample) {      // [32][ns]
+                                                                       float* __restrict__ sample,        // [32][ns]
+                                                                       const u32* __restrict__ dead = nullptr) {   // removed rows (sq_dense_remove.hpp): no sample
     extern __shared__ float lq[];   // [d][33]: element k of query j at k * 33 + j (conflict-free for lane = query)
     for (int i = threadIdx.x; i < MID_MAX_Q * d; i += 256) {
         const int j = i / d, k = i - j * d;
@@ -279,6 +280,10 @@ static __global__ __launch_bounds__(256) void dense_mid_sample_kernel(const floa
     const long long i = ((long long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 2 + (lane >> 5);   // sampled row index
     if (i >= ns) return;
     const long long row = i * stride < n ? i * stride : n - 1;
+    if (dense_row_dead(dead, row)) {
+        sample[(long long)j * ns + i] = __builtin_inff();
+        return;
+    }
     const float* x = db + row * ld;
     double acc = 0.0;
     int k = 0;
@@ -459,7 +464,8 @@ static __global__ __launch_bounds__(256) void dense_mid_cos_sample_kernel(const 
                                                                            const float* __restrict__ q_mid,   // [32][d]
                                                                            const double* __restrict__ qn2_mid,
                                                                            const double* __restrict__ nx64,
-                                                                           float* __restrict__ sample) {      // [32][ns]
+                                                                           float* __restrict__ sample,        // [32][ns]
+                                                                           const u32* __restrict__ dead = nullptr) {
     extern __shared__ float lq[];
     for (int i = threadIdx.x; i < MID_MAX_Q * d; i += 256) {
         const int j = i / d, k = i - j * d;
@@ -470,6 +476,10 @@ static __global__ __launch_bounds__(256) void dense_mid_cos_sample_kernel(const 
     const long long i = ((long long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 2 + (lane >> 5);
     if (i >= ns) return;
     const long long row = i * stride < n ? i * stride : n - 1;
+    if (dense_row_dead(dead, row)) {
+        sample[(long long)j * ns + i] = __builtin_inff();
+        return;
+    }
     const float* x = db + row * ld;
     double acc = 0.0;
     int k = 0;

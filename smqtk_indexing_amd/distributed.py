@@ -92,7 +92,8 @@ class ShardedIndex:
 
 
 def dense_shard(db_shard, row0: int, metric: int = 0, group=None) -> ShardedIndex:
-    """Shard from a CUDA float32 tensor ``[n_local, d]`` (borrowed, d % 64 == 0)."""
+    """Shard from a CUDA float32 tensor ``[n_local, d]`` (borrowed, d % 64 == 0).  ``shard.index.remove(ids)`` takes
+    rows out in place (``sq_dense_remove``, global ids ``row0 + row``); the tensor is not written."""
     import torch
     from . import _lib
 
@@ -147,6 +148,9 @@ class MutableShardedIndex:
       kernels cap k) drops them and rebuilds its local index.
     * ``search(queries, k)`` -- each shard answers ``k + dead`` locally, drops dead rows, maps local rows to
       global ids, then the usual all-gather + host merge.
+    * a local index that offers ``remove(local_rows)`` (:func:`dense_local_builder`: ``sq_dense_remove``, the rows
+      leave the device index in place) is told of every removal: the shard then answers plain ``k`` and ``max_dead``
+      no longer forces a rebuild (``compact_at`` still does).  Local indexes without it keep the behaviour above.
 
     ``build_local(rows) -> search(queries, k) -> (dist [nq,k], local_row [nq,k])`` builds the per-shard
     searcher (padding: row -1); :func:`dense_local_builder` / :func:`hamming_local_builder` wrap the HIP
@@ -180,8 +184,15 @@ class MutableShardedIndex:
         dist.all_gather(outs, mine, group=self.group)
         return [int(x.item()) for x in outs]
 
+    def _remover(self):
+        """``remove(local_rows)`` of the local index, if it offers one."""
+        return getattr(self._local, "remove", None) if self._local is not None else None
+
     def _rebuild(self) -> None:
         self._local = self.build_local(self.rows) if self.rows.shape[0] else None
+        remover = self._remover()
+        if remover is not None and bool(self.dead.any()) and not bool(self.dead.all()):
+            remover(self.dead.nonzero().flatten().numpy())      # (built from all local rows: the dead ones leave again)
 
     def count(self) -> int:
         return int(sum(self.live))
@@ -219,18 +230,24 @@ class MutableShardedIndex:
         for r in range(self.world):
             self.live[r] -= found[r]
         n_dead = int(self.dead.sum())
-        if n_dead and (n_dead > self.compact_at * int(self.dead.numel()) or n_dead > self.max_dead):
+        remover = self._remover()
+        if n_dead and (n_dead > self.compact_at * int(self.dead.numel()) or (remover is None and n_dead > self.max_dead)):
             keep = ~self.dead
             self.rows = self.rows[keep.to(self.rows.device)].contiguous()
             self.ids, self.dead = self.ids[keep], torch.zeros(int(keep.sum()), dtype=torch.bool)
             self._rebuild()
+        elif remover is not None and bool(hit.any()) and n_dead < int(self.dead.numel()):
+            remover(pos_c[hit].numpy())        # in place on the device; a shard left without a live row is not searched
 
     # -------------------------------------------------------------- search
     def search(self, queries, k: int, merge_on: Optional[int] = None):
         import torch
         nq = int(queries.shape[0])
         n_local, n_dead = int(self.dead.numel()), int(self.dead.sum())
-        kk = min(n_local, int(k) + n_dead)
+        if self._remover() is not None:
+            kk = min(n_local - n_dead, int(k))      # the local index has dropped the dead rows itself
+        else:
+            kk = min(n_local, int(k) + n_dead)
         if self._local is not None and kk > 0:
             d, r = self._local(queries, kk)
             d, r = d.cpu(), r.cpu()
@@ -273,6 +290,8 @@ def dense_local_builder(metric: int = 0) -> Callable:
             torch.cuda.current_stream().synchronize()
             return od, oi
         search.index = index  # type: ignore[attr-defined]
+        # sq_dense_remove on the borrowed shard (local row ids; the caller's rows are not written)
+        search.remove = lambda local_rows: index.remove(np.asarray(local_rows, dtype=np.int64))  # type: ignore[attr-defined]
         return search
     return build
 

@@ -53,9 +53,9 @@ class HipBruteForceNearestNeighborsIndex(NearestNeighborsIndex):
         self._blocks: List[np.ndarray] = []
         self._all_f32 = True     # every indexed vector is float32: the float32 search distances are final
         self._dev: Optional[_lib.DenseIndex] = None
-        # rows removed while a device index is resident stay in it as tombstones (their `_elements` entry is None):
-        # a search asks for k + len(_dead) rows and drops them; the index is rebuilt from the live rows once they pass
-        # a quarter of it (what distributed.MutableShardedIndex does per shard)
+        # rows removed while a device index is resident leave it in place (sq_dense_remove, what faiss.py:644-694 does
+        # with remove_ids): their `_elements` entry is None and a search asks for plain k.  Once they pass a quarter
+        # of the rows the device drops them (sq_dense_compact) and the host state is renumbered from its old_to_new.
         self._dead: set = set()
 
     def get_config(self) -> Dict[str, Any]:
@@ -150,16 +150,34 @@ class HipBruteForceNearestNeighborsIndex(NearestNeighborsIndex):
                 if u not in self._row_of:
                     raise KeyError(u)          # nothing modified yet
             drop = set(uids)
-            if self._dev is not None and 4 * (len(self._dead) + len(drop)) <= len(self._elements):
-                # tombstones: the resident matrix is neither re-uploaded nor re-indexed
-                for u in drop:
-                    r = self._row_of.pop(u)
-                    self._elements[r] = None       # type: ignore[call-overload]
-                    self._dead.add(r)
+            if self._dev is not None and len(drop) < self.count():
+                # on the device, in place: the resident matrix is neither re-uploaded nor re-indexed
+                self._drop_rows(list(drop))
                 return
             kept = [e for e in self._elements if e is not None and e.uuid() not in drop]
             rows = [self._row_of[e.uuid()] for e in kept]
             self._set(kept, np.ascontiguousarray(self._matrix[rows], dtype=np.float32))
+
+    def _drop_rows(self, uids: Sequence[Hashable]) -> None:
+        """Rows of these (indexed, distinct) uuids leave the device index in place; past a quarter of the rows removed
+        the device compacts itself and the host state follows its renumbering."""
+        assert self._dev is not None
+        rows = sorted(self._row_of[u] for u in uids)
+        self._dev.remove(np.asarray(rows, dtype=np.int64))
+        for u in uids:
+            r = self._row_of.pop(u)
+            self._elements[r] = None       # type: ignore[call-overload]
+            self._dead.add(r)
+        if 4 * len(self._dead) > len(self._elements):
+            old_to_new = np.asarray(self._dev.compact(), dtype=np.int64)
+            keep = np.flatnonzero(old_to_new >= 0)
+            elements: List[DescriptorElement] = [None] * len(keep)     # type: ignore[list-item]
+            for old in keep:
+                elements[int(old_to_new[old])] = self._elements[int(old)]
+            self._elements = elements
+            self._row_of = {e.uuid(): i for i, e in enumerate(elements)}
+            self._blocks = [np.ascontiguousarray(self._matrix[keep], dtype=np.float32)]
+            self._dead = set()
 
     def nn_many(self, vectors: np.ndarray, n: int = 1) -> Tuple[np.ndarray, np.ndarray]:
         """Batched search: ``[nq, d]`` -> (row ids ``[nq, k]``, distances ``[nq, k]``)."""
@@ -168,15 +186,9 @@ class HipBruteForceNearestNeighborsIndex(NearestNeighborsIndex):
                 raise ValueError("No index currently set to query from!")
             k = min(int(n), self.count())
             q = np.asarray(vectors, dtype=np.float32)
-            if not self._dead:
-                dist, idx = self._device().search(q, k)
-                return idx, dist
-            # tombstoned rows: ask for as many more, drop them (the (distance, row) order of the rest is unchanged)
-            dist, idx = self._device().search(q, min(k + len(self._dead), len(self._elements)))
-            dead = np.fromiter(self._dead, dtype=np.int64, count=len(self._dead))
-            live = ~np.isin(idx, dead)
-            pos = np.argsort(~live, axis=1, kind="stable")[:, :k]      # live entries first, in their order
-            return np.take_along_axis(idx, pos, axis=1), np.take_along_axis(dist, pos, axis=1)
+            # (removed rows are gone from the device index too -- `_dead` is only non-empty while `_dev` exists: plain k)
+            dist, idx = self._device().search(q, k)
+            return idx, dist
 
     def elements_of(self, rows: Sequence[int]) -> Tuple[DescriptorElement, ...]:
         with self._lock:
