@@ -41,9 +41,10 @@ inline int fail(int code, const char* fmt, ...) {
                             __FILE__, __LINE__);                                      \
     } while (0)
 
-#define SQ_TRY(expr)              \
-    do {                          \
-        int rc_ = (expr);         \
+// (variadic: an expression such as launch<kernel<A, B>>(...) has commas of its own)
+#define SQ_TRY(...)                   \
+    do {                              \
+        int rc_ = (__VA_ARGS__);      \
         if (rc_ != SQ_OK) return rc_; \
     } while (0)
 
@@ -90,23 +91,30 @@ extern Options g_opt;   // process-wide defaults (sq_set_option); a handle may o
 // name -> member, shared by sq_set_option and sq_handle_set_option (sq_core.hip)
 int Options::*option_member(const char* name);
 
-// Wait for a stream the way a latency-bound caller wants to: poll hipStreamQuery for a while (a search is
-// a fraction of a millisecond; the blocking wait's wake-up costs tens of microseconds of it), then block.
+// Wait the way a latency-bound caller wants to: poll `query` for a while (a search is a fraction of a millisecond;
+// the blocking wait's wake-up costs tens of microseconds of it), then `block`.
 // Option "spin_wait_us" (default 2000; 0 = always block).
-inline hipError_t stream_wait(hipStream_t st) {
+template <class Query, class Block>
+inline hipError_t poll_then_block(Query query, Block block) {
     const long long budget_us = g_opt.spin_wait_us;
     if (budget_us > 0) {
         const auto t0 = std::chrono::steady_clock::now();
         for (;;) {
             for (int i = 0; i < 64; ++i) {
-                const hipError_t e = hipStreamQuery(st);
+                const hipError_t e = query();
                 if (e != hipErrorNotReady) return e;
             }
             if (std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count() > budget_us)
                 break;
         }
     }
-    return hipStreamSynchronize(st);
+    return block();
+}
+inline hipError_t stream_wait(hipStream_t st) {
+    return poll_then_block([st] { return hipStreamQuery(st); }, [st] { return hipStreamSynchronize(st); });
+}
+inline hipError_t event_wait(hipEvent_t ev) {
+    return poll_then_block([ev] { return hipEventQuery(ev); }, [ev] { return hipEventSynchronize(ev); });
 }
 
 // ------------------------------------------------------- device buffer (RAII)
@@ -257,17 +265,31 @@ inline int cu_count(int device) {
     return p.multiProcessorCount;
 }
 
-// hipFuncSetAttribute(MaxDynamicSharedMemorySize) applies to the CURRENT device's copy of a kernel: once per (kernel,
-// device), the mask being the caller's static state for that kernel (a second GPU used from the same process otherwise
+// ----------------------------------------------------------------- launches
+// Launch `Kernel` and report a bad launch configuration where it happens, not at the next wait.
+template <auto Kernel, class... Args>
+inline int launch(dim3 grid, dim3 block, size_t lds, hipStream_t st, Args&&... args) {
+    Kernel<<<grid, block, lds, st>>>(std::forward<Args>(args)...);
+    SQ_HIP(hipGetLastError());
+    return SQ_OK;
+}
+
+// launch() for a kernel that may take more than 64 KiB of dynamic LDS.  `max_dyn_lds` is the largest `lds` the kernel
+// is ever launched with (a kernel with static LDS of its own asks for its ring, not the CU's 160 KiB).
+// hipFuncSetAttribute(MaxDynamicSharedMemorySize) applies to the CURRENT device's copy of a kernel: once per (kernel
+// instantiation, device), the mask below being this instantiation's (a second GPU used from the same process otherwise
 // never gets the attribute and its launches with more than 64 KiB of LDS fail).
-inline int ensure_dyn_lds(const void* fn, int bytes, std::atomic<unsigned long long>& done_devices) {
+template <auto Kernel, class... Args>
+inline int launch_lds(int max_dyn_lds, dim3 grid, dim3 block, size_t lds, hipStream_t st, Args&&... args) {
+    static std::atomic<unsigned long long> done_devices{0};
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) dev = 0;
     const unsigned long long bit = dev >= 0 && dev < 64 ? 1ull << dev : 0ull;
-    if (bit && (done_devices.load(std::memory_order_relaxed) & bit)) return SQ_OK;
-    SQ_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    if (bit) done_devices.fetch_or(bit, std::memory_order_relaxed);
-    return SQ_OK;
+    if (!bit || !(done_devices.load(std::memory_order_relaxed) & bit)) {
+        SQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, max_dyn_lds));
+        if (bit) done_devices.fetch_or(bit, std::memory_order_relaxed);
+    }
+    return launch<Kernel>(grid, block, lds, st, std::forward<Args>(args)...);
 }
 
 inline size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }

@@ -202,42 +202,10 @@ static int dense_dead_reapply(DenseHandle* h, long long row_from, hipStream_t st
     SQ_HIP(hipGetLastError());
     return SQ_OK;
 }
-static constexpr int kSelectLdsKeys64 = 16384;
-static constexpr int kSelectLdsKeys128 = 7168;
-
-// select + the finalisation post-op (keys -> distances / ids, certification, status) in one launch
-// `expect`: candidates per query the caller expects (0 = unknown).  The kernel keeps up to lds_keys keys of a query in
-// LDS and reads longer lists from global memory; sizing the LDS for the expected list instead of the largest possible
-// lets two workgroups share a CU (36-40 registers per thread: LDS is what limits them) -- with one workgroup per query
-// a 1024-query batch is four rounds of workgroups otherwise.
-template <class K, class Post>
-static int select_launch_t(const K* keys, const u32* cnt, u32 cap, long long stride, int k, int nq, K* out,
-                           const Post& post, hipStream_t st, DevBuf& sort_scratch, long long expect = 0, int cnt_shift = 0) {
-    static std::atomic<unsigned long long> attr_done{0};
-    const int lds_max = sizeof(K) == 8 ? kSelectLdsKeys64 : kSelectLdsKeys128;
-    // beyond the one-workgroup select: full sort (sq_select.hpp, "any-k sorted select"); the scratch belongs to the
-    // call slot (asynchronous calls in flight, or two handles on two threads, must not share it)
-    if (k > lds_max) return sort_select_large<K, Post>(keys, cnt, cap, stride, k, nq, out, sort_scratch, post, st);
-    int lds_keys = lds_max;
-    if (expect > 0 && nq > 256) {  // (fewer queries than CUs: one round of workgroups either way)
-        const int half = (int)((80 * 1024) / sizeof(K)) - SELECT_SORT_MAX;  // two workgroups in 160 KB
-        if (half >= k && 2 * expect <= half) lds_keys = half;
-    }
-    const size_t lds_full = (size_t)(lds_max + SELECT_SORT_MAX) * sizeof(K);
-    const size_t lds = (size_t)(lds_keys + SELECT_SORT_MAX) * sizeof(K);
-    SQ_TRY(ensure_dyn_lds(reinterpret_cast<const void*>(&select_topk_kernel<K, Post>), (int)lds_full, attr_done));
-    hipLaunchKernelGGL((select_topk_kernel<K, Post>), dim3(nq), dim3(1024), lds, st, keys, cnt, cap, stride, k, lds_keys,
-                       out, post, cnt_shift);
-    return SQ_OK;
-}
-
 template <int WAVES, int NSTAGE, int KU, int QT, int QP, bool AB, bool SAMPLE, bool NT = false>
 static int scan_launch_t(const DenseScanArgs& a, size_t lds, hipStream_t st) {
-    static std::atomic<unsigned long long> attr_done{0};
-    SQ_TRY(ensure_dyn_lds(reinterpret_cast<const void*>(&dense_scan_kernel<WAVES, NSTAGE, KU, QT, QP, AB, SAMPLE, NT>), 160 * 1024, attr_done));
-    hipLaunchKernelGGL((dense_scan_kernel<WAVES, NSTAGE, KU, QT, QP, AB, SAMPLE, NT>), dim3((unsigned)(a.nrb * a.nqt)),
-                       dim3(WAVES * 64), lds, st, a);
-    return SQ_OK;
+    return launch_lds<dense_scan_kernel<WAVES, NSTAGE, KU, QT, QP, AB, SAMPLE, NT>>(160 * 1024, dim3((unsigned)(a.nrb * a.nqt)),
+                                                                                   dim3(WAVES * 64), lds, st, a);
 }
 
 static constexpr int SCAN_LDS_TAIL = 8 * 16;  // per-wave survivor counters
@@ -349,32 +317,13 @@ static int scan_query_tiles(const Options& o, int d_pad, int nqt) {
     return want;
 }
 
-// Wait for an event the way stream_wait waits for a stream (poll, then block).
-static hipError_t event_wait(hipEvent_t ev) {
-    const long long budget_us = g_opt.spin_wait_us;
-    if (budget_us > 0) {
-        const auto t0 = std::chrono::steady_clock::now();
-        for (;;) {
-            for (int i = 0; i < 64; ++i) {
-                const hipError_t e = hipEventQuery(ev);
-                if (e != hipErrorNotReady) return e;
-            }
-            if (std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count() > budget_us)
-                break;
-        }
-    }
-    return hipEventSynchronize(ev);
-}
-
 // the int8 scan for a row width (sq_dense_i8.hpp I8Geom): launch, and the attribute every instantiation needs once
 template <int KS, bool SAMPLE>
 static int dense8_scan_launch_t(const Dense8ScanArgs& a, hipStream_t st) {
     using G = I8Geom<KS>;
-    static std::atomic<unsigned long long> attr_done{0};
+    constexpr int ring = G::WAVES * G::NSTAGE * G::SLOT_BYTES;
     // (the kernel has a few bytes of static LDS of its own: the attribute is the ring, not the CU's 160 KiB)
-    SQ_TRY(ensure_dyn_lds(reinterpret_cast<const void*>(&dense8_scan_kernel<KS, SAMPLE>), G::WAVES * G::NSTAGE * G::SLOT_BYTES, attr_done));
-    hipLaunchKernelGGL((dense8_scan_kernel<KS, SAMPLE>), dim3((unsigned)a.nrb), dim3(G::WAVES * 64), (size_t)G::WAVES * G::NSTAGE * G::SLOT_BYTES, st, a);
-    return SQ_OK;
+    return launch_lds<dense8_scan_kernel<KS, SAMPLE>>(ring, dim3((unsigned)a.nrb), dim3(G::WAVES * 64), ring, st, a);
 }
 template <bool SAMPLE>
 static int dense8_scan_launch(int row_bytes, const Dense8ScanArgs& a, hipStream_t st) {
@@ -388,10 +337,8 @@ static int dense8_scan_launch(int row_bytes, const Dense8ScanArgs& a, hipStream_
 template <int QT, bool SAMPLE>
 static int dense8_scan_mt_launch_t(const Dense8ScanArgs& a, hipStream_t st) {
     using G = I8Geom<4>;
-    static std::atomic<unsigned long long> attr_done{0};
-    SQ_TRY(ensure_dyn_lds(reinterpret_cast<const void*>(&dense8_scan_mt_kernel<QT, SAMPLE>), 160 * 1024, attr_done));
-    hipLaunchKernelGGL((dense8_scan_mt_kernel<QT, SAMPLE>), dim3((unsigned)(a.nrb * a.nqt)), dim3(G::WAVES * 64), (size_t)G::WAVES * G::NSTAGE * G::SLOT_BYTES, st, a);
-    return SQ_OK;
+    return launch_lds<dense8_scan_mt_kernel<QT, SAMPLE>>(160 * 1024, dim3((unsigned)(a.nrb * a.nqt)), dim3(G::WAVES * 64),
+                                                         (size_t)G::WAVES * G::NSTAGE * G::SLOT_BYTES, st, a);
 }
 // one query tile per wave: dense8_scan_kernel for the row width; 2 or 4 tiles (128-byte rows): dense8_scan_mt_kernel
 template <bool SAMPLE>
@@ -405,11 +352,9 @@ static int dense8_scan_any(int row_bytes, int qt, const Dense8ScanArgs& a, hipSt
 template <int KS>
 static int dense8_head_launch_t(const Dense8HeadArgs& a, hipStream_t st) {
     using G = I8Geom<KS>;
-    static std::atomic<unsigned long long> attr_done{0};
+    constexpr int ring = G::WAVES * G::NSTAGE * G::SLOT_BYTES;
     // (the kernel has static LDS of its own: the attribute is the ring, not the CU's 160 KiB)
-    SQ_TRY(ensure_dyn_lds(reinterpret_cast<const void*>(&dense8_head_kernel<KS>), G::WAVES * G::NSTAGE * G::SLOT_BYTES, attr_done));
-    hipLaunchKernelGGL((dense8_head_kernel<KS>), dim3((unsigned)a.s.nrb), dim3(G::WAVES * 64), (size_t)G::WAVES * G::NSTAGE * G::SLOT_BYTES, st, a);
-    return SQ_OK;
+    return launch_lds<dense8_head_kernel<KS>>(ring, dim3((unsigned)a.s.nrb), dim3(G::WAVES * 64), ring, st, a);
 }
 static int dense8_head_launch(int row_bytes, const Dense8HeadArgs& a, hipStream_t st) {
     switch (row_bytes) {
@@ -422,10 +367,8 @@ static int dense8_head_launch(int row_bytes, const Dense8HeadArgs& a, hipStream_
 template <int KS, bool COSINE>
 static int dense8_body_launch_t(const Dense8ScanArgs& a, const Dense8TailArgs& t, hipStream_t st) {
     using G = I8Geom<KS>;
-    static std::atomic<unsigned long long> attr_done{0};
-    SQ_TRY(ensure_dyn_lds(reinterpret_cast<const void*>(&dense8_body_kernel<KS, COSINE>), G::WAVES * G::NSTAGE * G::SLOT_BYTES, attr_done));
-    hipLaunchKernelGGL((dense8_body_kernel<KS, COSINE>), dim3((unsigned)a.nrb), dim3(G::WAVES * 64), (size_t)G::WAVES * G::NSTAGE * G::SLOT_BYTES, st, a, t);
-    return SQ_OK;
+    constexpr int ring = G::WAVES * G::NSTAGE * G::SLOT_BYTES;
+    return launch_lds<dense8_body_kernel<KS, COSINE>>(ring, dim3((unsigned)a.nrb), dim3(G::WAVES * 64), ring, st, a, t);
 }
 static int dense8_body_launch(int row_bytes, bool cosine, const Dense8ScanArgs& a, const Dense8TailArgs& t, hipStream_t st) {
     switch (row_bytes) {
@@ -1211,11 +1154,6 @@ static int dense_resolve(DenseHandle* h, DenseSlot& s) {
         double* m_cnq = reinterpret_cast<double*>(m_map + 32);
         float* m_qw = reinterpret_cast<float*>(m_cnq + 32);
         float2* m_lin = reinterpret_cast<float2*>(m_qw + 32);
-        static std::atomic<unsigned long long> attr8{0}, attr4{0}, attr8c{0}, attr4c{0};
-        if (waves == 8 && !cosine) SQ_TRY(ensure_dyn_lds(reinterpret_cast<const void*>(&dense_mid_scan_kernel<8, false>), 160 * 1024, attr8));
-        if (waves == 4 && !cosine) SQ_TRY(ensure_dyn_lds(reinterpret_cast<const void*>(&dense_mid_scan_kernel<4, false>), 160 * 1024, attr4));
-        if (waves == 8 && cosine) SQ_TRY(ensure_dyn_lds(reinterpret_cast<const void*>(&dense_mid_scan_kernel<8, true>), 160 * 1024, attr8c));
-        if (waves == 4 && cosine) SQ_TRY(ensure_dyn_lds(reinterpret_cast<const void*>(&dense_mid_scan_kernel<4, true>), 160 * 1024, attr4c));
         if (cosine && h->mid_cos_n != n) {
             // the cosine tier's origin and per-row terms (sq_dense_mid.hpp), once per index and again after an append
             if (!h->mid_cos_center.p) {
@@ -1247,10 +1185,6 @@ static int dense_resolve(DenseHandle* h, DenseSlot& s) {
         const long long mid_ns = (n + mid_stride - 1) / mid_stride;
         const size_t mid_sample_lds = (size_t)d * 33 * 4;
         SQ_TRY(h->mid_sample.reserve((size_t)MID_MAX_Q * mid_ns * 4));
-        {
-            static std::atomic<unsigned long long> attr_s{0};
-            SQ_TRY(ensure_dyn_lds(reinterpret_cast<const void*>(&dense_mid_sample_kernel), 512 * 33 * 4, attr_s));
-        }
         std::vector<int> left;
         for (size_t t0 = 0; t0 < todo.size(); t0 += MID_MAX_Q) {
             MidSelection sel{};
@@ -1272,8 +1206,8 @@ static int dense_resolve(DenseHandle* h, DenseSlot& s) {
                 hipLaunchKernelGGL(dense_prep_queries_kernel, dim3(MID_MAX_Q), dim3(256), 0, st, h->mid_q.as<float>(), sel.count, d, d_pad,
                                    h->metric, h->mid_planes.as<uint4>(), m_qn2, m_thr, m_cnt, m_oflag, h->mid_qal.as<float>(), ldq,
                                    h->center.p ? h->center.as<float>() : nullptr);
-                hipLaunchKernelGGL(dense_mid_sample_kernel, dim3((unsigned)((mid_ns + 7) / 8)), dim3(256), mid_sample_lds, st, h->db, h->ld, d, n,
-                                   mid_stride, mid_ns, (const float*)h->mid_q.as<float>(), (const double*)m_qn2, h->mid_sample.as<float>(), deadp);
+                SQ_TRY(launch_lds<dense_mid_sample_kernel>(512 * 33 * 4, dim3((unsigned)((mid_ns + 7) / 8)), dim3(256), mid_sample_lds, st, h->db, h->ld, d, n,
+                                                           mid_stride, mid_ns, (const float*)h->mid_q.as<float>(), (const double*)m_qn2, h->mid_sample.as<float>(), deadp));
                 hipLaunchKernelGGL((kth_threshold_f32_kernel<DenseMidThrPost>), dim3(sel.count), dim3(1024), 0, st, h->mid_sample.as<float>(),
                                    mid_ns, kk, m_thr,
                                    DenseMidThrPost{m_map, (const float*)out_dist, (const u32*)hs_dev, k, kk, m_qn2, fb_mid.beta});
@@ -1299,13 +1233,13 @@ static int dense_resolve(DenseHandle* h, DenseSlot& s) {
             a.qw = m_qw;
             if (cosine) {
                 if (waves == 8)
-                    hipLaunchKernelGGL((dense_mid_scan_kernel<8, true>), dim3(nrb), dim3(512), mid_lds, st, a);
+                    SQ_TRY(launch_lds<dense_mid_scan_kernel<8, true>>(160 * 1024, dim3(nrb), dim3(512), mid_lds, st, a));
                 else
-                    hipLaunchKernelGGL((dense_mid_scan_kernel<4, true>), dim3(nrb), dim3(256), mid_lds, st, a);
+                    SQ_TRY(launch_lds<dense_mid_scan_kernel<4, true>>(160 * 1024, dim3(nrb), dim3(256), mid_lds, st, a));
             } else if (waves == 8) {
-                hipLaunchKernelGGL((dense_mid_scan_kernel<8, false>), dim3(nrb), dim3(512), mid_lds, st, a);
+                SQ_TRY(launch_lds<dense_mid_scan_kernel<8, false>>(160 * 1024, dim3(nrb), dim3(512), mid_lds, st, a));
             } else {
-                hipLaunchKernelGGL((dense_mid_scan_kernel<4, false>), dim3(nrb), dim3(256), mid_lds, st, a);
+                SQ_TRY(launch_lds<dense_mid_scan_kernel<4, false>>(160 * 1024, dim3(nrb), dim3(256), mid_lds, st, a));
             }
             const int wpb = 2;
             const size_t rr_lds = ldq <= 156 ? (size_t)32 * (ldq + 4) * 4 : 0;
@@ -1342,13 +1276,8 @@ static int dense_resolve(DenseHandle* h, DenseSlot& s) {
     int gmax = (int)std::min<long long>(EXACT_GROUP, std::max<long long>(1, (4ll << 30) / (n * (long long)key_bytes)));
     if (d > (128 << EXACT_GROUP_DEPTH) || (h->opt.dense_debug & 256)) gmax = 1;    // debug 256: measurement, one query per pass
     const size_t grp_lds = (size_t)EXACT_GROUP * ((d + 3) / 4 * 4) * 4;
-    const bool grp_ok = grp_lds <= 160 * 1024 - 256 && d <= (128 << EXACT_GROUP_DEPTH);
-    if (grp_ok) {
-        SQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_exact_group_kernel<false, u64>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)grp_lds));
-        SQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_exact_group_kernel<true, K128>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)grp_lds));
-    }
+    constexpr int grp_lds_max = 160 * 1024 - 256;   // (the attribute is set once per device: the largest group any index asks for)
+    const bool grp_ok = grp_lds <= (size_t)grp_lds_max && d <= (128 << EXACT_GROUP_DEPTH);
     // the exact path keeps its own per-query counters: the slot's belong to a call that may still be in flight
     // when another asynchronous call's queries are redone
     SQ_TRY(h->fb_cnt.reserve((size_t)(nq + 64) * 4));
@@ -1374,11 +1303,11 @@ static int dense_resolve(DenseHandle* h, DenseSlot& s) {
         if (gx > 8192) gx = 8192;
         if (grp_ok) {
             if (cosine)
-                hipLaunchKernelGGL((dense_exact_group_kernel<true, K128>), dim3(gx), dim3(256), grp_lds, st, h->db, h->ld, d, q,
-                                   grp, n, h->big_keys.as<K128>(), fb_sample, fb_ns, (int)fb_stride, cnx, cnq, deadp);
+                SQ_TRY(launch_lds<dense_exact_group_kernel<true, K128>>(grp_lds_max, dim3(gx), dim3(256), grp_lds, st, h->db, h->ld, d, q,
+                                                                        grp, n, h->big_keys.as<K128>(), fb_sample, fb_ns, (int)fb_stride, cnx, cnq, deadp));
             else
-                hipLaunchKernelGGL((dense_exact_group_kernel<false, u64>), dim3(gx), dim3(256), grp_lds, st, h->db, h->ld, d, q,
-                                   grp, n, h->big_keys.as<u64>(), fb_sample, fb_ns, (int)fb_stride, nullptr, nullptr, deadp);
+                SQ_TRY(launch_lds<dense_exact_group_kernel<false, u64>>(grp_lds_max, dim3(gx), dim3(256), grp_lds, st, h->db, h->ld, d, q,
+                                                                        grp, n, h->big_keys.as<u64>(), fb_sample, fb_ns, (int)fb_stride, nullptr, nullptr, deadp));
         } else {  // one query per pass (gmax == 1 here)
             const int qi = grp.idx[0];
             if (cosine)

@@ -233,13 +233,10 @@ static int fit_gram_cov(FitHandle* h, double* out_dev) {
     if (d > FIT_MAX_D) return fail(SQ_ERR_UNSUPPORTED, "sq_itqfit: d=%d above %d", d, FIT_MAX_D);
     // thread tiles: 256 threads x (TP x TQ) cover an output tile (4 x 4 when the whole output is <= 64 x 64)
     if (d <= 64)
-        hipLaunchKernelGGL((fit_gram_kernel<T, 0, 4, 4>), dim3(grid, tiles, tiles), dim3(256), lds, 0, (const T*)h->x, nrm,
-                           h->mean.as<double>(), nullptr, nullptr, 0, h->n, d, d, rpb, out_dev);
-    else
-        hipLaunchKernelGGL((fit_gram_kernel<T, 0, 8, 8>), dim3(grid, tiles, tiles), dim3(256), lds, 0, (const T*)h->x, nrm,
-                           h->mean.as<double>(), nullptr, nullptr, 0, h->n, d, d, rpb, out_dev);
-    SQ_HIP(hipGetLastError());
-    return SQ_OK;
+        return launch<fit_gram_kernel<T, 0, 4, 4>>(dim3(grid, tiles, tiles), dim3(256), lds, nullptr, (const T*)h->x, nrm,
+                                                   h->mean.as<double>(), nullptr, nullptr, 0, h->n, d, d, rpb, out_dev);
+    return launch<fit_gram_kernel<T, 0, 8, 8>>(dim3(grid, tiles, tiles), dim3(256), lds, nullptr, (const T*)h->x, nrm,
+                                               h->mean.as<double>(), nullptr, nullptr, 0, h->n, d, d, rpb, out_dev);
 }
 
 }  // namespace sq
@@ -283,19 +280,19 @@ extern "C" int sq_itqfit_create(const void* x, int dtype, int64_t n, int d, int 
     if (norm_ord == SQ_NORM_L2) {
         if ((rc = h->nrm.reserve((size_t)n * 8)) != SQ_OK) return bail(rc);
         const unsigned g = (unsigned)((n + 31) / 32);
-        if (dtype == SQ_DTYPE_F32)
-            hipLaunchKernelGGL((fit_rownorm_kernel<float>), dim3(g), dim3(256), 0, 0, (const float*)h->x, (long long)n, d, h->nrm.as<double>());
-        else
-            hipLaunchKernelGGL((fit_rownorm_kernel<double>), dim3(g), dim3(256), 0, 0, (const double*)h->x, (long long)n, d, h->nrm.as<double>());
+        rc = dtype == SQ_DTYPE_F32
+                 ? launch<fit_rownorm_kernel<float>>(dim3(g), dim3(256), 0, nullptr, (const float*)h->x, (long long)n, d, h->nrm.as<double>())
+                 : launch<fit_rownorm_kernel<double>>(dim3(g), dim3(256), 0, nullptr, (const double*)h->x, (long long)n, d, h->nrm.as<double>());
+        if (rc != SQ_OK) return bail(rc);
     }
     if (hipMemset(h->acc.p, 0, (size_t)d * 8) != hipSuccess) return bail(fail(SQ_ERR_HIP, "memset failed"));
     const long long rpb = 1024;
     const unsigned g = (unsigned)((n + rpb - 1) / rpb);
     const double* nrm = norm_ord == SQ_NORM_L2 ? h->nrm.as<double>() : nullptr;
-    if (dtype == SQ_DTYPE_F32)
-        hipLaunchKernelGGL((fit_colsum_kernel<float>), dim3(g), dim3(256), 0, 0, (const float*)h->x, (long long)n, d, rpb, nrm, h->acc.as<double>());
-    else
-        hipLaunchKernelGGL((fit_colsum_kernel<double>), dim3(g), dim3(256), 0, 0, (const double*)h->x, (long long)n, d, rpb, nrm, h->acc.as<double>());
+    rc = dtype == SQ_DTYPE_F32
+             ? launch<fit_colsum_kernel<float>>(dim3(g), dim3(256), 0, nullptr, (const float*)h->x, (long long)n, d, rpb, nrm, h->acc.as<double>())
+             : launch<fit_colsum_kernel<double>>(dim3(g), dim3(256), 0, nullptr, (const double*)h->x, (long long)n, d, rpb, nrm, h->acc.as<double>());
+    if (rc != SQ_OK) return bail(rc);
     std::vector<double> sums((size_t)d);
     if (hipMemcpy(sums.data(), h->acc.p, (size_t)d * 8, hipMemcpyDeviceToHost) != hipSuccess)
         return bail(fail(SQ_ERR_HIP, "sq_itqfit_create: column means failed: %s", hipGetErrorString(hipGetLastError())));
@@ -352,17 +349,12 @@ extern "C" int sq_itqfit_project(sq_handle_t hid, const double* pc, int bits) {
     const unsigned chunks = (unsigned)((bits + bc - 1) / bc);
     const double* nrm = h->norm == SQ_NORM_L2 ? h->nrm.as<double>() : nullptr;
     const unsigned g = (unsigned)std::min<long long>((h->n + 31) / 32, 4ll * cu_count(h->device));
-    if (h->dtype == SQ_DTYPE_F32) {
-        SQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&fit_project_kernel<float>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        hipLaunchKernelGGL((fit_project_kernel<float>), dim3(g, chunks), dim3(256), lds, 0, (const float*)h->x, nrm,
-                           h->mean.as<double>(), h->small.as<double>(), h->n, d, bits, bc, pck, h->v.as<double>());
-    } else {
-        SQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&fit_project_kernel<double>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        hipLaunchKernelGGL((fit_project_kernel<double>), dim3(g, chunks), dim3(256), lds, 0, (const double*)h->x, nrm,
-                           h->mean.as<double>(), h->small.as<double>(), h->n, d, bits, bc, pck, h->v.as<double>());
-    }
+    if (h->dtype == SQ_DTYPE_F32)
+        SQ_TRY(launch_lds<fit_project_kernel<float>>(160 * 1024, dim3(g, chunks), dim3(256), lds, nullptr, (const float*)h->x, nrm,
+                                                     h->mean.as<double>(), h->small.as<double>(), h->n, d, bits, bc, pck, h->v.as<double>()));
+    else
+        SQ_TRY(launch_lds<fit_project_kernel<double>>(160 * 1024, dim3(g, chunks), dim3(256), lds, nullptr, (const double*)h->x, nrm,
+                                                      h->mean.as<double>(), h->small.as<double>(), h->n, d, bits, bc, pck, h->v.as<double>()));
     SQ_HIP(hipDeviceSynchronize());
     return SQ_OK;
 }
@@ -391,12 +383,11 @@ extern "C" int sq_itqfit_iterate(sq_handle_t hid, const double* r, double* out_c
     const unsigned grid = (unsigned)((h->n + rpb - 1) / rpb);
     const size_t lds = (size_t)2 * 16 * FIT_GT * 8;
     const unsigned tiles = (unsigned)((b + FIT_GT - 1) / FIT_GT);
-    if (b <= 64)
-        hipLaunchKernelGGL((fit_gram_kernel<double, 1, 4, 4>), dim3(grid, tiles, tiles), dim3(256), lds, 0, nullptr, nullptr,
-                           nullptr, h->v.as<double>(), codes.as<u64>(), words, h->n, b, b, rpb, h->acc.as<double>());
-    else
-        hipLaunchKernelGGL((fit_gram_kernel<double, 1, 8, 8>), dim3(grid, tiles, tiles), dim3(256), lds, 0, nullptr, nullptr,
-                           nullptr, h->v.as<double>(), codes.as<u64>(), words, h->n, b, b, rpb, h->acc.as<double>());
+    rc = b <= 64 ? launch<fit_gram_kernel<double, 1, 4, 4>>(dim3(grid, tiles, tiles), dim3(256), lds, nullptr, nullptr, nullptr, nullptr,
+                                                            h->v.as<double>(), codes.as<u64>(), words, h->n, b, b, rpb, h->acc.as<double>())
+                 : launch<fit_gram_kernel<double, 1, 8, 8>>(dim3(grid, tiles, tiles), dim3(256), lds, nullptr, nullptr, nullptr, nullptr,
+                                                            h->v.as<double>(), codes.as<u64>(), words, h->n, b, b, rpb, h->acc.as<double>());
+    if (rc != SQ_OK) return done(rc);
     if (hipMemcpy(out_c, h->acc.p, (size_t)b * b * 8, hipMemcpyDeviceToHost) != hipSuccess)
         return done(fail(SQ_ERR_HIP, "sq_itqfit_iterate: failed: %s", hipGetErrorString(hipGetLastError())));
     return done(SQ_OK);

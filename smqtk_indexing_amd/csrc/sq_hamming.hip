@@ -13,6 +13,7 @@
 // few survivors.  Small arrays and overflowing queries take the all-keys path.
 // Integer-exact.  DESIGN.md section 4.3.
 #include <algorithm>
+#include <type_traits>
 
 #include "sq_dma.hpp"
 #include "sq_select.hpp"
@@ -29,6 +30,23 @@ struct RowPerm {
 // `depth` slots, each with a stream of its own, so that the short kernels around the scan (histogram, threshold,
 // compaction, select) of neighbouring calls overlap the scans and the host reads a call's status words one call later
 // -- the scheme of the dense search (sq_dense.hip).
+struct HammingPlan {   // what hamming_plan() decides for a call (the rules are there)
+    int kk = 0;                   // min(k, n)
+    u32 cap = 0;                  // candidates per query
+    bool small = false;           // n <= cap: the all-keys scan
+    long long key_stride = 0;     // keys per query in the slot's key array
+    int step = 0;                 // the histogram samples every step-th block
+    bool stream_ok = false;       // a register stream kernel exists for the width
+    bool ring = false, nt = false;  // hamming_ring_kernel, and its non-temporal build
+    bool fused = false;           // answered by hamming_pick_kernel: the mini-lists are what a flagged query is redone from
+    int thr_rank = 0;             // sample rank of the fused call's threshold (< kk: the tightened bet)
+    bool body_kernel = false;     // the fused call's stream is hamming_body_kernel
+    int qbatch = 0;               // queries per stream launch
+    int G = 0;                    // workgroups of the stream = mini-lists per query
+    u32 S = 0;                    // entries per mini-list
+    int map_rows = 0;             // 1: the mini-lists hold physical rows
+    bool prof = false;            // hipEvent timing of this call
+};
 struct HammingCall {
     bool pending = false;
     const u64* qs = nullptr;
@@ -36,12 +54,8 @@ struct HammingCall {
     int* out_dist = nullptr;
     long long* out_idx = nullptr;
     hipStream_t st = nullptr;
-    bool small = false, prof = false, use_event = false, force_fb = false;
-    bool fused = false;           // answered by hamming_pick_kernel: the mini-lists below are what a flagged query is redone from
-    int G = 0, map_rows = 0;
-    u32 S = 0;
-    long long key_stride = 0;
-    u32 cap = 0;
+    bool use_event = false, force_fb = false;
+    HammingPlan plan;
     sq_stats_t stats{};
 };
 struct HammingSlot {
@@ -663,132 +677,312 @@ struct HammingFinalize {
 namespace sq {
 
 // ------------------------------------------------------------- host driver
-template <int W, int C>
-static void launch_scan(const HammingHandle* h, const u64* qs, int nq, const int* thr, u64* keys, u32* cnt, u32 cap,
-                        long long key_stride, int mode, hipStream_t st) {
-    long long per_block = 256ll * C;
-    unsigned blocks = (unsigned)((h->n + per_block - 1) / per_block);
-    hipLaunchKernelGGL((hamming_scan_kernel<W, C>), dim3(blocks), dim3(256), 0, st, h->codes, h->n, h->pmul, qs, nq, thr, keys,
-                       cnt, cap, key_stride, mode);
+// Codes per thread of the register kernels: a thread of the scan / histogram kernels holds 4 / W codes of W words,
+// one of the stream / body kernels twice as many.  The template arguments and the host's block arithmetic both
+// come from here.
+constexpr int scan_codes(int W) { return W == 1 ? 4 : W == 2 ? 2 : 1; }
+constexpr int stream_codes(int W) { return 2 * scan_codes(W); }
+
+// Runtime code width -> compile-time: f(std::integral_constant<int, W>) for the one of Ws... that W equals,
+// otherwise() for every other width.
+template <int... Ws, class F, class Other>
+static int with_width(int W, F&& f, Other&& otherwise) {
+    int rc = SQ_OK;
+    const bool hit = ((W == Ws && ((rc = f(std::integral_constant<int, Ws>{})), true)) || ...);
+    return hit ? rc : otherwise();
 }
 
-static void scan_dispatch(const HammingHandle* h, const u64* qs, int nq, const int* thr, u64* keys, u32* cnt, u32 cap,
-                          long long key_stride, int mode, hipStream_t st) {
-    switch (h->words) {
-        case 1: launch_scan<1, 4>(h, qs, nq, thr, keys, cnt, cap, key_stride, mode, st); break;
-        case 2: launch_scan<2, 2>(h, qs, nq, thr, keys, cnt, cap, key_stride, mode, st); break;
-        case 4: launch_scan<4, 1>(h, qs, nq, thr, keys, cnt, cap, key_stride, mode, st); break;
-        default: {
-            unsigned blocks = (unsigned)((h->n + 255) / 256);
-            hipLaunchKernelGGL(hamming_scan_generic_kernel, dim3(blocks), dim3(256), 0, st, h->codes, h->n, h->pmul, h->words,
-                               qs, nq, thr, keys, cnt, cap, key_stride, mode);
-        }
+static int scan_dispatch(const HammingHandle* h, const u64* qs, int nq, const int* thr, u64* keys, u32* cnt, u32 cap,
+                         long long key_stride, int mode, hipStream_t st) {
+    return with_width<1, 2, 4>(
+        h->words,
+        [&](auto w) {
+            constexpr int W = decltype(w)::value, C = scan_codes(W);
+            const unsigned blocks = (unsigned)((h->n + 256ll * C - 1) / (256ll * C));
+            return launch<hamming_scan_kernel<W, C>>(dim3(blocks), dim3(256), 0, st, h->codes, h->n, h->pmul, qs, nq, thr, keys, cnt, cap,
+                                                     key_stride, mode);
+        },
+        [&] {
+            const unsigned blocks = (unsigned)((h->n + 255) / 256);
+            return launch<hamming_scan_generic_kernel>(dim3(blocks), dim3(256), 0, st, h->codes, h->n, h->pmul, h->words, qs, nq, thr, keys,
+                                                       cnt, cap, key_stride, mode);
+        });
+}
+
+// blocks of the sampled histogram: every `step`-th block of 256 * scan_codes(W) codes
+static unsigned hist_blocks(const HammingHandle* h, int step) {
+    const long long per_block = 256ll * scan_codes(h->words);
+    const long long blocks_all = (h->n + per_block - 1) / per_block;
+    return (unsigned)((blocks_all + step - 1) / step);
+}
+
+static int hist_dispatch(const HammingHandle* h, const u64* qs, int nq, int bits, u32* hist, int step, hipStream_t st) {
+    const unsigned blocks = hist_blocks(h, step);
+    return with_width<1, 2, 4>(
+        h->words,
+        [&](auto w) {
+            constexpr int W = decltype(w)::value;
+            const int nb = bits + 1;
+            int qchunk = (48 * 1024 / 4) / nb;
+            if (qchunk < 1) qchunk = 1;
+            if (qchunk > nq) qchunk = nq;
+            const unsigned gy = (unsigned)((nq + qchunk - 1) / qchunk);
+            return launch<hamming_hist_kernel<W, scan_codes(W)>>(dim3(blocks, gy), dim3(256), (size_t)qchunk * nb * 4, st, h->codes, h->n, qs, nq,
+                                                                 bits, hist, step, qchunk);
+        },
+        [&] { return launch<hamming_hist_generic_kernel>(dim3(blocks), dim3(256), 0, st, h->codes, h->n, h->words, qs, nq, bits, hist, step); });
+}
+
+// Everything a search decides before it touches the device, from the handle, its options and the call's shape.
+// hamming_enqueue launches what the plan says; hamming_resolve replays parts of it (HammingCall::plan).
+static HammingPlan hamming_plan(const HammingHandle* h, int nq, int k, bool use_event) {
+    const long long n = h->n;
+    const int W = h->words;
+    HammingPlan p;
+    const int kk = p.kk = (int)(k < n ? k : n);
+    p.prof = h->opt.profile == 1 || (h->opt.profile > 1 && (!use_event || h->async_calls % (unsigned)h->opt.profile == 0));
+    u32 cap = h->opt.candidate_cap > 0 ? (u32)h->opt.candidate_cap : 65536u;
+    // room for the tie group at the threshold distance (integer distances: the codes AT the threshold can outnumber
+    // those below it several times)
+    if (h->opt.candidate_cap <= 0 && cap < (u32)std::min<long long>(16ll * kk, 1ll << 30)) cap = (u32)std::min<long long>(16ll * kk, 1ll << 30);
+    if (cap < (u32)(2 * kk)) cap = (u32)(2 * kk);
+    p.cap = cap;
+    p.small = n <= (long long)cap;
+    p.key_stride = p.small ? n : (long long)cap;
+    if (p.small) return p;   // one all-keys scan and the select: nothing else to decide
+
+    int step = h->opt.sample_stride > 0 ? h->opt.sample_stride : 64;
+    // keep the sample comfortably larger than k
+    const long long per_block = 256ll * scan_codes(W);
+    const long long blocks_all = (n + per_block - 1) / per_block;
+    while (step > 1 && (blocks_all / step) * per_block < 64ll * kk) step >>= 1;
+    // the threshold admits ~step * k codes (k of them in the 1/step sample) times the tie expansion: keep that
+    // inside the candidate lists.  (At the default step of 64 every query with k >= ~500 overflowed its list
+    // and took the exact path: 18 ms per query at 10 M codes, found by bench.py --workload lsh_c3.)
+    if (h->opt.sample_stride <= 0)
+        while (step > 1 && (long long)step * kk * 8 > (long long)cap) step >>= 1;
+    p.step = step;
+    const bool stream_ok = p.stream_ok = W == 1 || W == 2 || W == 4;
+    // LDS-DMA ring (hamming_ring_kernel): HBM bound batches over arrays the MALL cannot hold.  Beyond ~24 queries
+    // the inner loop is VALU bound and the register kernel's 32 waves per CU win.
+    const size_t code_bytes = (size_t)n * W * 8;
+    const bool ring_shape = (W == 1 || W == 2 || W == 4 || W == 8 || W == 16) && (reinterpret_cast<uintptr_t>(h->codes) & 15u) == 0 &&
+                            n * (long long)W * 8 >= 2ll * HR_UNIT * HR_WAVES;
+    const bool ring = p.ring = ring_shape && (h->opt.hamming_ring == 1 ||
+                                              (h->opt.hamming_ring < 0 && nq <= 24 && code_bytes >= ((size_t)256 << 20)) ||
+                                              (h->opt.hamming_ring < 0 && !stream_ok && nq <= 64));
+    // non-temporal stream for arrays far beyond the MALL (read once per call)
+    p.nt = code_bytes >= ((size_t)512 << 20);
+    // Small batches in three launches (sq_hamming_fused.hpp): head (sampled histogram + thresholds by the last
+    // workgroup), the stream, pick (prefix sum over the mini-lists, exact k-th distance, gather, sort, results).
+    // (calls beyond 32 queries -- up to one stream launch's batch -- keep the threshold launch: hamming_body_kernel then reads
+    // the thresholds instead of computing them in its prologue)
+    const int fused_max_nq = ring ? HF_MAX_NQ : (W == 4 ? 384 : 1024);
+    const bool fused = p.fused = h->opt.hamming_fused != 0 && !h->no_fused && stream_ok && nq <= fused_max_nq && 2 * kk <= HF_SORT_CAP;
+    // The fused call's threshold: the general chain takes the smallest t whose SAMPLE count reaches k -- safe (the sample
+    // is a subset) and loose: ~step x k codes pass (7.8 k per query at 10 M x 64 bits, k = 100), and with 0.4 survivors
+    // per wave and chunk the emission path, not the popcounts, is half of the stream's time.  The pick kernel counts what
+    // the stream admitted, so the threshold may be a bet: the smallest t whose sample count reaches r, where a t that
+    // admits fewer than k codes overall would show r in a 1/step sample with probability < 1e-9 (Poisson tail:
+    // r = lambda + 7 sqrt(lambda) + 6, lambda = k / step).  A lost bet (M < k) is seen by the pick kernel and the call
+    // is redone with the safe rule (hamming_resolve); results are exact either way.
+    p.thr_rank = kk;
+    if (fused && h->opt.hamming_tighten != 0) {
+        const double lambda = (double)kk / (double)step;
+        const int r = (int)ceil(lambda + 7.0 * sqrt(lambda) + 6.0);
+        if (r < p.thr_rank) p.thr_rank = r;
+        if (h->opt.hamming_tighten >= 2) p.thr_rank = 1;   // (testing: a bet that is usually lost -- the redo path)
     }
-}
+    // the stream of a fused call: hamming_body_kernel (queries broadcast with v_readlane: two instructions per query word
+    // and chunk -- 128- and 256-bit codes beyond 32 queries measure 4-35 % slower with it than with the LDS-broadcast
+    // stream kernel, tools/hamming_width_sweep.sh) or, for those, hamming_stream_kernel between the tightened threshold
+    // and the pick kernel
+    p.body_kernel = fused && !ring && (W == 1 || nq <= HF_MAX_NQ);
+    p.map_rows = (ring || p.body_kernel) ? 1 : 0;   // (ring and body kernels leave physical rows in the mini-lists)
+    if (!stream_ok && !ring) return p;   // the one-kernel scan with global counters: no mini-lists
 
-template <int W, int C>
-static void launch_hist(const HammingHandle* h, const u64* qs, int nq, int bits, u32* hist, int step, hipStream_t st) {
-    long long per_block = 256ll * C;
-    long long blocks_all = (h->n + per_block - 1) / per_block;
-    unsigned blocks = (unsigned)((blocks_all + step - 1) / step);
-    int nb = bits + 1;
-    int qchunk = (48 * 1024 / 4) / nb;
-    if (qchunk < 1) qchunk = 1;
-    if (qchunk > nq) qchunk = nq;
-    unsigned gy = (unsigned)((nq + qchunk - 1) / qchunk);
-    size_t lds = (size_t)qchunk * nb * 4;
-    hipLaunchKernelGGL((hamming_hist_kernel<W, C>), dim3(blocks, gy), dim3(256), lds, st, h->codes, h->n, qs, nq, bits,
-                       hist, step, qchunk);
-}
-
-static void hist_dispatch(const HammingHandle* h, const u64* qs, int nq, int bits, u32* hist, int step,
-                          hipStream_t st) {
-    switch (h->words) {
-        case 1: launch_hist<1, 4>(h, qs, nq, bits, hist, step, st); break;
-        case 2: launch_hist<2, 2>(h, qs, nq, bits, hist, step, st); break;
-        case 4: launch_hist<4, 1>(h, qs, nq, bits, hist, step, st); break;
-        default: {
-            long long blocks_all = (h->n + 255) / 256;
-            unsigned blocks = (unsigned)((blocks_all + step - 1) / step);
-            hipLaunchKernelGGL(hamming_hist_generic_kernel, dim3(blocks), dim3(256), 0, st, h->codes, h->n, h->words,
-                               qs, nq, bits, hist, step);
-        }
-    }
-}
-
-static constexpr int kSelectLdsKeys64 = 16384;  // 128 KiB of LDS for the candidate keys
-
-template <class Post>
-static int select_launch(const u64* keys, const u32* cnt, u32 cap, long long stride, int k, int nq, u64* out,
-                         hipStream_t st, DevBuf& sort_scratch, Post post) {
-    static bool attr_set = false;
-    if (k > kSelectLdsKeys64)  // linear.py:235-238 has no limit on n: the any-k sorted select (sq_select.hpp)
-        return sort_select_large<u64, Post>(keys, cnt, cap, stride, k, nq, out, sort_scratch, post, st);
-    const size_t lds = (size_t)(kSelectLdsKeys64 + SELECT_SORT_MAX) * sizeof(u64);
-    if (!attr_set) {
-        SQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&select_topk_kernel<u64, Post>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_set = true;
-    }
-    hipLaunchKernelGGL((select_topk_kernel<u64, Post>), dim3(nq), dim3(1024), lds, st, keys, cnt, cap, stride, k,
-                       kSelectLdsKeys64, out, post);
-    return SQ_OK;
-}
-
-// Wait for an event the way stream_wait waits for a stream (poll, then block).
-static hipError_t hamming_event_wait(hipEvent_t ev) {
-    const long long budget_us = g_opt.spin_wait_us;
-    if (budget_us > 0) {
-        const auto t0 = std::chrono::steady_clock::now();
-        for (;;) {
-            for (int i = 0; i < 64; ++i) {
-                const hipError_t e = hipEventQuery(ev);
-                if (e != hipErrorNotReady) return e;
+    // streaming scan into per-(block, query) mini-lists, then a prefix-sum compaction: no global atomics
+    // register kernel: 8 workgroups per CU (32 waves: the VALU-bound inner loop wants full occupancy); the LDS copy
+    // of the queries (nq * (8W+8) bytes) must fit 8 times, so wide codes take the queries in smaller batches.
+    // ring kernel: one 512-thread workgroup per CU -- on three quarters of the CUs when calls are pipelined and the
+    // pass is HBM bound: the neighbouring calls' select needs most of a CU's LDS, and such a stream loses
+    // nothing on 192 CUs
+    p.qbatch = ring ? 64 : (W == 4 ? 384 : 1024);
+    const int cus = cu_count(h->device);
+    // (from ~8 queries per pass the ring kernel is VALU bound and wants every CU; the neighbours' short kernels
+    // then simply queue behind it)
+    int G = ring ? (use_event && nq <= 4 ? cus * 3 / 4 : cus) : 8 * cus;
+    if (G > 2048) G = 2048;
+    if (ring) {
+        const long long units = (n * (long long)W * 8) / HR_UNIT;
+        if ((long long)G * HR_WAVES > units) G = (int)std::max<long long>(1, units / HR_WAVES);
+    } else {
+        const long long per_chunk = 256ll * stream_codes(W);
+        const long long nchunks = (n + per_chunk - 1) / per_chunk;
+        if (fused && nchunks > (long long)8 * cus && 8 * cus <= 2048) {
+            // every CU holds j workgroups that walk ceil(nchunks / (j CUs)) chunks each: the pass lasts j * that many
+            // chunk times on the fullest CU.  10 M x 64-bit codes = 4883 chunks: 8 workgroups per CU -> 8 x 3 = 24
+            // chunk times where 4883 / 256 = 19.1 would do; 5 per CU -> 5 x 4 = 20
+            // (at most 6 workgroups of the body kernel fit a CU: 80 VGPRs, and nq * (8 W + 8) bytes of LDS each)
+            int jmax = 6;
+            const size_t lds_wg = (size_t)nq * (W * 8 + 8);
+            if (lds_wg * jmax > (size_t)160 * 1024) jmax = (int)((size_t)160 * 1024 / lds_wg);
+            if (jmax < 3) jmax = 3;
+            int best_j = jmax;
+            long long best = -1;
+            for (int j = jmax; j >= 3; --j) {
+                const long long cost = (long long)j * ((nchunks + (long long)j * cus - 1) / ((long long)j * cus));
+                if (best < 0 || cost < best) best = cost, best_j = j;
             }
-            if (std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count() > budget_us)
-                break;
+            G = best_j * cus;
         }
+        if ((long long)G > nchunks) G = (int)nchunks;  // short arrays: fewer, fuller mini-lists
     }
-    return hipEventSynchronize(ev);
+    p.G = G;
+    long long want = 8ll * 128ll * kk / G;  // ~8x the expected fill of a mini-list
+    if (fused && p.thr_rank < kk) want = 8ll * 128ll * p.thr_rank / G;   // (the tightened threshold admits ~ rank x step codes)
+    p.S = 32;
+    while ((long long)p.S < want && p.S < 4096u) p.S <<= 1;
+    return p;
 }
 
-template <int W>
-static int ring_launch(const HammingHandle* h, bool nt, int G, const u64* qc, int nqc, const int* thr, u64* seg, u32* bcnt, u32 S,
-                       hipStream_t st) {
-    static bool attr_set[2] = {false, false};
-    const size_t lds = (size_t)HR_WAVES * HR_NSTAGE * HR_UNIT + (size_t)nqc * 4;
-    if (!attr_set[nt ? 1 : 0]) {
-        if (nt)
-            SQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&hamming_ring_kernel<W, true>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        else
-            SQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&hamming_ring_kernel<W, false>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_set[nt ? 1 : 0] = true;
+// A buffer that is wiped once per allocation and that its kernels leave clean: `zeroed` is the allocation wiped last.
+static int reserve_zeroed(DevBuf& b, void*& zeroed, size_t bytes, hipStream_t st) {
+    SQ_TRY(b.reserve(bytes));
+    if (zeroed != b.p) {
+        SQ_HIP(hipMemsetAsync(b.p, 0, b.cap, st));
+        zeroed = b.p;
     }
-    if (nt)
-        hipLaunchKernelGGL((hamming_ring_kernel<W, true>), dim3(G), dim3(HR_WAVES * 64), lds, st, h->codes, h->n, h->pmul, qc, nqc, thr,
-                           seg, bcnt, S);
-    else
-        hipLaunchKernelGGL((hamming_ring_kernel<W, false>), dim3(G), dim3(HR_WAVES * 64), lds, st, h->codes, h->n, h->pmul, qc, nqc, thr,
-                           seg, bcnt, S);
     return SQ_OK;
+}
+
+// select + finalisation of the slot's call over `keys` ([nq][p.key_stride], up to `cap` valid per query)
+static int select_finalize(const HammingHandle* h, HammingSlot& s, u32 cap, hipStream_t st) {
+    const HammingCall& c = s.call;
+    u32* cnt = s.cnt.as<u32>();
+    return select_launch_t<u64>(s.keys.as<u64>(), cnt, cap, c.plan.key_stride, c.k, c.nq, s.out_keys.as<u64>(),
+                                HammingFinalize{cnt, cap, c.plan.kk, h->id_base, c.out_dist, c.out_idx, s.status.as<u32>(),
+                                                static_cast<u32*>(s.status_host.dev), c.nq},
+                                st, s.sort_tmp);
+}
+
+// The stream of `nqc` queries into the mini-lists: the LDS-DMA ring or the register kernel.
+static int stream_launch(const HammingHandle* h, const HammingPlan& p, const u64* qc, int nqc, const int* thr, u64* seg, u32* bcnt,
+                         hipStream_t st) {
+    if (p.ring) {
+        const size_t lds = (size_t)HR_WAVES * HR_NSTAGE * HR_UNIT + (size_t)nqc * 4;
+        return with_width<1, 2, 4, 8, 16>(
+            h->words,
+            [&](auto w) {
+                constexpr int W = decltype(w)::value;
+                const dim3 grid(p.G), block(HR_WAVES * 64);
+                return p.nt ? launch_lds<hamming_ring_kernel<W, true>>(160 * 1024, grid, block, lds, st, h->codes, h->n, h->pmul, qc, nqc, thr, seg, bcnt, p.S)
+                            : launch_lds<hamming_ring_kernel<W, false>>(160 * 1024, grid, block, lds, st, h->codes, h->n, h->pmul, qc, nqc, thr, seg, bcnt, p.S);
+            },
+            [&] { return fail(SQ_ERR_UNSUPPORTED, "hamming ring: %d-word codes", h->words); });
+    }
+    return with_width<1, 2, 4>(
+        h->words,
+        [&](auto w) {
+            constexpr int W = decltype(w)::value;
+            return launch<hamming_stream_kernel<W, stream_codes(W)>>(dim3(p.G), dim3(256), (size_t)nqc * (W * 8 + 8), st, h->codes, h->n, h->pmul, qc,
+                                                                     nqc, thr, seg, bcnt, p.S);
+        },
+        [&] { return fail(SQ_ERR_UNSUPPORTED, "hamming stream: %d-word codes", h->words); });
+}
+
+// n <= cap: every key of every query (one scan), then the select.
+static int enqueue_small(HammingHandle* h, HammingSlot& s, const HammingPlan& p, hipStream_t st) {
+    const HammingCall& c = s.call;
+    const u32 n = (u32)h->n;
+    SQ_TRY(launch<fill_u32_kernel>(dim3((c.nq + 255) / 256), dim3(256), 0, st, s.cnt.as<u32>(), (long long)c.nq, n));
+    if (p.prof) SQ_HIP(hipEventRecord(s.ev[1], st));
+    SQ_TRY(scan_dispatch(h, c.qs, c.nq, s.thr.as<int>(), s.keys.as<u64>(), s.cnt.as<u32>(), n, p.key_stride, /*mode*/ 1, st));
+    if (p.prof) SQ_HIP(hipEventRecord(s.ev[2], st));
+    return select_finalize(h, s, n, st);
+}
+
+// Small batches in three launches (sq_hamming_fused.hpp): sampled histogram (+ the threshold launch where the stream does
+// not compute the thresholds itself), the stream, pick.  One pass: nq <= p.qbatch.
+static int enqueue_fused(HammingHandle* h, HammingSlot& s, const HammingPlan& p, hipStream_t st) {
+    const HammingCall& c = s.call;
+    const int nq = c.nq, bits = h->words * 64;
+    int* thr = s.thr.as<int>();
+    SQ_TRY(reserve_zeroed(s.fhist, s.fhist_zeroed, (size_t)(nq > HF_MAX_NQ ? nq : HF_MAX_NQ) * (bits + 1) * 4, st));
+    u32* hist = s.fhist.as<u32>();
+    if (nq > 8 && nq <= HF_MAX_NQ) {   // a lane per query: no same-address LDS atomics (sq_hamming_fused.hpp)
+        SQ_TRY(with_width<1, 2, 4>(
+            h->words,
+            [&](auto w) {
+                constexpr int W = decltype(w)::value;
+                return launch<hamming_hist_by_query_kernel<W, scan_codes(W)>>(dim3(hist_blocks(h, p.step)), dim3(256), (size_t)32 * (bits + 1) * 4, st,
+                                                                              h->codes, h->n, c.qs, nq, bits, hist, p.step);
+            },
+            [&] { return fail(SQ_ERR_UNSUPPORTED, "hamming fused: %d-word codes", h->words); }));
+    } else {
+        SQ_TRY(hist_dispatch(h, c.qs, nq, bits, hist, p.step, st));
+    }
+    if (p.ring || nq > HF_MAX_NQ) SQ_TRY(launch<hamming_thr_kernel>(dim3((nq + 63) / 64), dim3(64), 0, st, hist, nq, bits, p.thr_rank, thr));
+    if (p.prof) SQ_HIP(hipEventRecord(s.ev[1], st));
+    SQ_TRY(s.bcnt.reserve((size_t)p.G * nq * 4));
+    SQ_TRY(s.seg.reserve((size_t)p.G * nq * p.S * 8));
+    u64* seg = s.seg.as<u64>();
+    u32* bcnt = s.bcnt.as<u32>();
+    if (p.body_kernel) {
+        SQ_TRY(with_width<1, 2, 4>(
+            h->words,
+            [&](auto w) {
+                constexpr int W = decltype(w)::value;
+                return launch<hamming_body_kernel<W, stream_codes(W)>>(dim3(p.G), dim3(256), (size_t)nq * (W * 8 + 8), st, h->codes, h->n, h->pmul, c.qs,
+                                                                       nq, nq <= HF_MAX_NQ ? hist : nullptr, bits, p.thr_rank, thr, seg, bcnt, p.S);
+            },
+            [&] { return fail(SQ_ERR_UNSUPPORTED, "hamming fused: %d-word codes", h->words); }));
+    } else {
+        SQ_TRY(stream_launch(h, p, c.qs, nq, thr, seg, bcnt, st));
+    }
+    if (p.prof) SQ_HIP(hipEventRecord(s.ev[2], st));
+    return launch<hamming_pick_kernel>(dim3(nq), dim3(1024), 0, st, seg, bcnt, p.G, nq, p.S, bits, c.k, p.kk, thr, p.map_rows, h->pmul, h->n,
+                                       h->id_base, c.out_dist, c.out_idx, s.status.as<u32>(), static_cast<u32*>(s.status_host.dev), nq, p.cap, hist);
+}
+
+// The general chain: sampled histogram, thresholds (the safe rank-k rule), the stream and a compaction per query batch --
+// or, for the widths without a stream kernel, one scan with global counters -- then the select.
+static int enqueue_general(HammingHandle* h, HammingSlot& s, const HammingPlan& p, hipStream_t st) {
+    const HammingCall& c = s.call;
+    const int nq = c.nq, W = h->words, bits = W * 64;
+    u32* cnt = s.cnt.as<u32>();
+    int* thr = s.thr.as<int>();
+    u64* keys = s.keys.as<u64>();
+    const bool mini_lists = p.stream_ok || p.ring;
+    SQ_TRY(s.hist.reserve((size_t)nq * (bits + 1) * 4));
+    u32* hist = s.hist.as<u32>();
+    SQ_HIP(hipMemsetAsync(hist, 0, (size_t)nq * (bits + 1) * 4, st));
+    if (!mini_lists) SQ_HIP(hipMemsetAsync(cnt, 0, (size_t)nq * 4, st));  // the compaction writes cnt itself
+    SQ_TRY(hist_dispatch(h, c.qs, nq, bits, hist, p.step, st));
+    SQ_TRY(launch<hamming_thr_kernel>(dim3((nq + 63) / 64), dim3(64), 0, st, hist, nq, bits, p.kk, thr));
+    if (p.prof) SQ_HIP(hipEventRecord(s.ev[1], st));
+    if (mini_lists) {
+        SQ_TRY(s.bcnt.reserve((size_t)p.G * nq * 4));
+        u32* bcnt = s.bcnt.as<u32>();
+        for (int q0 = 0; q0 < nq; q0 += p.qbatch) {
+            const int nqc = nq - q0 < p.qbatch ? nq - q0 : p.qbatch;
+            SQ_TRY(s.seg.reserve((size_t)p.G * nqc * p.S * 8));
+            u64* seg = s.seg.as<u64>();
+            SQ_TRY(stream_launch(h, p, c.qs + (long long)q0 * W, nqc, thr + q0, seg, bcnt, st));
+            SQ_TRY(launch<hamming_compact_kernel>(dim3(nqc, COMPACT_SLICES), dim3(256), 0, st, seg, bcnt, p.G, nqc, p.S,
+                                                  keys + (long long)q0 * p.key_stride, cnt + q0, p.cap, p.key_stride, p.map_rows, h->pmul, h->n));
+        }
+    } else {
+        SQ_TRY(scan_dispatch(h, c.qs, nq, thr, keys, cnt, p.cap, p.key_stride, /*mode*/ 0, st));
+    }
+    if (p.prof) SQ_HIP(hipEventRecord(s.ev[2], st));
+    return select_finalize(h, s, p.cap, st);
 }
 
 // Enqueue one search on `st` with the workspace of slot `s`; nothing is waited for.  hamming_resolve() finishes
 // the call: it waits for the kernels, reads the status words and sends overflowing queries down the exact path.
 static int hamming_enqueue(HammingHandle* h, HammingSlot& s, const u64* qs, int nq, int k, int* out_dist, long long* out_idx,
                            hipStream_t st, bool use_event) {
-    const long long n = h->n;
-    const int W = h->words, bits = W * 64;
-    const int kk = (int)(k < n ? k : n);
-    const bool prof = h->opt.profile == 1 || (h->opt.profile > 1 && (!use_event || h->async_calls % (unsigned)h->opt.profile == 0));
-    u32 cap = h->opt.candidate_cap > 0 ? (u32)h->opt.candidate_cap : 65536u;
-    // room for the tie group at the threshold distance (integer distances: the codes AT the threshold can outnumber
-    // those below it several times)
-    if (h->opt.candidate_cap <= 0 && cap < (u32)std::min<long long>(16ll * kk, 1ll << 30)) cap = (u32)std::min<long long>(16ll * kk, 1ll << 30);
-    if (cap < (u32)(2 * kk)) cap = (u32)(2 * kk);
-    const bool small = n <= (long long)cap;
     HammingCall& c = s.call;
     c = HammingCall{};
     c.qs = qs;
@@ -797,11 +991,10 @@ static int hamming_enqueue(HammingHandle* h, HammingSlot& s, const u64* qs, int 
     c.out_dist = out_dist;
     c.out_idx = out_idx;
     c.st = st;
-    c.small = small;
-    c.prof = prof;
     c.use_event = use_event;
-    c.cap = cap;
-    if (prof) {
+    c.plan = hamming_plan(h, nq, k, use_event);
+    const HammingPlan& p = c.plan;
+    if (p.prof) {
         for (auto& e : s.ev)
             if (!e) SQ_HIP(hipEventCreate(&e));
         SQ_HIP(hipEventRecord(s.ev[0], st));
@@ -810,207 +1003,14 @@ static int hamming_enqueue(HammingHandle* h, HammingSlot& s, const u64* qs, int 
     SQ_TRY(s.thr.reserve((size_t)nq * 4));
     SQ_TRY(s.out_keys.reserve((size_t)nq * k * 8));
     SQ_TRY(s.status.reserve((size_t)nq * 4));
-    SQ_TRY(s.status_host.reserve((size_t)nq * 8));
-    u32* hs = reinterpret_cast<u32*>(s.status_host.p);  // [status (nq) | counts (nq)]
-    u32* hs_dev = nullptr;
-    SQ_TRY(s.status_host.device_ptr(reinterpret_cast<void**>(&hs_dev)));
-    u32* cnt = s.cnt.as<u32>();
-    int* thr = s.thr.as<int>();
-    u64* okeys = s.out_keys.as<u64>();
-    u32* status = s.status.as<u32>();
-    const long long key_stride = small ? n : (long long)cap;
-    SQ_TRY(s.keys.reserve((size_t)nq * key_stride * 8));
-    u64* keys = s.keys.as<u64>();
-
-    if (small) {
-        hipLaunchKernelGGL(fill_u32_kernel, dim3((nq + 255) / 256), dim3(256), 0, st, cnt, (long long)nq, (u32)n);
-        if (prof) SQ_HIP(hipEventRecord(s.ev[1], st));
-        scan_dispatch(h, qs, nq, thr, keys, cnt, (u32)n, key_stride, /*mode*/ 1, st);
-        if (prof) SQ_HIP(hipEventRecord(s.ev[2], st));
-        c.stats.scan_launches = 1;
-        c.stats.bytes_scanned = n * W * 8;
-        SQ_TRY(select_launch(keys, cnt, (u32)n, key_stride, k, nq, okeys, st, s.sort_tmp,
-                             HammingFinalize{cnt, (u32)n, kk, h->id_base, out_dist, out_idx, status, hs_dev, nq}));
-    } else {
-        int step = h->opt.sample_stride > 0 ? h->opt.sample_stride : 64;
-        // keep the sample comfortably larger than k
-        const long long per_block = 256ll * (W == 1 ? 4 : W == 2 ? 2 : 1);
-        const long long blocks_all = (n + per_block - 1) / per_block;
-        while (step > 1 && (blocks_all / step) * per_block < 64ll * kk) step >>= 1;
-        // the threshold admits ~step * k codes (k of them in the 1/step sample) times the tie expansion: keep that
-        // inside the candidate lists.  (At the default step of 64 every query with k >= ~500 overflowed its list
-        // and took the exact path: 18 ms per query at 10 M codes, found by bench.py --workload lsh_c3.)
-        if (h->opt.sample_stride <= 0)
-            while (step > 1 && (long long)step * kk * 8 > (long long)cap) step >>= 1;
-        const bool stream_ok = W == 1 || W == 2 || W == 4;
-        // LDS-DMA ring (hamming_ring_kernel): HBM bound batches over arrays the MALL cannot hold.  Beyond ~24 queries
-        // the inner loop is VALU bound and the register kernel's 32 waves per CU win.
-        const size_t code_bytes = (size_t)n * W * 8;
-        const bool ring_shape = (W == 1 || W == 2 || W == 4 || W == 8 || W == 16) && (reinterpret_cast<uintptr_t>(h->codes) & 15u) == 0 &&
-                                n * (long long)W * 8 >= 2ll * HR_UNIT * HR_WAVES;
-        const bool ring = ring_shape && (h->opt.hamming_ring == 1 ||
-                                         (h->opt.hamming_ring < 0 && nq <= 24 && code_bytes >= ((size_t)256 << 20)) ||
-                                         (h->opt.hamming_ring < 0 && !stream_ok && nq <= 64));
-        // Small batches in three launches (sq_hamming_fused.hpp): head (sampled histogram + thresholds by the last
-        // workgroup), the stream, pick (prefix sum over the mini-lists, exact k-th distance, gather, sort, results).
-        // (calls beyond 32 queries -- up to one stream launch's batch -- keep the threshold launch: hamming_body_kernel then reads
-        // the thresholds instead of computing them in its prologue)
-        const int fused_max_nq = ring ? HF_MAX_NQ : (W == 4 ? 384 : 1024);
-        const bool fused = h->opt.hamming_fused != 0 && !h->no_fused && stream_ok && nq <= fused_max_nq && 2 * kk <= HF_SORT_CAP;
-        // The fused call's threshold: the general chain takes the smallest t whose SAMPLE count reaches k -- safe (the sample
-        // is a subset) and loose: ~step x k codes pass (7.8 k per query at 10 M x 64 bits, k = 100), and with 0.4 survivors
-        // per wave and chunk the emission path, not the popcounts, is half of the stream's time.  The pick kernel counts what
-        // the stream admitted, so the threshold may be a bet: the smallest t whose sample count reaches r, where a t that
-        // admits fewer than k codes overall would show r in a 1/step sample with probability < 1e-9 (Poisson tail:
-        // r = lambda + 7 sqrt(lambda) + 6, lambda = k / step).  A lost bet (M < k) is seen by the pick kernel and the call
-        // is redone with the safe rule (hamming_resolve); results are exact either way.
-        int thr_rank = kk;
-        if (fused && h->opt.hamming_tighten != 0) {
-            const double lambda = (double)kk / (double)step;
-            const int r = (int)ceil(lambda + 7.0 * sqrt(lambda) + 6.0);
-            if (r < thr_rank) thr_rank = r;
-            if (h->opt.hamming_tighten >= 2) thr_rank = 1;   // (testing: a bet that is usually lost -- the redo path)
-        }
-        c.fused = fused;
-        // the stream of a fused call: hamming_body_kernel (queries broadcast with v_readlane: two instructions per query word
-        // and chunk -- 128- and 256-bit codes beyond 32 queries measure 4-35 % slower with it than with the LDS-broadcast
-        // stream kernel, tools/hamming_width_sweep.sh) or, for those, hamming_stream_kernel between the tightened threshold
-        // and the pick kernel
-        const bool body_kernel = fused && !ring && (W == 1 || nq <= HF_MAX_NQ);
-        u32* hist = nullptr;
-        if (fused) {
-            const size_t words = (size_t)(nq > HF_MAX_NQ ? nq : HF_MAX_NQ) * (bits + 1);
-            SQ_TRY(s.fhist.reserve(words * 4));
-            if (s.fhist_zeroed != s.fhist.p) {   // a new allocation: wiped once, the pick kernel leaves it clean
-                SQ_HIP(hipMemsetAsync(s.fhist.p, 0, s.fhist.cap, st));
-                s.fhist_zeroed = s.fhist.p;
-            }
-            hist = s.fhist.as<u32>();
-            if (nq > 8 && nq <= HF_MAX_NQ) {   // a lane per query: no same-address LDS atomics (sq_hamming_fused.hpp)
-                const long long blocks_all2 = (n + per_block - 1) / per_block;
-                const unsigned blocks = (unsigned)((blocks_all2 + step - 1) / step);
-                const size_t lds = (size_t)32 * (bits + 1) * 4;
-                if (W == 1)
-                    hipLaunchKernelGGL((hamming_hist_by_query_kernel<1, 4>), dim3(blocks), dim3(256), lds, st, h->codes, n, qs, nq, bits, hist, step);
-                else if (W == 2)
-                    hipLaunchKernelGGL((hamming_hist_by_query_kernel<2, 2>), dim3(blocks), dim3(256), lds, st, h->codes, n, qs, nq, bits, hist, step);
-                else
-                    hipLaunchKernelGGL((hamming_hist_by_query_kernel<4, 1>), dim3(blocks), dim3(256), lds, st, h->codes, n, qs, nq, bits, hist, step);
-            } else {
-                hist_dispatch(h, qs, nq, bits, hist, step, st);
-            }
-            if (ring || nq > HF_MAX_NQ) hipLaunchKernelGGL(hamming_thr_kernel, dim3((nq + 63) / 64), dim3(64), 0, st, hist, nq, bits, thr_rank, thr);
-        } else {
-            SQ_TRY(s.hist.reserve((size_t)nq * (bits + 1) * 4));
-            hist = s.hist.as<u32>();
-            SQ_HIP(hipMemsetAsync(hist, 0, (size_t)nq * (bits + 1) * 4, st));
-            if (!stream_ok && !ring) SQ_HIP(hipMemsetAsync(cnt, 0, (size_t)nq * 4, st));  // the compaction writes cnt itself
-            hist_dispatch(h, qs, nq, bits, hist, step, st);
-            hipLaunchKernelGGL(hamming_thr_kernel, dim3((nq + 63) / 64), dim3(64), 0, st, hist, nq, bits, kk, thr);
-        }
-        if (prof) SQ_HIP(hipEventRecord(s.ev[1], st));
-        if (stream_ok || ring) {
-            // streaming scan into per-(block, query) mini-lists, then a prefix-sum compaction: no global atomics
-            // register kernel: 8 workgroups per CU (32 waves: the VALU-bound inner loop wants full occupancy); the LDS copy
-            // of the queries (nq * (8W+8) bytes) must fit 8 times, so wide codes take the queries in smaller batches.
-            // ring kernel: one 512-thread workgroup per CU -- on three quarters of the CUs when calls are pipelined and the
-            // pass is HBM bound: the neighbouring calls' select needs most of a CU's LDS, and such a stream loses
-            // nothing on 192 CUs
-            const int qbatch = ring ? 64 : (W == 4 ? 384 : 1024);
-            const int cus = cu_count(h->device);
-            // (from ~8 queries per pass the ring kernel is VALU bound and wants every CU; the neighbours' short kernels
-            // then simply queue behind it)
-            int G = ring ? (use_event && nq <= 4 ? cus * 3 / 4 : cus) : 8 * cus;
-            if (G > 2048) G = 2048;
-            if (ring) {
-                const long long units = (n * (long long)W * 8) / HR_UNIT;
-                if ((long long)G * HR_WAVES > units) G = (int)std::max<long long>(1, units / HR_WAVES);
-            } else {
-                const long long per_chunk = 256ll * (W == 1 ? 8 : W == 2 ? 4 : 2);
-                const long long nchunks = (n + per_chunk - 1) / per_chunk;
-                if (fused && nchunks > (long long)8 * cus && 8 * cus <= 2048) {
-                    // every CU holds j workgroups that walk ceil(nchunks / (j CUs)) chunks each: the pass lasts j * that many
-                    // chunk times on the fullest CU.  10 M x 64-bit codes = 4883 chunks: 8 workgroups per CU -> 8 x 3 = 24
-                    // chunk times where 4883 / 256 = 19.1 would do; 5 per CU -> 5 x 4 = 20
-                    // (at most 6 workgroups of the body kernel fit a CU: 80 VGPRs, and nq * (8 W + 8) bytes of LDS each)
-                    int jmax = 6;
-                    const size_t lds_wg = (size_t)nq * (W * 8 + 8);
-                    if (lds_wg * jmax > (size_t)160 * 1024) jmax = (int)((size_t)160 * 1024 / lds_wg);
-                    if (jmax < 3) jmax = 3;
-                    int best_j = jmax;
-                    long long best = -1;
-                    for (int j = jmax; j >= 3; --j) {
-                        const long long cost = (long long)j * ((nchunks + (long long)j * cus - 1) / ((long long)j * cus));
-                        if (best < 0 || cost < best) best = cost, best_j = j;
-                    }
-                    G = best_j * cus;
-                }
-                if ((long long)G > nchunks) G = (int)nchunks;  // short arrays: fewer, fuller mini-lists
-            }
-            long long want = 8ll * 128ll * kk / G;  // ~8x the expected fill of a mini-list
-            if (fused && thr_rank < kk) want = 8ll * 128ll * thr_rank / G;   // (the tightened threshold admits ~ rank x step codes)
-            u32 S = 32;
-            while ((long long)S < want && S < 4096u) S <<= 1;
-            SQ_TRY(s.bcnt.reserve((size_t)G * nq * 4));
-            u32* bcnt = s.bcnt.as<u32>();
-            // non-temporal stream for arrays far beyond the MALL (read once per call)
-            const bool nt = code_bytes >= ((size_t)512 << 20);
-            for (int q0 = 0; q0 < nq; q0 += qbatch) {
-                const int nqc = nq - q0 < qbatch ? nq - q0 : qbatch;
-                SQ_TRY(s.seg.reserve((size_t)G * nqc * S * 8));
-                u64* seg = s.seg.as<u64>();
-                const size_t lds = (size_t)nqc * (W * 8 + 8);
-                const u64* qc = qs + (long long)q0 * W;
-                if (ring) {
-                    switch (W) {
-                        case 1: SQ_TRY(ring_launch<1>(h, nt, G, qc, nqc, thr + q0, seg, bcnt, S, st)); break;
-                        case 2: SQ_TRY(ring_launch<2>(h, nt, G, qc, nqc, thr + q0, seg, bcnt, S, st)); break;
-                        case 4: SQ_TRY(ring_launch<4>(h, nt, G, qc, nqc, thr + q0, seg, bcnt, S, st)); break;
-                        case 8: SQ_TRY(ring_launch<8>(h, nt, G, qc, nqc, thr + q0, seg, bcnt, S, st)); break;
-                        default: SQ_TRY(ring_launch<16>(h, nt, G, qc, nqc, thr + q0, seg, bcnt, S, st)); break;
-                    }
-                } else if (body_kernel) {
-                    if (W == 1)
-                        hipLaunchKernelGGL((hamming_body_kernel<1, 8>), dim3(G), dim3(256), lds, st, h->codes, n, h->pmul, qc, nqc,
-                                           nq <= HF_MAX_NQ ? hist : nullptr, bits, thr_rank, thr, seg, bcnt, S);
-                    else if (W == 2)
-                        hipLaunchKernelGGL((hamming_body_kernel<2, 4>), dim3(G), dim3(256), lds, st, h->codes, n, h->pmul, qc, nqc,
-                                           nq <= HF_MAX_NQ ? hist : nullptr, bits, thr_rank, thr, seg, bcnt, S);
-                    else
-                        hipLaunchKernelGGL((hamming_body_kernel<4, 2>), dim3(G), dim3(256), lds, st, h->codes, n, h->pmul, qc, nqc,
-                                           nq <= HF_MAX_NQ ? hist : nullptr, bits, thr_rank, thr, seg, bcnt, S);
-                } else if (W == 1)
-                    hipLaunchKernelGGL((hamming_stream_kernel<1, 8>), dim3(G), dim3(256), lds, st, h->codes, n, h->pmul, qc, nqc,
-                                       thr + q0, seg, bcnt, S);
-                else if (W == 2)
-                    hipLaunchKernelGGL((hamming_stream_kernel<2, 4>), dim3(G), dim3(256), lds, st, h->codes, n, h->pmul, qc, nqc,
-                                       thr + q0, seg, bcnt, S);
-                else
-                    hipLaunchKernelGGL((hamming_stream_kernel<4, 2>), dim3(G), dim3(256), lds, st, h->codes, n, h->pmul, qc, nqc,
-                                       thr + q0, seg, bcnt, S);
-                if (fused) {   // (nq <= qbatch: one pass)
-                    c.G = G;
-                    c.S = S;
-                    c.map_rows = (ring || body_kernel) ? 1 : 0;   // (ring and body kernels leave physical rows in the mini-lists)
-                    c.key_stride = key_stride;
-                    if (prof) SQ_HIP(hipEventRecord(s.ev[2], st));
-                    hipLaunchKernelGGL(hamming_pick_kernel, dim3(nq), dim3(1024), 0, st, seg, bcnt, G, nq, S, bits, k, kk, thr, (ring || body_kernel) ? 1 : 0,
-                                       h->pmul, n, h->id_base, out_dist, out_idx, status, hs_dev, nq, cap, hist);
-                } else
-                    hipLaunchKernelGGL(hamming_compact_kernel, dim3(nqc, COMPACT_SLICES), dim3(256), 0, st, seg, bcnt, G, nqc, S,
-                                       keys + (long long)q0 * key_stride, cnt + q0, cap, key_stride, ring ? 1 : 0, h->pmul, n);
-            }
-        } else {
-            scan_dispatch(h, qs, nq, thr, keys, cnt, cap, key_stride, /*mode*/ 0, st);
-        }
-        if (prof && !fused) SQ_HIP(hipEventRecord(s.ev[2], st));
-        c.stats.scan_launches = 1;
-        c.stats.bytes_scanned = n * W * 8;
-        if (!fused)
-            SQ_TRY(select_launch(keys, cnt, cap, key_stride, k, nq, okeys, st, s.sort_tmp,
-                                 HammingFinalize{cnt, cap, kk, h->id_base, out_dist, out_idx, status, hs_dev, nq}));
-    }
-    if (prof) SQ_HIP(hipEventRecord(s.ev[3], st));
+    SQ_TRY(s.status_host.reserve((size_t)nq * 8));   // [status (nq) | counts (nq)]
+    void* hs_dev = nullptr;
+    SQ_TRY(s.status_host.device_ptr(&hs_dev));       // (the parts read s.status_host.dev)
+    SQ_TRY(s.keys.reserve((size_t)nq * p.key_stride * 8));
+    SQ_TRY(p.small ? enqueue_small(h, s, p, st) : p.fused ? enqueue_fused(h, s, p, st) : enqueue_general(h, s, p, st));
+    c.stats.scan_launches = 1;
+    c.stats.bytes_scanned = h->n * h->words * 8;
+    if (p.prof) SQ_HIP(hipEventRecord(s.ev[3], st));
     if (use_event) {
         if (!s.ev_done) SQ_HIP(hipEventCreateWithFlags(&s.ev_done, hipEventDisableTiming));
         SQ_HIP(hipEventRecord(s.ev_done, st));
@@ -1020,23 +1020,56 @@ static int hamming_enqueue(HammingHandle* h, HammingSlot& s, const u64* qs, int 
     return SQ_OK;
 }
 
+// hamming_pick_kernel flagged a query whose entries at distance <= T outnumber its sort buffer (a huge tie group): the
+// general compaction + select answers the call from the same mini-lists.
+static int redo_tie_groups(HammingHandle* h, HammingSlot& s, hipStream_t st) {
+    const HammingCall& c = s.call;
+    const HammingPlan& p = c.plan;
+    SQ_TRY(launch<hamming_compact_kernel>(dim3(c.nq, COMPACT_SLICES), dim3(256), 0, st, s.seg.as<u64>(), s.bcnt.as<u32>(), p.G, c.nq, p.S,
+                                          s.keys.as<u64>(), s.cnt.as<u32>(), p.cap, p.key_stride, p.map_rows, h->pmul, h->n));
+    SQ_TRY(select_finalize(h, s, p.cap, st));
+    SQ_HIP(hipStreamSynchronize(st));
+    SQ_HIP(hipGetLastError());
+    h->stats.scan_launches++;
+    return SQ_OK;
+}
+
+// Exact path of query `q` (candidate overflow): every key of the query, radix-selected from global memory.
+static int redo_exact(HammingHandle* h, HammingSlot& s, int q, hipStream_t st) {
+    const HammingCall& c = s.call;
+    const long long n = h->n;
+    const int k = c.k;
+    u32* cnt = s.cnt.as<u32>() + q;
+    h->stats.fallback_queries++;
+    SQ_TRY(h->big_keys.reserve((size_t)n * 8));
+    u64* bk = h->big_keys.as<u64>();
+    SQ_TRY(launch<fill_u32_kernel>(dim3(1), dim3(64), 0, st, cnt, 1ll, (u32)(n > 0xffffffffll ? 0xffffffffu : n)));
+    SQ_TRY(scan_dispatch(h, c.qs + (long long)q * h->words, 1, s.thr.as<int>(), bk, cnt, (u32)n, n, /*mode*/ 1, st));
+    SQ_TRY(select_launch_t<u64>(bk, cnt, (u32)n, n, k, 1, s.out_keys.as<u64>() + (long long)q * k,
+                                HammingFinalize{cnt, (u32)n, c.plan.kk, h->id_base, c.out_dist + (long long)q * k,
+                                                c.out_idx + (long long)q * k, s.status.as<u32>() + q, nullptr, 0},
+                                st, h->fb_sort));
+    h->stats.scan_launches++;
+    // (one query at a time: big_keys is shared)
+    SQ_HIP(hipStreamSynchronize(st));
+    SQ_HIP(hipGetLastError());
+    return SQ_OK;
+}
+
 // Finish the call enqueued on slot `s`: wait for its kernels, collect the statistics and redo every query whose
 // candidate list overflowed on the exact path (synchronously, on the call's stream).  h->stats = this call's.
 static int hamming_resolve(HammingHandle* h, HammingSlot& s) {
     HammingCall& c = s.call;
     if (!c.pending) return SQ_OK;
     c.pending = false;
-    const long long n = h->n;
-    const int W = h->words;
-    const int nq = c.nq, k = c.k;
-    const int kk = (int)(k < n ? k : n);
+    const int nq = c.nq;
     hipStream_t st = c.st;
     // status words and candidate counts are in pinned host memory once the call has drained (written by the
     // finalisation): the host decides whether any query needs the exact path
-    SQ_HIP(c.use_event ? hamming_event_wait(s.ev_done) : stream_wait(st));
+    SQ_HIP(c.use_event ? event_wait(s.ev_done) : stream_wait(st));
     SQ_HIP(hipGetLastError());
     h->stats = c.stats;
-    if (c.prof) {
+    if (c.plan.prof) {
         float a = 0, b = 0;
         SQ_HIP(hipEventElapsedTime(&a, s.ev[1], s.ev[2]));
         SQ_HIP(hipEventElapsedTime(&b, s.ev[0], s.ev[3]));
@@ -1044,60 +1077,27 @@ static int hamming_resolve(HammingHandle* h, HammingSlot& s) {
         h->stats.total_ms = b;
     }
     const u32* hs = reinterpret_cast<const u32*>(s.status_host.p);
-    u32* cnt = s.cnt.as<u32>();
-    int* thr = s.thr.as<int>();
-    u64* okeys = s.out_keys.as<u64>();
-    u32* status = s.status.as<u32>();
-    if (c.fused) {
-        bool short_bet = false;
-        for (int q = 0; q < nq; ++q) short_bet = short_bet || (hs[q] & 16u) != 0;
+    if (c.plan.fused) {
+        bool short_bet = false, tie_group = false;
+        for (int q = 0; q < nq; ++q) short_bet = short_bet || (hs[q] & 16u) != 0, tie_group = tie_group || (hs[q] & 8u) != 0;
         if (short_bet) {
             // the tightened threshold admitted fewer than k codes for some query: the whole call again through the general
             // chain (safe threshold), synchronously, on the same slot and stream
             const HammingCall again = c;
             h->no_fused = true;
-            int rc = hamming_enqueue(h, s, again.qs, nq, k, again.out_dist, again.out_idx, st, false);
+            int rc = hamming_enqueue(h, s, again.qs, nq, again.k, again.out_dist, again.out_idx, st, false);
             h->no_fused = false;
             SQ_TRY(rc);
             SQ_TRY(hamming_resolve(h, s));
             h->stats.fallback_queries += nq;   // (counted: it cost a second pass)
             return SQ_OK;
         }
-        // hamming_pick_kernel flags a query whose entries at distance <= T outnumber its sort buffer (a huge tie group): the
-        // general compaction + select answers the call from the same mini-lists
-        bool redo = false;
-        for (int q = 0; q < nq; ++q) redo = redo || (hs[q] & 8u) != 0;
-        if (redo) {
-            u32* hs_dev = nullptr;
-            SQ_TRY(s.status_host.device_ptr(reinterpret_cast<void**>(&hs_dev)));
-            hipLaunchKernelGGL(hamming_compact_kernel, dim3(nq, COMPACT_SLICES), dim3(256), 0, st, s.seg.as<u64>(), s.bcnt.as<u32>(), c.G, nq,
-                               c.S, s.keys.as<u64>(), cnt, c.cap, c.key_stride, c.map_rows, h->pmul, n);
-            SQ_TRY(select_launch(s.keys.as<u64>(), cnt, c.cap, c.key_stride, k, nq, okeys, st, s.sort_tmp,
-                                 HammingFinalize{cnt, c.cap, kk, h->id_base, c.out_dist, c.out_idx, status, hs_dev, nq}));
-            SQ_HIP(hipStreamSynchronize(st));
-            SQ_HIP(hipGetLastError());
-            h->stats.scan_launches++;
-        }
+        if (tie_group) SQ_TRY(redo_tie_groups(h, s, st));
     }
     for (int q = 0; q < nq; ++q) h->stats.candidates += hs[nq + q];
-    // exact path (candidate overflow): every key of the query, radix-selected from global memory
     const bool force_fb = c.force_fb || h->opt.force_fallback != 0;
-    for (int q = 0; q < nq; ++q) {
-        if (!c.small && (hs[q] != 0 || force_fb)) {
-            h->stats.fallback_queries++;
-            SQ_TRY(h->big_keys.reserve((size_t)n * 8));
-            u64* bk = h->big_keys.as<u64>();
-            hipLaunchKernelGGL(fill_u32_kernel, dim3(1), dim3(64), 0, st, cnt + q, 1ll, (u32)(n > 0xffffffffll ? 0xffffffffu : n));
-            scan_dispatch(h, c.qs + (long long)q * W, 1, thr, bk, cnt + q, (u32)n, n, /*mode*/ 1, st);
-            SQ_TRY(select_launch(bk, cnt + q, (u32)n, n, k, 1, okeys + (long long)q * k, st, h->fb_sort,
-                                 HammingFinalize{cnt + q, (u32)n, kk, h->id_base, c.out_dist + (long long)q * k,
-                                                 c.out_idx + (long long)q * k, status + q, nullptr, 0}));
-            h->stats.scan_launches++;
-            // (one query at a time: big_keys is shared)
-            SQ_HIP(hipStreamSynchronize(st));
-            SQ_HIP(hipGetLastError());
-        }
-    }
+    for (int q = 0; q < nq; ++q)
+        if (!c.plan.small && (hs[q] != 0 || force_fb)) SQ_TRY(redo_exact(h, s, q, st));
     return SQ_OK;
 }
 
@@ -1201,8 +1201,7 @@ static int hamming_grow_keep(DevBuf& b, size_t used, size_t need) {
 static int hamming_materialise_rank(HammingHandle* h, long long rows_needed) {
     if (!h->rank.p) {
         SQ_TRY(h->rank.reserve((size_t)std::max(rows_needed, h->n) * 4));
-        hipLaunchKernelGGL(hamming_rank_init_kernel, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, 0, h->rank.as<u32>(),
-                           h->n, h->pmul);
+        SQ_TRY(launch<hamming_rank_init_kernel>(dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, nullptr, h->rank.as<u32>(), h->n, h->pmul));
         SQ_HIP(hipDeviceSynchronize());
     } else {
         SQ_TRY(hamming_grow_keep(h->rank, (size_t)h->n * 4, (size_t)rows_needed * 4));
@@ -1267,8 +1266,9 @@ extern "C" int sq_hamming_create(const uint64_t* codes, int64_t n, int words, in
         } else {
             int rc = h->owned.reserve(bytes);
             if (rc != SQ_OK) return bail(rc);
-            hipLaunchKernelGGL(hamming_permute_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, src, (long long)n,
-                               words, mul, h->owned.as<u64>());
+            rc = launch<hamming_permute_kernel>(dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, src, (long long)n, words, mul,
+                                                h->owned.as<u64>());
+            if (rc != SQ_OK) return bail(rc);
             hipError_t e = hipDeviceSynchronize();
             if (e != hipSuccess) return bail(fail(SQ_ERR_HIP, "sq_hamming_create: permutation failed: %s", hipGetErrorString(e)));
             h->codes = h->owned.as<u64>();
@@ -1363,8 +1363,8 @@ extern "C" int sq_hamming_append(sq_handle_t hid, const uint64_t* new_codes, int
     SQ_TRY(h->mut_tmp.reserve((size_t)m * 8));
     SQ_HIP(hipMemcpy(h->owned.as<u64>() + n_old * W, new_codes, (size_t)m * W * 8, hipMemcpyHostToDevice));
     SQ_HIP(hipMemcpy(h->mut_tmp.p, insert_pos, (size_t)m * 8, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(hamming_rank_insert_kernel, dim3((unsigned)((n_new + 255) / 256)), dim3(256), 0, 0, h->rank.as<u32>(),
-                       n_old, h->mut_tmp.as<long long>(), (long long)m);
+    SQ_TRY(launch<hamming_rank_insert_kernel>(dim3((unsigned)((n_new + 255) / 256)), dim3(256), 0, nullptr, h->rank.as<u32>(), n_old,
+                                              h->mut_tmp.as<long long>(), (long long)m));
     SQ_HIP(hipDeviceSynchronize());
     h->n = n_new;
     return SQ_OK;
@@ -1393,12 +1393,12 @@ extern "C" int sq_hamming_remove(sq_handle_t hid, const int64_t* ranks, int64_t 
     u32* cnt = movers + m;
     SQ_HIP(hipMemcpy(rr, ranks, (size_t)m * 8, hipMemcpyHostToDevice));
     SQ_HIP(hipMemset(cnt, 0, 8));
-    hipLaunchKernelGGL(hamming_remove_mark_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, h->rank.as<u32>(), n, rr,
-                       (long long)m, holes, movers, cnt);
-    hipLaunchKernelGGL(hamming_remove_move_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, 0, h->owned.as<u64>(),
-                       h->rank.as<u32>(), h->words, holes, movers, cnt);
-    hipLaunchKernelGGL(hamming_rank_remove_kernel, dim3((unsigned)((n - m + 255) / 256)), dim3(256), 0, 0, h->rank.as<u32>(),
-                       n - m, rr, (long long)m);
+    SQ_TRY(launch<hamming_remove_mark_kernel>(dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, h->rank.as<u32>(), n, rr, (long long)m,
+                                              holes, movers, cnt));
+    SQ_TRY(launch<hamming_remove_move_kernel>(dim3((unsigned)((m + 255) / 256)), dim3(256), 0, nullptr, h->owned.as<u64>(), h->rank.as<u32>(),
+                                              h->words, holes, movers, cnt));
+    SQ_TRY(launch<hamming_rank_remove_kernel>(dim3((unsigned)((n - m + 255) / 256)), dim3(256), 0, nullptr, h->rank.as<u32>(), n - m, rr,
+                                              (long long)m));
     SQ_HIP(hipDeviceSynchronize());
     h->n = n - m;
     return SQ_OK;

@@ -404,35 +404,19 @@ static int itq_launch_t(const ItqArgs& a0, hipStream_t st, int device) {
     a.nchunks = (a.d16 + dk - 1) / dk;
     a.vec4 = (a.d % 4 == 0) && (reinterpret_cast<uintptr_t>(a.x) % (4 * sizeof(T)) == 0);
     const size_t lds = fixed + (size_t)dk * RSTRIDE * 8;
-    static bool attr_set = false;
-    if (!attr_set) {
-        SQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&itq_hash_kernel<T, CT>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_set = true;
-    }
     const long long rows_per_block = 4ll * RT * 16;
     const long long nblocks = (a.n + rows_per_block - 1) / rows_per_block;
     long long gx = 2ll * cu_count(device);
     if (gx > nblocks) gx = nblocks;
     const int groups = (a.words * 64 + NCOL - 1) / NCOL;
-    hipLaunchKernelGGL((itq_hash_kernel<T, CT>), dim3((unsigned)gx, (unsigned)groups), dim3(256), lds, st, a);
-    SQ_HIP(hipGetLastError());
-    return SQ_OK;
+    return launch_lds<itq_hash_kernel<T, CT>>(160 * 1024, dim3((unsigned)gx, (unsigned)groups), dim3(256), lds, st, a);
 }
 
 // ---- the certified bf16x3 filter in front of the float64 kernel (sq_itq_fast.hpp)
 template <int WAVES, int NSTAGE, int KU, int CT, bool NORMED, bool BREG>
 static int itq_fast_launch_t(const ItqFastArgs& fa, size_t lds, hipStream_t st) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        SQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&itq_fast_kernel<WAVES, NSTAGE, KU, CT, NORMED, BREG>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_set = true;
-    }
-    hipLaunchKernelGGL((itq_fast_kernel<WAVES, NSTAGE, KU, CT, NORMED, BREG>), dim3((unsigned)fa.nrb), dim3(WAVES * 64), lds,
-                       st, fa);
-    SQ_HIP(hipGetLastError());
-    return SQ_OK;
+    return launch_lds<itq_fast_kernel<WAVES, NSTAGE, KU, CT, NORMED, BREG>>(160 * 1024, dim3((unsigned)fa.nrb), dim3(WAVES * 64), lds,
+                                                                            st, fa);
 }
 
 // Geometry of the filter for (d, words); stages == 0: the filter does not apply.
@@ -552,12 +536,12 @@ struct ItqCallCtx {
     long long fallback_rows = 0;              // rows hashed by the float64 kernel
 };
 
-static void itq_count_undecided(ItqCallCtx* ctx, const u64* seg, const u32* seg_cnt, long long seg_cap, long long nwaves,
-                                hipStream_t st) {
-    if (!ctx) return;
+static int itq_count_undecided(ItqCallCtx* ctx, const u64* seg, const u32* seg_cnt, long long seg_cap, long long nwaves,
+                               hipStream_t st) {
+    if (!ctx) return SQ_OK;
     ctx->filter_launches += 1;
-    if (ctx->cand_dev)
-        hipLaunchKernelGGL(itq_count_undecided_kernel, dim3((unsigned)nwaves), dim3(256), 0, st, seg, seg_cnt, seg_cap, ctx->cand_dev);
+    if (!ctx->cand_dev) return SQ_OK;
+    return launch<itq_count_undecided_kernel>(dim3((unsigned)nwaves), dim3(256), 0, st, seg, seg_cnt, seg_cap, ctx->cand_dev);
 }
 
 // float32 rows through the filter; the rows it cannot decide through the float64 kernel.
@@ -593,10 +577,11 @@ static int itq_fast_path(const ItqArgs& a, const ItqFastGeom& g, hipStream_t st,
     // by the prep kernel and added to the column's coefficient.
     const double eps_rel = ((9.5367431640625e-07 + 4.76837158203125e-07) * 1.001 + 3.0 * a.d * 5.9604644775390625e-08 +
                             9.5367431640625e-07 + (l2 ? 3.814697265625e-06 : 0.0)) * 1.001;
-    hipLaunchKernelGGL(itq_fast_prep_kernel, dim3((unsigned)pc), dim3(256), 0, st, a.mean, a.rot, a.d, a.bits, a.pad,
-                       reinterpret_cast<unsigned short*>(base + o_img), reinterpret_cast<float*>(base + o_cn),
-                       reinterpret_cast<float*>(base + o_cb), reinterpret_cast<float*>(base + o_cbe),
-                       reinterpret_cast<double*>(base + o_rt), eps_rel, reinterpret_cast<float*>(base + o_cabs));
+    int rc = launch<itq_fast_prep_kernel>(dim3((unsigned)pc), dim3(256), 0, st, a.mean, a.rot, a.d, a.bits, a.pad,
+                                          reinterpret_cast<unsigned short*>(base + o_img), reinterpret_cast<float*>(base + o_cn),
+                                          reinterpret_cast<float*>(base + o_cb), reinterpret_cast<float*>(base + o_cbe),
+                                          reinterpret_cast<double*>(base + o_rt), eps_rel, reinterpret_cast<float*>(base + o_cabs));
+    if (rc != SQ_OK) return done(rc);
     ItqFastArgs fa{};
     fa.x = reinterpret_cast<const float*>(a.x);
     fa.n = a.n;
@@ -617,12 +602,12 @@ static int itq_fast_path(const ItqArgs& a, const ItqFastGeom& g, hipStream_t st,
     fa.n_tiles = n_tiles;
     fa.nrb = nrb;
     fa.nstage = g.stages;
-    int rc = l2 ? itq_fast_dispatch<true>(fa, g, st) : itq_fast_dispatch<false>(fa, g, st);
+    rc = l2 ? itq_fast_dispatch<true>(fa, g, st) : itq_fast_dispatch<false>(fa, g, st);
     if (rc != SQ_OK) return done(rc);
     // the undecided bits, one float64 dot product each, straight from the per-wave segments
-    hipLaunchKernelGGL(itq_fix_bits_kernel, dim3((unsigned)nwaves, ITQ_FIX_PARTS), dim3(256), 0, st, a, fa.seg, fa.seg_cnt, seg_cap,
-                       reinterpret_cast<const double*>(base + o_rt));
-    itq_count_undecided(ctx, fa.seg, fa.seg_cnt, seg_cap, nwaves, st);
+    rc = launch<itq_fix_bits_kernel>(dim3((unsigned)nwaves, ITQ_FIX_PARTS), dim3(256), 0, st, a, fa.seg, fa.seg_cnt, seg_cap,
+                                     reinterpret_cast<const double*>(base + o_rt));
+    if (rc == SQ_OK) rc = itq_count_undecided(ctx, fa.seg, fa.seg_cnt, seg_cap, nwaves, st);
     return done(rc);
 }
 
@@ -674,10 +659,11 @@ static int itq_wide_path(const ItqArgs& a, hipStream_t st, int device, ItqCallCt
     const int m = a.d < 256 ? a.d : 256;
     const double eps_rel = ((9.5367431640625e-07 + 4.76837158203125e-07) * 1.001 + 1.5 * (m + 8.0) * 5.9604644775390625e-08 +
                             2.0 * a.d * 5.9604644775390625e-08 * 9.765625e-04 + 9.5367431640625e-07 + (l2 ? 3.814697265625e-06 : 0.0)) * 1.001;
-    hipLaunchKernelGGL(itq_fast_prep_kernel, dim3((unsigned)pc), dim3(256), 0, st, a.mean, a.rot, a.d, a.bits, a.pad,
-                       reinterpret_cast<unsigned short*>(base + o_img), reinterpret_cast<float*>(base + o_cn),
-                       reinterpret_cast<float*>(base + o_cb), reinterpret_cast<float*>(base + o_cbe),
-                       reinterpret_cast<double*>(base + o_rt), eps_rel, reinterpret_cast<float*>(base + o_cabs));
+    int rc = launch<itq_fast_prep_kernel>(dim3((unsigned)pc), dim3(256), 0, st, a.mean, a.rot, a.d, a.bits, a.pad,
+                                          reinterpret_cast<unsigned short*>(base + o_img), reinterpret_cast<float*>(base + o_cn),
+                                          reinterpret_cast<float*>(base + o_cb), reinterpret_cast<float*>(base + o_cbe),
+                                          reinterpret_cast<double*>(base + o_rt), eps_rel, reinterpret_cast<float*>(base + o_cabs));
+    if (rc != SQ_OK) return done(rc);
     ItqWideArgs wa{};
     wa.x = a.x;
     wa.n = a.n;
@@ -706,18 +692,14 @@ static int itq_wide_path(const ItqArgs& a, hipStream_t st, int device, ItqCallCt
         wa.stamps = stamp_buf.as<u64>();
     }   // (measurement: the ablation bits of sq_itq_wide.hpp ride on option dense_debug)
     const size_t lds = 2 * (size_t)ITQW_CHUNK_BYTES + 4 * 256 * 4 + (size_t)ITQW_WAVES * ITQW_NSTAGE * ITQF_UNIT_BYTES + ITQW_WAVES * 2048;
-    auto launch = [&](auto kern) -> int {
-        SQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        hipLaunchKernelGGL(kern, dim3((unsigned)nrb), dim3(ITQW_WAVES * 64), lds, st, wa);
-        return SQ_OK;
-    };
-    int rc;
+    const dim3 grid((unsigned)nrb), block(ITQW_WAVES * 64);
     if (a.d <= 256)
-        rc = l2 ? launch(&itq_wide_kernel<T, true, 1>) : launch(&itq_wide_kernel<T, false, 1>);
+        rc = l2 ? launch_lds<itq_wide_kernel<T, true, 1>>(160 * 1024, grid, block, lds, st, wa)
+                : launch_lds<itq_wide_kernel<T, false, 1>>(160 * 1024, grid, block, lds, st, wa);
     else
-        rc = l2 ? launch(&itq_wide_kernel<T, true, 2>) : launch(&itq_wide_kernel<T, false, 2>);
+        rc = l2 ? launch_lds<itq_wide_kernel<T, true, 2>>(160 * 1024, grid, block, lds, st, wa)
+                : launch_lds<itq_wide_kernel<T, false, 2>>(160 * 1024, grid, block, lds, st, wa);
     if (rc != SQ_OK) return done(rc);
-    SQ_HIP(hipGetLastError());
     if (wa.stamps) {
         std::vector<unsigned long long> hst((size_t)nrb * 64);
         SQ_HIP(hipMemcpy(hst.data(), wa.stamps, hst.size() * 8, hipMemcpyDeviceToHost));
@@ -732,10 +714,10 @@ static int itq_wide_path(const ItqArgs& a, hipStream_t st, int device, ItqCallCt
             fprintf(stderr, "\n");
         }
     }
-    hipLaunchKernelGGL((itq_fix_bits_wide_kernel<T>), dim3((unsigned)nwaves, ITQ_FIX_PARTS), dim3(256), 0, st, a, wa.seg, wa.seg_cnt, seg_cap,
-                       reinterpret_cast<const double*>(base + o_rt));
-    itq_count_undecided(ctx, wa.seg, wa.seg_cnt, seg_cap, nwaves, st);
-    return done(SQ_OK);
+    rc = launch<itq_fix_bits_wide_kernel<T>>(dim3((unsigned)nwaves, ITQ_FIX_PARTS), dim3(256), 0, st, a, wa.seg, wa.seg_cnt, seg_cap,
+                                             reinterpret_cast<const double*>(base + o_rt));
+    if (rc == SQ_OK) rc = itq_count_undecided(ctx, wa.seg, wa.seg_cnt, seg_cap, nwaves, st);
+    return done(rc);
 }
 
 }  // namespace sq
@@ -753,11 +735,7 @@ static bool itq_xwide_applies(const ItqArgs& a) {
 template <class T, bool NORMED, int CT>
 static int itq_xwide_launch_t(const ItqXwideArgs& xa, int nrb, hipStream_t st) {
     constexpr size_t lds = 2 * (size_t)CT * 8192 + 3 * (size_t)CT * 32 * 4;
-    static std::atomic<unsigned long long> attr_done{0};
-    SQ_TRY(ensure_dyn_lds(reinterpret_cast<const void*>(&itq_xwide_kernel<T, NORMED, CT>), 160 * 1024, attr_done));
-    hipLaunchKernelGGL((itq_xwide_kernel<T, NORMED, CT>), dim3((unsigned)nrb), dim3(ITQX_WAVES * 64), lds, st, xa);
-    SQ_HIP(hipGetLastError());
-    return SQ_OK;
+    return launch_lds<itq_xwide_kernel<T, NORMED, CT>>(160 * 1024, dim3((unsigned)nrb), dim3(ITQX_WAVES * 64), lds, st, xa);
 }
 
 template <class T>
@@ -805,6 +783,7 @@ static int itq_xwide_path(const ItqArgs& a, hipStream_t st, int device, ItqCallC
         (void)hipFreeAsync(cbase, st);
         return rc;
     };
+    int rc;
     if (!cached) {
         // relative error of x . R_b per unit |x||R_b| (sq_itq_xwide.hpp): the split, the dropped x_lo R_lo, the float32
         // accumulation flushed per 64-k slab (192 products each, then ceil(d / 64) additions), the float32 scale /
@@ -815,14 +794,15 @@ static int itq_xwide_path(const ItqArgs& a, hipStream_t st, int device, ItqCallC
                                 (1.5 * (3.0 * ITQX_SLAB_K + 8.0) + 1.5 * (nslab + 1.0)) * u24 * (1.0 + 1.0 / 512.0) +
                                 9.5367431640625e-07 + (l2 ? 3.814697265625e-06 : 0.0)) * 1.001;
         SQ_HIP(hipMemsetAsync(cbase + o_img, 0, img_bytes, st));   // (k beyond d: finite zeros under zero row fragments)
-        hipLaunchKernelGGL(itq_fast_prep_kernel, dim3((unsigned)pc), dim3(256), 0, st, a.mean, a.rot, a.d, a.bits, a.pad,
-                           reinterpret_cast<unsigned short*>(cbase + o_img), reinterpret_cast<float*>(mbase + o_cn),
-                           reinterpret_cast<float*>(mbase + o_cb), reinterpret_cast<float*>(mbase + o_cbe),
-                           reinterpret_cast<double*>(mbase + o_rt), eps_rel, reinterpret_cast<float*>(mbase + o_cabs));
+        rc = launch<itq_fast_prep_kernel>(dim3((unsigned)pc), dim3(256), 0, st, a.mean, a.rot, a.d, a.bits, a.pad,
+                                          reinterpret_cast<unsigned short*>(cbase + o_img), reinterpret_cast<float*>(mbase + o_cn),
+                                          reinterpret_cast<float*>(mbase + o_cb), reinterpret_cast<float*>(mbase + o_cbe),
+                                          reinterpret_cast<double*>(mbase + o_rt), eps_rel, reinterpret_cast<float*>(mbase + o_cabs));
+        if (rc != SQ_OK) return done(rc);
         const long long chunks = (long long)(img_bytes / 16);
-        hipLaunchKernelGGL(itq_xwide_relayout_kernel, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, st,
-                           reinterpret_cast<const uint4*>(cbase + o_img), reinterpret_cast<uint4*>(mbase + o_ximg), dp, ct, chunks);
-        SQ_HIP(hipGetLastError());
+        rc = launch<itq_xwide_relayout_kernel>(dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, st,
+                                               reinterpret_cast<const uint4*>(cbase + o_img), reinterpret_cast<uint4*>(mbase + o_ximg), dp, ct, chunks);
+        if (rc != SQ_OK) return done(rc);
         if (keep) *ctx->prep_valid = true;
     }
     ItqXwideArgs xa{};
@@ -843,7 +823,6 @@ static int itq_xwide_path(const ItqArgs& a, hipStream_t st, int device, ItqCallC
     xa.seg_cap = seg_cap;
     xa.n_tiles = n_tiles;
     xa.nslab = (a.d + ITQX_SLAB_K - 1) / ITQX_SLAB_K;
-    int rc;
 #define SQ_ITQX_CASE(CTv)                                                                              \
     case CTv:                                                                                          \
         rc = l2 ? itq_xwide_launch_t<T, true, CTv>(xa, nrb, st) : itq_xwide_launch_t<T, false, CTv>(xa, nrb, st); \
@@ -857,11 +836,10 @@ static int itq_xwide_path(const ItqArgs& a, hipStream_t st, int device, ItqCallC
     }
 #undef SQ_ITQX_CASE
     if (rc != SQ_OK) return done(rc);
-    hipLaunchKernelGGL((itq_fix_bits_xwide_kernel<T>), dim3((unsigned)nwaves, ITQ_FIX_PARTS), dim3(256), 0, st, a, xa.seg, xa.seg_cnt,
-                       seg_cap, reinterpret_cast<const double*>(mbase + o_rt));
-    SQ_HIP(hipGetLastError());
-    itq_count_undecided(ctx, xa.seg, xa.seg_cnt, seg_cap, nwaves, st);
-    return done(SQ_OK);
+    rc = launch<itq_fix_bits_xwide_kernel<T>>(dim3((unsigned)nwaves, ITQ_FIX_PARTS), dim3(256), 0, st, a, xa.seg, xa.seg_cnt, seg_cap,
+                                              reinterpret_cast<const double*>(mbase + o_rt));
+    if (rc == SQ_OK) rc = itq_count_undecided(ctx, xa.seg, xa.seg_cnt, seg_cap, nwaves, st);
+    return done(rc);
 }
 
 template <class T>
@@ -877,17 +855,15 @@ static int itq_launch(const ItqArgs& a0, hipStream_t st, int device, ItqCallCtx*
     if (itq_xwide_applies<T>(a)) return itq_xwide_path<T>(a, st, device, ctx);
     if (ctx) ctx->fallback_rows += a.n;
     void* nrm = nullptr;
+    int rc = SQ_OK;
     if (a.norm != SQ_NORM_NONE) {  // stream-ordered scratch: [n] norms in x's dtype
         SQ_HIP(scratch_alloc(&nrm, (size_t)a.n * sizeof(T), st, device));
         long long gx = std::min<long long>((a.n + 31) / 32, 16ll * cu_count(device));
-        hipLaunchKernelGGL((itq_norms_kernel<T>), dim3((unsigned)gx), dim3(256), 0, st, reinterpret_cast<const T*>(a.x),
-                           a.n, a.d, reinterpret_cast<T*>(nrm), (const u32*)nullptr, (const u32*)nullptr, a.norm);
+        rc = launch<itq_norms_kernel<T>>(dim3((unsigned)gx), dim3(256), 0, st, reinterpret_cast<const T*>(a.x), a.n, a.d,
+                                         reinterpret_cast<T*>(nrm), (const u32*)nullptr, (const u32*)nullptr, a.norm);
         a.nrm = nrm;
     }
-    int rc;
-    if (a.words == 1) rc = itq_launch_t<T, 4>(a, st, device);
-    else if (a.words == 2) rc = itq_launch_t<T, 8>(a, st, device);
-    else rc = itq_launch_t<T, 16>(a, st, device);
+    if (rc == SQ_OK) rc = a.words == 1 ? itq_launch_t<T, 4>(a, st, device) : a.words == 2 ? itq_launch_t<T, 8>(a, st, device) : itq_launch_t<T, 16>(a, st, device);
     if (nrm) (void)hipFreeAsync(nrm, st);
     return rc;
 }

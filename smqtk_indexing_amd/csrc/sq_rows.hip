@@ -212,36 +212,18 @@ __global__ void lsh_finalize_kernel(const K* __restrict__ sorted, const u32* __r
     }
 }
 
-template <class K>
-static int rows_select(const K* keys, const u32* cnt, u32 cap, long long stride, int k, int nq, K* out, hipStream_t st,
-                       DevBuf& sort_scratch) {
-    static bool attr_set = false;
-    const int lds_keys = sizeof(K) == 8 ? 16384 : 7168;
-    if (k > lds_keys)  // lsh.py:513-518 slices whatever n is asked: the any-k sorted select (sq_select.hpp)
-        return sort_select_large<K, SelectNoPost>(keys, cnt, cap, stride, k, nq, out, sort_scratch, SelectNoPost(), st);
-    const size_t lds = (size_t)(lds_keys + SELECT_SORT_MAX) * sizeof(K);
-    if (!attr_set) {
-        SQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&select_topk_kernel<K>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_set = true;
-    }
-    hipLaunchKernelGGL((select_topk_kernel<K>), dim3(nq), dim3(1024), lds, st, keys, cnt, cap, stride, k, lds_keys, out);
-    return SQ_OK;
-}
-
 template <class T, class K>
 static int rows_rerank_t(RowsHandle* h, int nq, int metric, long long maxc, int k, hipStream_t st) {
     SQ_TRY(h->keys.reserve((size_t)nq * maxc * sizeof(K)));
     SQ_TRY(h->out_keys.reserve((size_t)nq * k * sizeof(K)));
     const unsigned gx = (unsigned)((maxc + 31) / 32);
-    hipLaunchKernelGGL((rows_rerank_keys_kernel<T, K>), dim3(gx, nq), dim3(256), 0, st,
-                       reinterpret_cast<const T*>(h->rows), h->n, h->d, h->q_dev.as<T>(), metric,
-                       h->cand_dev.as<long long>(), h->off_dev.as<long long>(), maxc, h->keys.as<K>(), h->cnt_dev.as<u32>());
-    SQ_TRY(rows_select<K>(h->keys.as<K>(), h->cnt_dev.as<u32>(), (u32)maxc, maxc, k, nq, h->out_keys.as<K>(), st, h->sort_tmp));
-    hipLaunchKernelGGL((rows_finalize_kernel<K>), dim3(nq), dim3(256), 0, st, h->out_keys.as<K>(), h->cnt_dev.as<u32>(), k,
-                       h->out_dist.p, h->out_pos.as<long long>());
-    SQ_HIP(hipGetLastError());
-    return SQ_OK;
+    SQ_TRY(launch<rows_rerank_keys_kernel<T, K>>(dim3(gx, nq), dim3(256), 0, st, reinterpret_cast<const T*>(h->rows), h->n, h->d,
+                                                 h->q_dev.as<T>(), metric, h->cand_dev.as<long long>(), h->off_dev.as<long long>(), maxc,
+                                                 h->keys.as<K>(), h->cnt_dev.as<u32>()));
+    SQ_TRY(select_launch_t<K>(h->keys.as<K>(), h->cnt_dev.as<u32>(), (u32)maxc, maxc, k, nq, h->out_keys.as<K>(), SelectNoPost(), st,
+                              h->sort_tmp));
+    return launch<rows_finalize_kernel<K>>(dim3(nq), dim3(256), 0, st, h->out_keys.as<K>(), h->cnt_dev.as<u32>(), k, h->out_dist.p,
+                                           h->out_pos.as<long long>());
 }
 
 }  // namespace sq
@@ -392,14 +374,13 @@ static int lsh_rerank_t(RowsHandle* h, int nq, int metric, long long maxc, int k
     SQ_TRY(h->keys.reserve((size_t)nq * maxc * sizeof(K)));
     SQ_TRY(h->out_keys.reserve((size_t)nq * k_sel * sizeof(K)));
     const unsigned gx = (unsigned)((maxc + 31) / 32);
-    hipLaunchKernelGGL((rows_rerank_keys_kernel<T, K>), dim3(gx, nq), dim3(256), 0, st,
-                       reinterpret_cast<const T*>(h->rows), h->n, h->d, h->q_dev.as<T>(), metric,
-                       h->cand_dev.as<long long>(), h->off_dev.as<long long>(), maxc, h->keys.as<K>(), h->cnt_dev.as<u32>());
-    SQ_TRY(rows_select<K>(h->keys.as<K>(), h->cnt_dev.as<u32>(), (u32)maxc, maxc, k_sel, nq, h->out_keys.as<K>(), st, h->sort_tmp));
-    hipLaunchKernelGGL((lsh_finalize_kernel<K>), dim3(nq), dim3(256), 0, st, h->out_keys.as<K>(), h->cnt_dev.as<u32>(), k_sel,
-                       k_out, h->cand_dev.as<long long>(), h->off_dev.as<long long>(), out_dist_dev, out_rows_dev);
-    SQ_HIP(hipGetLastError());
-    return SQ_OK;
+    SQ_TRY(launch<rows_rerank_keys_kernel<T, K>>(dim3(gx, nq), dim3(256), 0, st, reinterpret_cast<const T*>(h->rows), h->n, h->d,
+                                                 h->q_dev.as<T>(), metric, h->cand_dev.as<long long>(), h->off_dev.as<long long>(), maxc,
+                                                 h->keys.as<K>(), h->cnt_dev.as<u32>()));
+    SQ_TRY(select_launch_t<K>(h->keys.as<K>(), h->cnt_dev.as<u32>(), (u32)maxc, maxc, k_sel, nq, h->out_keys.as<K>(), SelectNoPost(), st,
+                              h->sort_tmp));
+    return launch<lsh_finalize_kernel<K>>(dim3(nq), dim3(256), 0, st, h->out_keys.as<K>(), h->cnt_dev.as<u32>(), k_sel, k_out,
+                                          h->cand_dev.as<long long>(), h->off_dev.as<long long>(), out_dist_dev, out_rows_dev);
 }
 }  // namespace sq
 
@@ -455,9 +436,8 @@ extern "C" int sq_lsh_query(sq_handle_t rows_h, sq_handle_t hamming_h, sq_handle
     long long* th = reinterpret_cast<long long*>(h->totals_host.p);
     long long* th_dev = nullptr;
     SQ_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&th_dev), th, 0));
-    hipLaunchKernelGGL(lsh_bucket_sizes_kernel, dim3(nq), dim3(256), 0, st, h->ham_idx.as<long long>(), m, h->csr_off, h->n_codes,
-                       pre, tot);
-    hipLaunchKernelGGL(lsh_offsets_kernel, dim3(1), dim3(1), 0, st, tot, nq, h->off_dev.as<long long>(), th_dev);
+    SQ_TRY(launch<lsh_bucket_sizes_kernel>(dim3(nq), dim3(256), 0, st, h->ham_idx.as<long long>(), m, h->csr_off, h->n_codes, pre, tot));
+    SQ_TRY(launch<lsh_offsets_kernel>(dim3(1), dim3(1), 0, st, tot, nq, h->off_dev.as<long long>(), th_dev));
     SQ_HIP(stream_wait(st));
     const long long total = th[0], maxc = th[1];
     if (maxc >= (1ll << 32)) return fail(SQ_ERR_UNSUPPORTED, "sq_lsh_query: more than 2^32-1 candidates for one query");
@@ -471,8 +451,8 @@ extern "C" int sq_lsh_query(sq_handle_t rows_h, sq_handle_t hamming_h, sq_handle
     }
     SQ_TRY(h->cand_dev.reserve((size_t)(total > 0 ? total : 1) * 8));
     const long long mc = maxc > 0 ? maxc : 1;
-    hipLaunchKernelGGL(lsh_fill_candidates_kernel, dim3((unsigned)((m + 31) / 32), nq), dim3(256), 0, st, h->ham_idx.as<long long>(),
-                       m, h->csr_off, h->csr_rows, h->n_codes, pre, h->off_dev.as<long long>(), h->cand_dev.as<long long>());
+    SQ_TRY(launch<lsh_fill_candidates_kernel>(dim3((unsigned)((m + 31) / 32), nq), dim3(256), 0, st, h->ham_idx.as<long long>(), m,
+                                              h->csr_off, h->csr_rows, h->n_codes, pre, h->off_dev.as<long long>(), h->cand_dev.as<long long>()));
     const int k_sel = (int)std::min<long long>(k_out, mc);
     int rc;
     if (k64)

@@ -351,17 +351,42 @@ static int sort_select_large(const K* keys, const u32* cnt, u32 cap, long long s
     SQ_TRY(scratch.reserve((size_t)2 * nq * P * sizeof(K)));
     K* a = scratch.as<K>();
     K* b = a + (size_t)nq * P;
-    hipLaunchKernelGGL((sortl_chunk_kernel<K>), dim3((unsigned)(P / CH), (unsigned)nq), dim3(1024), 0, st, keys, cnt, cap, stride,
-                       a, P);
+    SQ_TRY(launch<sortl_chunk_kernel<K>>(dim3((unsigned)(P / CH), (unsigned)nq), dim3(1024), 0, st, keys, cnt, cap, stride, a, P));
     for (long long run = CH; run < P; run <<= 1) {
-        hipLaunchKernelGGL((sortl_merge_kernel<K>), dim3((unsigned)((P + 255) / 256), (unsigned)nq), dim3(256), 0, st, a, b, P, run);
+        SQ_TRY(launch<sortl_merge_kernel<K>>(dim3((unsigned)((P + 255) / 256), (unsigned)nq), dim3(256), 0, st, a, b, P, run));
         K* t = a;
         a = b;
         b = t;
     }
-    hipLaunchKernelGGL((sortl_finish_kernel<K, Post>), dim3((unsigned)nq), dim3(1024), 0, st, a, P, k, out, post);
-    SQ_HIP(hipGetLastError());
-    return SQ_OK;
+    return launch<sortl_finish_kernel<K, Post>>(dim3((unsigned)nq), dim3(1024), 0, st, a, P, k, out, post);
+}
+
+// ------------------------------------------------------------ select launcher
+static constexpr int kSelectLdsKeys64 = 16384;   // 128 KiB of LDS for the candidate keys
+static constexpr int kSelectLdsKeys128 = 7168;
+
+// select + the caller's post-op (keys -> distances / ids, certification, status) in one launch
+// `expect`: candidates per query the caller expects (0 = unknown).  The kernel keeps up to lds_keys keys of a query in
+// LDS and reads longer lists from global memory; sizing the LDS for the expected list instead of the largest possible
+// lets two workgroups share a CU (36-40 registers per thread: LDS is what limits them) -- with one workgroup per query
+// a 1024-query batch is four rounds of workgroups otherwise.
+template <class K, class Post = SelectNoPost>
+static int select_launch_t(const K* keys, const u32* cnt, u32 cap, long long stride, int k, int nq, K* out,
+                           const Post& post, hipStream_t st, DevBuf& sort_scratch, long long expect = 0, int cnt_shift = 0) {
+    const int lds_max = sizeof(K) == 8 ? kSelectLdsKeys64 : kSelectLdsKeys128;
+    // beyond the one-workgroup select: full sort ("any-k sorted select" above; neither linear.py:235-238 nor
+    // lsh.py:513-518 limits k); the scratch belongs to the call slot (asynchronous calls in flight, or two handles on
+    // two threads, must not share it)
+    if (k > lds_max) return sort_select_large<K, Post>(keys, cnt, cap, stride, k, nq, out, sort_scratch, post, st);
+    int lds_keys = lds_max;
+    if (expect > 0 && nq > 256) {  // (fewer queries than CUs: one round of workgroups either way)
+        const int half = (int)((80 * 1024) / sizeof(K)) - SELECT_SORT_MAX;  // two workgroups in 160 KB
+        if (half >= k && 2 * expect <= half) lds_keys = half;
+    }
+    const size_t lds_full = (size_t)(lds_max + SELECT_SORT_MAX) * sizeof(K);
+    const size_t lds = (size_t)(lds_keys + SELECT_SORT_MAX) * sizeof(K);
+    return launch_lds<select_topk_kernel<K, Post>>((int)lds_full, dim3(nq), dim3(1024), lds, st, keys, cnt, cap, stride, k, lds_keys,
+                                                    out, post, cnt_shift);
 }
 
 // ------------------------------------------------------------ block helpers

@@ -198,6 +198,64 @@ def test_hamming_async_calls_equal_blocking_calls(depth, wait, ring):
     np.testing.assert_array_equal(oi[1].cpu().numpy(), want[1][1])
 
 
+# ------------------------------------------------------------------------- dynamic-LDS attributes per device
+def test_second_device_gets_its_lds_attributes():
+    """The dynamic-LDS limit of a kernel belongs to one device's copy of it: the kernels that launch with more than
+    64 KiB (Hamming ring and select, the LSH re-rank select, the bf16 ITQ filter) must get it on every device a
+    process uses, not only on the first.  The same calls on device 0, then on device 1 (a handle lives on the device
+    that is current when it is created): both against the oracle, and device 1 equal to device 0."""
+    if torch.cuda.device_count() < 2:
+        pytest.skip("needs two visible GPUs")
+    rng = np.random.default_rng(77)
+    codes = _codes(rng, 20_011, 8)
+    hq = rng.integers(0, 2 ** 64, size=(4, 8), dtype=np.uint64)
+    hq[0] = codes[5000]
+    rows = rng.standard_normal((3000, 96)).astype(np.float32)
+    rq = rng.standard_normal((2, 96)).astype(np.float32)
+    cands = [rng.permutation(3000)[:400], rng.permutation(3000)[:250]]
+    off = np.array([0, 400, 650], dtype=np.int64)
+    flat = np.concatenate(cands).astype(np.int64)
+    x = rng.standard_normal((4096, 128)).astype(np.float32)
+    mean = x.mean(axis=0).astype(np.float64)
+    rot = np.ascontiguousarray(np.linalg.qr(rng.standard_normal((128, 128)))[0][:, :64])
+
+    def run(device):
+        with torch.cuda.device(device):
+            idx = _lib.HammingIndex(codes)
+            idx.set_option("hamming_ring", 1)
+            ring = idx.search(hq, 50)
+            idx.set_option("hamming_fused", 0)           # select_topk_kernel answers
+            general = idx.search(hq, 50)
+            idx.close()
+            m = _lib.RowMatrix(rows)
+            rerank = m.rerank(rq, _lib.SQ_METRIC_L2, flat, off, 50)
+            m.close()
+            model = _lib.ItqModel(mean, rot)
+            hashed = model.hash(x)
+            model.close()
+        return ring, general, rerank, hashed
+
+    got = [run(0), run(1)]
+    z = O.itq_z(x, mean, rot)
+    ref_codes = O.pack_bits_msb(z >= 0)
+    for ring, general, (rdist, rpos), hashed in got:
+        for qi, q in enumerate(hq):
+            rd, ri = O.hamming_topk(codes, q, 50)
+            for d, i in (ring, general):
+                np.testing.assert_array_equal(d[qi], rd)
+                np.testing.assert_array_equal(i[qi], ri)
+        for qi, c in enumerate(cands):
+            full = O.dense_distances(rows[c], rq[qi], "euclidean")
+            order = np.argsort(full, kind="stable")[:50]
+            np.testing.assert_array_equal(rpos[qi], order)
+            np.testing.assert_array_equal(rdist[qi], full[order])
+        bad = (hashed != ref_codes).any(axis=1)          # (a bit may differ only where z is a rounding error from 0)
+        assert bad.sum() == 0 or np.abs(z[bad]).min(axis=1).max() < 1e-10
+    for a, b in zip(got[0], got[1]):
+        for u, v in zip(a, b) if isinstance(a, tuple) else ((a, b),):
+            np.testing.assert_array_equal(u, v)
+
+
 # ------------------------------------------------------------------------------------------ per-handle options
 def test_options_are_per_handle_two_threads():
     """sq_handle_set_option: two dense indexes searched from two threads with different pipeline depths, candidate
