@@ -211,7 +211,8 @@ int sq_hamming_destroy(sq_handle_t h);
  * library pads the rows).
  * Any d: rows of up to 8192 padded dimensions are filtered from a bfloat16 copy (up to 512: the ring kernels, and an
  * int8 copy for small batches; beyond: dense_wide_scan_kernel, the widths of the reference's own examples --
- * 2048- / 4096-dimensional descriptors, docs/examples/caffe_build_index.rst:35); wider rows take the exact path. */
+ * 2048- / 4096-dimensional descriptors, docs/examples/caffe_build_index.rst:35 -- and, with option "dense_int8_wide",
+ * an int8 copy for small batches there too); wider rows take the exact path. */
 int sq_dense_create(const float* db, int64_t n, int d, int metric, int mem,
                     int64_t id_base, sq_handle_t* out);
 /* The same with options of THIS index given at create, as name / value arrays: they become the handle's overrides
@@ -290,6 +291,13 @@ int sq_dense_search(sq_handle_t h, const float* queries, int nq, int k,
  * index through sq_dense_create_opts): no copy; 0 on a handle: the copy is not used; -1: after three calls in a row whose
  * candidate lists overflowed the filter is SUSPENDED (bfloat16 answers; the copy stays and follows appends) until the
  * index has doubled and chooses its clamp again, or until a call with 1 on the handle re-arms it; 1: never suspended.
+ * Option "dense_int8_wide" (0 by default): with 1 when the index is created (process-wide, or for one index through
+ * sq_dense_create_opts), L2 and cosine indexes of 513 to 8192 dimensions and at least 65536 rows keep the int8 copy too
+ * (rows padded to whole 128 bytes, + 4 bytes of row term) and calls of up to 32 queries filter on it (dense8_wide_scan_kernel)
+ * instead of on the bfloat16 copy; larger batches, and queries it cannot certify, go on as before -- the same bits either
+ * way.  The option is read when the copy is built (create, compact, an append to an index that has none yet); the copy
+ * follows appends and removals, "dense_int8" = 0 on the handle turns the stage off and its suspension works as above.
+ * sq_dense_info reports such a copy by the bytes it occupies.  0: nothing is built and every call is the bfloat16 chain's.
  * Option "dense_int8_batch" (64 by default): the largest batch the int8 filter takes (128-byte rows; 32 = one query tile only).
  * Option "dense_graph" (1 by default): asynchronous int8 calls of one shape replay a captured graph (one launch per call).
  * Option "dense_mid_tier" (1 by default): queries the first filter cannot certify take a second, tighter filter over the

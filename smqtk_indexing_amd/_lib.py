@@ -206,8 +206,21 @@ def device_name(device: int = 0) -> Tuple[str, int, int]:
     return buf.value.decode(), int(mem.value), int(cus.value)
 
 
+# Options sq_dense_create reads when it decides which copies an index keeps ("dense_int8" = 0: no int8 copy at all;
+# "dense_int8_wide" = 1: rows of 513 to 8192 dimensions keep one too).  ``DenseIndex(options=...)`` makes them the index's own.
+DENSE_CREATE_OPTIONS = ("dense_int8", "dense_int8_wide", "dense_no_center")
+
+_process_options: dict = {}   # what set_option was last given, by name (the library has no getter)
+
+
 def set_option(name: str, value: int) -> None:
     _check(load().sq_set_option(name.encode(), int(value)), f"sq_set_option({name})")
+    _process_options[name] = int(value)
+
+
+def process_option(name: str, default: Optional[int] = None) -> Optional[int]:
+    """The process-wide value :func:`set_option` last set for ``name`` (``default`` if it never did)."""
+    return _process_options.get(name, default)
 
 
 def get_stats(handle: int) -> dict:

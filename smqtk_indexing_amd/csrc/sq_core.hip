@@ -101,6 +101,7 @@ int Options::*option_member(const char* name) {
         {"dense_nt_keep_mb", &Options::dense_nt_keep_mb},
         {"dense_mid_tier", &Options::dense_mid_tier},
         {"dense_int8", &Options::dense_int8},
+        {"dense_int8_wide", &Options::dense_int8_wide},
         {"dense_graph", &Options::dense_graph},
         {"dense_fused", &Options::dense_fused},
         {"dense_tighten", &Options::dense_tighten},

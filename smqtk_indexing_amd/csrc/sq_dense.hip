@@ -33,6 +33,7 @@
 #include "sq_dense_mid.hpp"
 #include "sq_dense_i8.hpp"
 #include "sq_dense_wide.hpp"
+#include "sq_dense_i8_wide.hpp"
 #include "sq_dense_tighten.hpp"
 #include "sq_dense_remove.hpp"
 
@@ -104,8 +105,8 @@ struct DenseHandle : HandleBase {
     DevBuf scan8, nrow8;
     bool use8 = false;          // the int8 copy exists (and follows appends)
     bool suspended8 = false;    // ... but automatic mode (dense_int8 = -1) leaves it alone: its lists overflowed three calls in a row.  dense_int8 = 1 re-arms it, a rebuild (the index doubled) too
-    int row8 = 0;               // bytes per row of the copy: 128, 256 or 512
-    long long n_pad64 = 0;      // rows a pass covers (what sq_stats_t.bytes_scanned prices)
+    int row8 = 0;               // bytes per row of the copy: 128, 256 or 512; rows beyond 512 dimensions (sq_dense_i8_wide.hpp): a multiple of 128
+    long long n_pad64 = 0;      // rows a pass covers (what sq_stats_t.bytes_scanned prices): whole 64-row units, wide rows whole 32-row tiles
     long long n_alloc8 = 0;     // rows the copy is allocated and padded for: a multiple of 128 (the largest ring unit)
     double dx8 = 0.0, rmax8 = 0.0, xmax8 = 0.0;
     long long flagged8 = 0;
@@ -387,6 +388,142 @@ static bool dense_mid_shape_ok(const DenseHandle* h) {
            (cosine ? h->cos_nx.p != nullptr : h->norms.p != nullptr);
 }
 
+// The int8 first stage of a call of up to 32 queries over rows of 513 to 8192 dimensions (sq_dense_i8_wide.hpp): query
+// prep, sample pass, threshold, full pass, second-level threshold, re-rank, select -- the wide bfloat16 chain with the
+// int8 kernels in the places of its prep and its two passes, and the int8 certificate (Dense8ThrPost, DenseFinalize*::lin)
+// in the place of the bfloat16 bound.
+static int dense8_wide_enqueue(DenseHandle* h, DenseSlot& s, const float* q, int nq, int k, int kk, void* out_dist, long long* out_idx,
+                               hipStream_t st, bool prof, u32 cap, u32* hs_dev, u32* hs_raw_dev) {
+    const long long n = h->n;
+    const int d = h->d, row8 = h->row8, ku = i8w_units(row8), qw = ku * I8W_UNIT;
+    const bool cosine = h->metric == SQ_METRIC_COSINE;
+    const size_t key_bytes = cosine ? sizeof(K128) : sizeof(u64);
+    const long long key_stride = (long long)cap;
+    const long long n_tiles = (n + TILE_ROWS - 1) / TILE_ROWS;
+    // every stride-th tile is sampled: the bfloat16 chain's balance of sample pass against re-rank (dense_enqueue)
+    long long stride = h->opt.sample_stride;
+    if (stride <= 0) {
+        stride = (long long)(20.0 * sqrt((double)n / 1e7 * 100.0 / (double)kk) / (cosine ? 1.9 : 1.0) + 0.5);
+        if (stride > 24) stride = 24;
+        if (stride < 2) stride = 2;
+        if (stride > (long long)cap / (8ll * kk)) stride = (long long)cap / (8ll * kk);
+    }
+    if (stride > 64) stride = 64;
+    if (stride < 1) stride = 1;
+    while (stride > 1 && (n_tiles / stride) * 2 < 8ll * kk) stride >>= 1;
+    const long long ns_tiles = (n_tiles + stride - 1) / stride;
+    const long long ns = ns_tiles * 2;   // one sample (a 16-row group minimum) per lane half and tile
+    const int cus = cu_count(h->device);
+    int nrb = h->opt.dense_blocks > 0 ? h->opt.dense_blocks : 2 * cus;   // (32 KB of LDS: two eight-wave workgroups per CU)
+    nrb = (nrb + 7) / 8 * 8;
+    const long long n_waves = (long long)nrb * WIDE_WAVES;
+    const u32 wave_cap = 2048;
+    const int ldq = (d + 3) / 4 * 4;
+    const bool tighten = h->opt.dense_tighten != 0;
+    SQ_TRY(s.sample.reserve((size_t)TILE_ROWS * ns * 4));
+    SQ_TRY(s.keys.reserve((size_t)nq * key_stride * key_bytes));
+    SQ_TRY(s.q8.reserve((size_t)2 * TILE_ROWS * qw));
+    SQ_TRY(s.par8.reserve((size_t)TILE_ROWS * 8));
+    SQ_TRY(s.wave_out.reserve((size_t)n_waves * wave_cap * 8));
+    SQ_TRY(s.wave_cnt.reserve((size_t)n_waves * 8));
+    SQ_TRY(s.q_al.reserve((size_t)nq * ldq * 4));
+    u32 *tg_hist = nullptr, *tg_thr2k = nullptr;
+    float *tg_traw = nullptr, *tg_thr2 = nullptr;
+    if (tighten) {
+        SQ_TRY(s.wave_score.reserve((size_t)n_waves * wave_cap * 4));
+        SQ_TRY(s.tg.reserve((size_t)TG_CAP_Q * (TG_BINS + 3) * 4));
+        if (s.tg_zeroed != s.tg.p) {   // a new allocation: wiped once, dense_tighten_thr_kernel leaves the histogram clean
+            SQ_HIP(hipMemsetAsync(s.tg.p, 0, s.tg.cap, st));
+            s.tg_zeroed = s.tg.p;
+        }
+        tg_hist = s.tg.as<u32>();
+        tg_traw = reinterpret_cast<float*>(tg_hist + (size_t)TG_CAP_Q * TG_BINS);
+        tg_thr2 = tg_traw + TG_CAP_Q;
+        tg_thr2k = reinterpret_cast<u32*>(tg_thr2 + TG_CAP_Q);
+    }
+    u32* cnt = s.cnt.as<u32>();
+    float* thr = s.thr.as<float>();
+    double* qn2 = s.qn2.as<double>();
+    u32* oflag = s.oflag.as<u32>();
+    const float* centerp = (!cosine && h->center.p) ? h->center.as<float>() : nullptr;
+    hipLaunchKernelGGL(dense8_wide_prep_queries_kernel, dim3(TILE_ROWS), dim3(256), 0, st, q, nq, d, centerp, h->dx8, h->rmax8, h->xmax8,
+                       s.q8.as<signed char>(), qw, s.par8.as<float2>(), qn2, thr, cnt, oflag, s.q_al.as<float>(), ldq, cosine ? 1 : 0);
+    Dense8WideArgs a{};
+    a.scan8 = h->scan8.as<signed char>();
+    a.nrow = h->nrow8.as<float>();
+    a.row_bytes = row8;
+    a.ku = ku;
+    a.n = n;
+    a.n_tiles = n_tiles;
+    a.qs8 = s.q8.as<signed char>();
+    a.par = s.par8.as<float2>();
+    a.thr = thr;
+    a.wave_out = s.wave_out.as<uint2>();
+    a.wave_cnt = s.wave_cnt.as<u32>();
+    a.wave_cap = wave_cap;
+    a.sample_out = s.sample.as<float>();
+    a.ns = ns;
+    // sample pass
+    a.tile_step = stride;
+    a.n_sel = ns_tiles;
+    a.nrb = nrb;
+    if (ns_tiles < (long long)nrb * WIDE_WAVES) a.nrb = (int)(((ns_tiles + WIDE_WAVES - 1) / WIDE_WAVES + 7) / 8 * 8);
+    SQ_TRY(launch<dense8_wide_scan_kernel<true>>(dim3((unsigned)a.nrb), dim3(WIDE_WAVES * 64), 0, st, a));
+    const Dense8WideThrPost tp{Dense8ThrPost{s.par8.as<float2>(), qn2}, tg_traw};
+    hipLaunchKernelGGL((kth_threshold_f32_kernel<Dense8WideThrPost>), dim3(nq), dim3(1024), 0, st, a.sample_out, ns, kk, thr, tp);
+    // full pass
+    a.tile_step = 1;
+    a.n_sel = n_tiles;
+    a.nrb = nrb;
+    a.wave_score = tighten ? s.wave_score.as<float>() : nullptr;
+    if (prof) SQ_HIP(hipEventRecord(s.ev[1], st));
+    SQ_TRY(launch<dense8_wide_scan_kernel<false>>(dim3((unsigned)nrb), dim3(WIDE_WAVES * 64), 0, st, a));
+    if (prof) SQ_HIP(hipEventRecord(s.ev[2], st));
+    if (tighten) {
+        const Dense8WideThrPost tp2{tp.base, nullptr};   // (the same slack rule, nothing else)
+        hipLaunchKernelGGL(dense_tighten_hist_kernel, dim3(64, 1), dim3(256), 0, st, a.wave_out, a.wave_score, a.wave_cnt, wave_cap, n_waves,
+                           (const float*)thr, (const float*)tg_traw, TILE_ROWS, tg_hist);
+        hipLaunchKernelGGL((dense_tighten_thr_kernel<Dense8WideThrPost>), dim3(1), dim3(64), 0, st, tg_hist, (const float*)thr,
+                           (const float*)tg_traw, nq, TILE_ROWS, kk, tp2, tg_thr2, tg_thr2k);
+    }
+    // exact re-rank of the survivors from the float32 rows, select, certify: the bfloat16 chain's kernels
+    const int wpb = 2;
+    const unsigned rr_threads = 128 * wpb;
+    const size_t rr_lds = ldq <= 156 ? (size_t)32 * (ldq + 4) * 4 : 0;
+    const unsigned gxr = (unsigned)((n_waves + wpb - 1) / wpb);
+    const double* cnx = h->cos_nx.as<double>();
+    const double* cnq = s.cos_nq.as<double>();
+    if (cosine) {
+        if (tighten)
+            hipLaunchKernelGGL((dense_rerank_filtered_kernel<K128, true>), dim3(gxr), dim3(rr_threads), rr_lds, st, h->db, h->ld, d,
+                               s.q_al.as<float>(), ldq, a.wave_out, a.wave_cnt, wave_cap, n_waves, wpb, nq, TILE_ROWS, s.keys.as<K128>(), cnt,
+                               cap, oflag, cnx, cnq, h->opt.dense_debug, (const float*)a.wave_score, (const float*)tg_thr2);
+        else
+            hipLaunchKernelGGL(dense_rerank_cos_kernel, dim3(gxr), dim3(rr_threads), rr_lds, st, h->db, h->ld, d, s.q_al.as<float>(), ldq,
+                               a.wave_out, a.wave_cnt, wave_cap, n_waves, wpb, nq, TILE_ROWS, s.keys.as<K128>(), cnt, cap, oflag, cnx, cnq,
+                               h->opt.dense_debug);
+        if (prof) SQ_HIP(hipEventRecord(s.ev[4], st));
+        DenseFinalizeCos fin{cnt, cap, kk, h->id_base, thr, 0.0, 1, (double*)out_dist, out_idx, hs_dev, hs_raw_dev, oflag, 0};
+        fin.lin = s.par8.as<float2>();
+        if (tighten) fin.thr2k = tg_thr2k;
+        return select_launch_t<K128>(s.keys.as<K128>(), cnt, cap, key_stride, k, nq, s.out_keys.as<K128>(), fin, st, s.sort_tmp);
+    }
+    if (tighten)
+        hipLaunchKernelGGL((dense_rerank_filtered_kernel<u64, false>), dim3(gxr), dim3(rr_threads), rr_lds, st, h->db, h->ld, d,
+                           s.q_al.as<float>(), ldq, a.wave_out, a.wave_cnt, wave_cap, n_waves, wpb, nq, TILE_ROWS, s.keys.as<u64>(), cnt, cap,
+                           oflag, (const double*)nullptr, (const double*)nullptr, h->opt.dense_debug, (const float*)a.wave_score,
+                           (const float*)tg_thr2);
+    else
+        hipLaunchKernelGGL(dense_rerank_l2_kernel, dim3(gxr), dim3(rr_threads), rr_lds, st, h->db, h->ld, d, s.q_al.as<float>(), ldq,
+                           a.wave_out, a.wave_cnt, wave_cap, n_waves, wpb, nq, TILE_ROWS, s.keys.as<u64>(), cnt, cap, oflag,
+                           h->opt.dense_debug);
+    if (prof) SQ_HIP(hipEventRecord(s.ev[4], st));
+    DenseFinalizeL2 fin{cnt, cap, kk, h->id_base, thr, qn2, 0.0, 1, (float*)out_dist, out_idx, hs_dev, hs_raw_dev, oflag, 0};
+    fin.lin = s.par8.as<float2>();
+    if (tighten) fin.thr2k = tg_thr2k;
+    return select_launch_t<u64>(s.keys.as<u64>(), cnt, cap, key_stride, k, nq, s.out_keys.as<u64>(), fin, st, s.sort_tmp, 4 * stride * kk);
+}
+
 // Enqueue one search (nq <= kDenseQueryChunk queries) on `st` with the workspace of slot `s`; nothing is
 // waited for.  dense_resolve() finishes the call: it waits for the kernels, reads the status words and
 // sends uncertified queries down the exact path.
@@ -502,7 +639,18 @@ static int dense_enqueue(DenseHandle* h, DenseSlot& s, const float* q, int nq, i
                ++h->direct_calls % h->probe_interval != 0) {
         c.all_fallback = true;   // (nothing enqueued: dense_resolve starts every query at the middle tier)
         c.mid_direct = true;
-    } else if (scan_ok && h->use8 && h->opt.dense_int8 != 0 && !(h->suspended8 && h->opt.dense_int8 < 0) && kk <= (cosine ? kSelectLdsKeys128 : kSelectLdsKeys64) &&
+    } else if (scan_ok && h->use8 && h->row8 > I8_MAX_ROW_BYTES && h->opt.dense_int8 != 0 && !(h->suspended8 && h->opt.dense_int8 < 0) && nq <= TILE_ROWS) {
+        // ---- rows of 513 to 8192 dimensions, one query tile: the int8 first stage of sq_dense_i8_wide.hpp
+        // (scan_ok: kk is inside the one-workgroup select; larger batches take the bfloat16 chain below)
+        c.int8 = true;
+        if (h->suspended8) {   // dense_int8 = 1 on the handle: the filter is armed again (and judged again from the next calls)
+            h->suspended8 = false;
+            h->overflow8 = 0;
+        }
+        c.stats.scan_launches = 2;
+        c.stats.bytes_scanned = h->n_pad64 * ((long long)h->row8 + 4);
+        SQ_TRY(dense8_wide_enqueue(h, s, q, nq, k, kk, out_dist, out_idx, st, prof, cap, hs_dev, hs_raw_dev));
+    } else if (scan_ok && h->use8 && h->row8 <= I8_MAX_ROW_BYTES && h->opt.dense_int8 != 0 && !(h->suspended8 && h->opt.dense_int8 < 0) && kk <= (cosine ? kSelectLdsKeys128 : kSelectLdsKeys64) &&
                (nq <= TILE_ROWS || (h->row8 == 128 && (qt == 2 || qt == 4) && nq <= h->opt.dense_int8_batch))) {
         // ---- the int8 first-stage filter (sq_dense_i8.hpp): half the bytes per row, measured error bound
         c.int8 = true;
@@ -1463,18 +1611,51 @@ static int dense_build_rows(DenseHandle* h, long long row_base) {
 // no more than 256 rows, or 20 per million, beyond it: those become always-candidates), the copy, its float64 residuals.  Data
 // no clamp suits (heavy tails: too many rows beyond every bound) keeps the bf16 filter alone, and so does a failure to
 // allocate: neither is an error.
+// (rows of 513 to 8192 dimensions, sq_dense_i8_wide.hpp: only where option "dense_int8_wide" asks for it)
+static bool dense8_is_wide(const DenseHandle* h) { return h->d > I8_MAX_ROW_BYTES; }
+static bool dense8_wide_wanted(const DenseHandle* h) { return h->opt.dense_int8_wide != 0 && h->d_pad <= MAX_DPAD; }
+// the build kernels for a row width: EPL = row bytes / 64, wide rows in chunks of 512 bytes (EPL = 8)
+template <class... A>
+static void dense8_energy_launch(int row8, dim3 grid, A... a) {
+    switch (row8) {
+        case 128: hipLaunchKernelGGL(dense8_energy_kernel<2>, grid, dim3(256), 0, 0, a...); break;
+        case 256: hipLaunchKernelGGL(dense8_energy_kernel<4>, grid, dim3(256), 0, 0, a...); break;
+        default: hipLaunchKernelGGL(dense8_energy_kernel<8>, grid, dim3(256), 0, 0, a...); break;
+    }
+}
+template <class... A>
+static void dense8_clip_stats_launch(int row8, dim3 grid, A... a) {
+    switch (row8) {
+        case 128: hipLaunchKernelGGL(dense8_clip_stats_kernel<2>, grid, dim3(256), 0, 0, a...); break;
+        case 256: hipLaunchKernelGGL(dense8_clip_stats_kernel<4>, grid, dim3(256), 0, 0, a...); break;
+        default: hipLaunchKernelGGL(dense8_clip_stats_kernel<8>, grid, dim3(256), 0, 0, a...); break;
+    }
+}
+template <class... A>
+static void dense8_build_launch(int row8, dim3 grid, A... a) {
+    switch (row8) {
+        case 128: hipLaunchKernelGGL(dense8_build_kernel<2>, grid, dim3(256), 0, 0, a..., row8); break;
+        case 256: hipLaunchKernelGGL(dense8_build_kernel<4>, grid, dim3(256), 0, 0, a..., row8); break;
+        default: hipLaunchKernelGGL(dense8_build_kernel<8>, grid, dim3(256), 0, 0, a..., row8); break;
+    }
+}
+// rows a pass over the copy covers: whole ring units of 64 rows, wide rows whole 32-row tiles
+static long long dense8_pass_rows(const DenseHandle* h, long long n) { return dense8_is_wide(h) ? (n + 31) / 32 * 32 : (n + 63) / 64 * 64; }
+
 static int dense8_build(DenseHandle* h) {
     h->use8 = false;
     h->suspended8 = false;
     h->overflow8 = 0;
-    if (h->d > I8_MAX_ROW_BYTES || h->n < 65536 || h->opt.dense_int8 == 0) return SQ_OK;
+    const bool wide = dense8_is_wide(h);
+    if ((wide && !dense8_wide_wanted(h)) || h->n < 65536 || h->opt.dense_int8 == 0) return SQ_OK;
     const bool cosine = h->metric == SQ_METRIC_COSINE;
     const double* nx64 = cosine ? h->cos_nx.as<double>() : nullptr;   // cosine: the copy holds the unit-length rows
     const long long n = h->n;
     h->n8_built = n;   // (an attempt counts whether or not the data is accepted: dense8_append tries again when the index has doubled)
     const int d = h->d;
-    const int row8 = i8_row_bytes(d);
-    const long long n_pad64 = (n + 63) / 64 * 64, n_alloc = (n + 127) / 128 * 128;
+    const int row8 = wide ? i8w_row_bytes(d) : i8_row_bytes(d);
+    const size_t spare8 = wide ? I8W_SPARE : 0;   // (the wide kernel's last half unit: sq_dense_i8_wide.hpp)
+    const long long n_pad64 = dense8_pass_rows(h, n), n_alloc = (n + 127) / 128 * 128;
     const float* centerp = (!cosine && h->center.p) ? h->center.as<float>() : nullptr;
     DevBuf tmp;   // [sum f64 x2 | max bits u32 x2 | flagged u32]
     DevBuf r2row;
@@ -1487,7 +1668,7 @@ static int dense8_build(DenseHandle* h) {
         }
         return rc;
     };
-    if (tmp.reserve(64) != SQ_OK || r2row.reserve((size_t)n_alloc * 4) != SQ_OK || h->scan8.reserve((size_t)n_alloc * row8) != SQ_OK ||
+    if (tmp.reserve(64) != SQ_OK || r2row.reserve((size_t)n_alloc * 4) != SQ_OK || h->scan8.reserve((size_t)n_alloc * row8 + spare8) != SQ_OK ||
         h->nrow8.reserve((size_t)(n_alloc + 64) * 4) != SQ_OK) {   // (+ 64: a 32-row unit's DMA fetches 64 row terms)
         (void)hipGetLastError();
         return quit(SQ_OK);
@@ -1497,11 +1678,7 @@ static int dense8_build(DenseHandle* h) {
     for (int pass = 0; pass < 3; ++pass) {
         double er[2] = {0.0, 0.0};
         SQ_HIP(hipMemset(tmp.p, 0, 64));
-        switch (row8) {
-            case 128: hipLaunchKernelGGL(dense8_energy_kernel<2>, dim3(stat_blocks), dim3(256), 0, 0, h->db, n, h->ld, d, centerp, nx64, cap_e, tmp.as<double>()); break;
-            case 256: hipLaunchKernelGGL(dense8_energy_kernel<4>, dim3(stat_blocks), dim3(256), 0, 0, h->db, n, h->ld, d, centerp, nx64, cap_e, tmp.as<double>()); break;
-            default: hipLaunchKernelGGL(dense8_energy_kernel<8>, dim3(stat_blocks), dim3(256), 0, 0, h->db, n, h->ld, d, centerp, nx64, cap_e, tmp.as<double>()); break;
-        }
+        dense8_energy_launch(row8, dim3(stat_blocks), h->db, n, h->ld, d, centerp, nx64, cap_e, tmp.as<double>());
         SQ_HIP(hipMemcpy(er, tmp.p, 16, hipMemcpyDeviceToHost));
         if (!(er[1] >= 0.5 * (double)n)) return quit(SQ_OK);   // (half the rows non-finite or beyond 16 x the mean: not this filter's data)
         rms = sqrt(er[0] / (er[1] * d));
@@ -1531,11 +1708,7 @@ static int dense8_build(DenseHandle* h) {
     // large matrices choose from every 8th row (the kernel evaluates twelve clamps per element: 16 ms of a 40 ms build at
     // 10 M x 128 when it reads every row; the choice needs the shape of the residuals' tail, not every row)
     const int clip_step = n >= 2000000 ? 8 : 1;
-    switch (row8) {
-        case 128: hipLaunchKernelGGL(dense8_clip_stats_kernel<2>, dim3(stat_blocks), dim3(256), 0, 0, h->db, n, h->ld, d, centerp, nx64, ca, clipbuf.as<u32>(), clip_step); break;
-        case 256: hipLaunchKernelGGL(dense8_clip_stats_kernel<4>, dim3(stat_blocks), dim3(256), 0, 0, h->db, n, h->ld, d, centerp, nx64, ca, clipbuf.as<u32>(), clip_step); break;
-        default: hipLaunchKernelGGL(dense8_clip_stats_kernel<8>, dim3(stat_blocks), dim3(256), 0, 0, h->db, n, h->ld, d, centerp, nx64, ca, clipbuf.as<u32>(), clip_step); break;
-    }
+    dense8_clip_stats_launch(row8, dim3(stat_blocks), h->db, n, h->ld, d, centerp, nx64, ca, clipbuf.as<u32>(), clip_step);
     u32 counts[I8_NCLIP][I8_NCUT];
     SQ_HIP(hipMemcpy(counts, clipbuf.p, clip_bytes, hipMemcpyDeviceToHost));
     clipbuf.release();
@@ -1555,16 +1728,13 @@ static int dense8_build(DenseHandle* h) {
     if (best_c < 0) return quit(SQ_OK);   // every clamp leaves too many rows beyond every bound (heavy tails): the bf16 filter's relative bound suits such data
     const double dx = (double)ca.dx[best_c];
     {
-        const dim3 grid((unsigned)((n_alloc + 3) / 4)), blk(256);
+        const dim3 grid((unsigned)((n_alloc + 3) / 4));
         signed char* o8 = h->scan8.as<signed char>();
         float* nr8 = h->nrow8.as<float>();
         float* r2p = r2row.as<float>();
-        switch (row8) {
-            case 128: hipLaunchKernelGGL(dense8_build_kernel<2>, grid, blk, 0, 0, h->db, n, h->ld, d, n_alloc, centerp, nx64, ca.inv_dx[best_c], ca.dx[best_c], o8, nr8, r2p, 0ll); break;
-            case 256: hipLaunchKernelGGL(dense8_build_kernel<4>, grid, blk, 0, 0, h->db, n, h->ld, d, n_alloc, centerp, nx64, ca.inv_dx[best_c], ca.dx[best_c], o8, nr8, r2p, 0ll); break;
-            default: hipLaunchKernelGGL(dense8_build_kernel<8>, grid, blk, 0, 0, h->db, n, h->ld, d, n_alloc, centerp, nx64, ca.inv_dx[best_c], ca.dx[best_c], o8, nr8, r2p, 0ll); break;
-        }
+        dense8_build_launch(row8, grid, h->db, n, h->ld, d, n_alloc, centerp, nx64, ca.inv_dx[best_c], ca.dx[best_c], o8, nr8, r2p, 0ll);
         SQ_HIP(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(nr8 + n_alloc), 0x7f800000, 64));   // (+inf behind the last unit)
+        if (spare8) SQ_HIP(hipMemset(o8 + (size_t)n_alloc * row8, 0, spare8));
     }
     double* sum_r2 = tmp.as<double>() + 1;
     u32* maxb = reinterpret_cast<u32*>(tmp.as<double>() + 2);
@@ -1676,7 +1846,8 @@ static int grow_keep(DevBuf& b, size_t used, size_t need) {
 // from all its rows; one that had no copy (too small, or declined) tries when it has doubled since its last attempt.
 static int dense8_append(DenseHandle* h, long long n_old) {
     const long long n = h->n;
-    if (h->opt.dense_int8 == 0 || h->d > I8_MAX_ROW_BYTES) return SQ_OK;
+    // (a wide copy that exists follows the appends whatever "dense_int8_wide" says by now; none is started without it)
+    if (h->opt.dense_int8 == 0 || (dense8_is_wide(h) && !h->use8 && !dense8_wide_wanted(h))) return SQ_OK;
     if (!h->use8) {
         if (n >= 65536 && n >= 2 * h->n8_built) {
             h->n8_built = n;   // (the attempt counts whether or not the build accepts the data)
@@ -1689,14 +1860,15 @@ static int dense8_append(DenseHandle* h, long long n_old) {
     const double* nx64 = cosine ? h->cos_nx.as<double>() : nullptr;
     const float* centerp = (!cosine && h->center.p) ? h->center.as<float>() : nullptr;
     const int row8 = h->row8, d = h->d;
-    const long long n_pad64 = (n + 63) / 64 * 64, n_alloc = (n + 127) / 128 * 128;
+    const long long n_pad64 = dense8_pass_rows(h, n), n_alloc = (n + 127) / 128 * 128;
+    const size_t spare8 = dense8_is_wide(h) ? I8W_SPARE : 0;
     auto drop = [&]() {
         h->use8 = false;
         h->scan8.release();
         h->nrow8.release();
         return SQ_OK;
     };
-    if (grow_keep(h->scan8, (size_t)h->n_alloc8 * row8, (size_t)n_alloc * row8) != SQ_OK ||
+    if (grow_keep(h->scan8, (size_t)h->n_alloc8 * row8, (size_t)n_alloc * row8 + spare8) != SQ_OK ||
         grow_keep(h->nrow8, (size_t)(h->n_alloc8 + 64) * 4, (size_t)(n_alloc + 64) * 4) != SQ_OK) {
         (void)hipGetLastError();
         return drop();
@@ -1715,16 +1887,13 @@ static int dense8_append(DenseHandle* h, long long n_old) {
     };
     const long long row_base = n_old / 128 * 128;   // the unit the old rows ended in is redone with the new ones
     {
-        const dim3 grid((unsigned)((n_alloc - row_base + 3) / 4)), blk(256);
+        const dim3 grid((unsigned)((n_alloc - row_base + 3) / 4));
         signed char* o8 = h->scan8.as<signed char>();
         float* nr8 = h->nrow8.as<float>();
         float* r2p = r2row.as<float>();
-        switch (row8) {
-            case 128: hipLaunchKernelGGL(dense8_build_kernel<2>, grid, blk, 0, 0, h->db, n, h->ld, d, n_alloc, centerp, nx64, h->inv_dxf8, h->dxf8, o8, nr8, r2p, row_base); break;
-            case 256: hipLaunchKernelGGL(dense8_build_kernel<4>, grid, blk, 0, 0, h->db, n, h->ld, d, n_alloc, centerp, nx64, h->inv_dxf8, h->dxf8, o8, nr8, r2p, row_base); break;
-            default: hipLaunchKernelGGL(dense8_build_kernel<8>, grid, blk, 0, 0, h->db, n, h->ld, d, n_alloc, centerp, nx64, h->inv_dxf8, h->dxf8, o8, nr8, r2p, row_base); break;
-        }
+        dense8_build_launch(row8, grid, h->db, n, h->ld, d, n_alloc, centerp, nx64, h->inv_dxf8, h->dxf8, o8, nr8, r2p, row_base);
         SQ_HIP(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(nr8 + n_alloc), 0x7f800000, 64));
+        if (spare8) SQ_HIP(hipMemset(o8 + (size_t)n_alloc * row8, 0, spare8));
     }
     SQ_HIP(hipMemset(tmp.p, 0, 64));
     double* sum_r2 = tmp.as<double>() + 1;
@@ -1803,6 +1972,8 @@ extern "C" int sq_dense_info(sq_handle_t hid, int64_t* out, int n_out) {
     out[3] = h->owned.p ? 1 : 0;                                          // ... owned by the library (1) or borrowed from the caller (0)
     out[4] = (int64_t)h->scan.cap;                                        // bfloat16 scan copy
     out[5] = (int64_t)(h->scan8.cap + h->nrow8.cap);                      // int8 scan copy + its row terms
+    if (h->use8 && h->row8 > I8_MAX_ROW_BYTES)                            // (rows beyond 512 dimensions: the bytes the copy occupies -- it follows every append)
+        out[5] = (int64_t)((size_t)h->n_alloc8 * h->row8 + I8W_SPARE + (size_t)(h->n_alloc8 + 64) * 4);
     out[6] = (int64_t)(h->norms.cap + h->norms1.cap + h->cos_nx.cap + h->center.cap + h->zeros.cap);   // row statistics
     out[7] = h->use8 && !h->suspended8 ? 1 : 0;                                             // the int8 first stage is in use
     out[8] = h->build_us;                                                 // sq_dense_create: wall time of the whole build

@@ -68,7 +68,8 @@ __device__ __forceinline__ float i8_element(float v, const float* __restrict__ c
 // sum over rows of |x - c|^2 (float64) and their number, rows with |x - c|^2 > cap left out: the element rms the clamp
 // candidates are multiples of.  The host runs it three times, cap = inf, then 16 x the mean of the pass before: a few
 // rows thousands of times the size of the rest would otherwise own the rms (they end up beyond R either way).
-template <int EPL>   // elements per lane: row_bytes / 64
+// (rows beyond 512 dimensions, sq_dense_i8_wide.hpp: EPL = 8 and as many 512-element chunks as the row has)
+template <int EPL>   // elements per lane and chunk: min(row_bytes, 512) / 64
 static __global__ __launch_bounds__(256) void dense8_energy_kernel(const float* __restrict__ db, long long n, long long ld, int d,
                                                                     const float* __restrict__ center, const double* __restrict__ nx64,
                                                                     double cap, double* __restrict__ sum) {   // [0]: energy, [1]: rows
@@ -80,14 +81,16 @@ static __global__ __launch_bounds__(256) void dense8_energy_kernel(const float* 
         double e = 0.0;
         bool bad = false;
         const double inv_norm = nx64 ? 1.0 / sqrt(nx64[row]) : 1.0;
+        for (int k0 = 0; k0 < d; k0 += 64 * EPL) {
 #pragma unroll
-        for (int j = 0; j < EPL; ++j) {
-            const int k = EPL * lane + j;
-            if (k < d) {
-                const float v = db[row * ld + k];
-                const float xc = i8_element(v, center, k, nx64 != nullptr, inv_norm);
-                if (!(fabsf(xc) < 3.0e38f)) bad = true;
-                e += (double)xc * (double)xc;
+            for (int j = 0; j < EPL; ++j) {
+                const int k = k0 + EPL * lane + j;
+                if (k < d) {
+                    const float v = db[row * ld + k];
+                    const float xc = i8_element(v, center, k, nx64 != nullptr, inv_norm);
+                    if (!(fabsf(xc) < 3.0e38f)) bad = true;
+                    e += (double)xc * (double)xc;
+                }
             }
         }
         if (__ballot(bad) != 0ull) continue;
@@ -139,18 +142,20 @@ static __global__ __launch_bounds__(256) void dense8_clip_stats_kernel(const flo
         for (int c = 0; c < I8_NCLIP; ++c) r2[c] = 0.f;
         bool bad = false;
         const double inv_norm = nx64 ? 1.0 / sqrt(nx64[row]) : 1.0;
+        for (int k0 = 0; k0 < d; k0 += 64 * EPL) {
 #pragma unroll
-        for (int j = 0; j < EPL; ++j) {
-            const int k = EPL * lane + j;
-            if (k < d) {
-                const float v = db[row * ld + k];
-                const float xc = i8_element(v, center, k, nx64 != nullptr, inv_norm);
-                if (!(fabsf(xc) < 3.0e38f)) bad = true;
+            for (int j = 0; j < EPL; ++j) {
+                const int k = k0 + EPL * lane + j;
+                if (k < d) {
+                    const float v = db[row * ld + k];
+                    const float xc = i8_element(v, center, k, nx64 != nullptr, inv_norm);
+                    if (!(fabsf(xc) < 3.0e38f)) bad = true;
 #pragma unroll
-                for (int c = 0; c < I8_NCLIP; ++c) {
-                    const float t = fminf(fmaxf(rintf(xc * ca.inv_dx[c]), -127.f), 127.f);
-                    const float res = __fmaf_rn(-t, ca.dx[c], xc);
-                    r2[c] = __fmaf_rn(res, res, r2[c]);
+                    for (int c = 0; c < I8_NCLIP; ++c) {
+                        const float t = fminf(fmaxf(rintf(xc * ca.inv_dx[c]), -127.f), 127.f);
+                        const float res = __fmaf_rn(-t, ca.dx[c], xc);
+                        r2[c] = __fmaf_rn(res, res, r2[c]);
+                    }
                 }
             }
         }
@@ -173,56 +178,60 @@ static __global__ __launch_bounds__(256) void dense8_clip_stats_kernel(const flo
 
 // One wave per row: the int8 row, N_row = RD(|x'|^2) and the measured residual r_row^2 (rounded up) of rows
 // [row_base, n_pad).  Padding rows: zeros and N_row = +inf.  Rows with a non-finite element: N_row = +inf (their true
-// distance is inf / NaN: they rank last, as in the bf16 filter) and no residual.
+// distance is inf / NaN: they rank last, as in the bf16 filter) and no residual.  `row_bytes`: 64 EPL, or for rows beyond
+// 512 dimensions (EPL = 8) any multiple of 128: the row is written in chunks of 512 bytes, zeros behind d.
 template <int EPL>
 static __global__ __launch_bounds__(256) void dense8_build_kernel(const float* __restrict__ db, long long n, long long ld, int d,
                                                                    long long n_pad, const float* __restrict__ center,
                                                                    const double* __restrict__ nx64, float inv_dx, float dx,
                                                                    signed char* __restrict__ out8, float* __restrict__ nrow,
-                                                                   float* __restrict__ r2row, long long row_base) {
+                                                                   float* __restrict__ r2row, long long row_base, int row_bytes) {
     const int lane = threadIdx.x & 63;
     const long long row = row_base + (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= n_pad) return;
-    unsigned char q[EPL];
-#pragma unroll
-    for (int j = 0; j < EPL; ++j) q[j] = 0;
     double e2 = 0.0, r2 = 0.0;
     bool finite = true;
-    if (row < n) {
-        const double inv_norm = nx64 ? 1.0 / sqrt(nx64[row]) : 1.0;
+    const double inv_norm = (row < n && nx64) ? 1.0 / sqrt(nx64[row]) : 1.0;
+    for (int k0 = 0; k0 < row_bytes; k0 += 64 * EPL) {
+        unsigned char q[EPL];
 #pragma unroll
-        for (int j = 0; j < EPL; ++j) {
-            const int k = EPL * lane + j;
-            if (k < d) {
-                const float v = db[row * ld + k];
-                const float xc = i8_element(v, center, k, nx64 != nullptr, inv_norm);
-                if (!(xc == xc) || !(fabsf(xc) < 3.0e38f)) finite = false;
-                float t = rintf(xc * inv_dx);
-                t = fminf(fmaxf(t, -127.f), 127.f);
-                if (!(t == t)) t = 0.f;
-                q[j] = (unsigned char)(signed char)(int)t;
-                const double res = (double)xc - (double)t * (double)dx;
-                e2 += (double)xc * (double)xc;
-                r2 += res * res;
+        for (int j = 0; j < EPL; ++j) q[j] = 0;
+        if (row < n) {
+#pragma unroll
+            for (int j = 0; j < EPL; ++j) {
+                const int k = k0 + EPL * lane + j;
+                if (k < d) {
+                    const float v = db[row * ld + k];
+                    const float xc = i8_element(v, center, k, nx64 != nullptr, inv_norm);
+                    if (!(xc == xc) || !(fabsf(xc) < 3.0e38f)) finite = false;
+                    float t = rintf(xc * inv_dx);
+                    t = fminf(fmaxf(t, -127.f), 127.f);
+                    if (!(t == t)) t = 0.f;
+                    q[j] = (unsigned char)(signed char)(int)t;
+                    const double res = (double)xc - (double)t * (double)dx;
+                    e2 += (double)xc * (double)xc;
+                    r2 += res * res;
+                }
             }
+        }
+        // EPL bytes per lane, packed: a chunk is EPL * 64 bytes (the last chunk of a wide row may be 128 or 256 or 384 bytes)
+        if (k0 + EPL * lane >= row_bytes) continue;
+        unsigned char* dst = reinterpret_cast<unsigned char*>(out8) + row * row_bytes + k0 + EPL * lane;
+        if constexpr (EPL == 2) {
+            *reinterpret_cast<unsigned short*>(dst) = (unsigned short)(q[0] | (q[1] << 8));
+        } else if constexpr (EPL == 4) {
+            *reinterpret_cast<u32*>(dst) = (u32)q[0] | ((u32)q[1] << 8) | ((u32)q[2] << 16) | ((u32)q[3] << 24);
+        } else {
+            uint2 w;
+            w.x = (u32)q[0] | ((u32)q[1] << 8) | ((u32)q[2] << 16) | ((u32)q[3] << 24);
+            w.y = (u32)q[4] | ((u32)q[5] << 8) | ((u32)q[6] << 16) | ((u32)q[7] << 24);
+            *reinterpret_cast<uint2*>(dst) = w;
         }
     }
     finite = __ballot(!finite) == 0ull;
     for (int o = 32; o > 0; o >>= 1) {
         e2 += __shfl_xor(e2, o);
         r2 += __shfl_xor(r2, o);
-    }
-    // EPL bytes per lane, packed: the row is EPL * 64 bytes
-    unsigned char* dst = reinterpret_cast<unsigned char*>(out8) + row * (EPL * 64) + EPL * lane;
-    if constexpr (EPL == 2) {
-        *reinterpret_cast<unsigned short*>(dst) = (unsigned short)(q[0] | (q[1] << 8));
-    } else if constexpr (EPL == 4) {
-        *reinterpret_cast<u32*>(dst) = (u32)q[0] | ((u32)q[1] << 8) | ((u32)q[2] << 16) | ((u32)q[3] << 24);
-    } else {
-        uint2 w;
-        w.x = (u32)q[0] | ((u32)q[1] << 8) | ((u32)q[2] << 16) | ((u32)q[3] << 24);
-        w.y = (u32)q[4] | ((u32)q[5] << 8) | ((u32)q[6] << 16) | ((u32)q[7] << 24);
-        *reinterpret_cast<uint2*>(dst) = w;
     }
     if (lane == 0) {
         float nr = __builtin_inff(), rr = 0.f;

@@ -38,6 +38,9 @@ static __global__ __launch_bounds__(256) void dense_tighten_hist_kernel(const ui
         const uint2* seg = wave_out + w * wave_cap;
         const float* sc = wave_score + w * wave_cap;
         for (u32 e = threadIdx.x; e < c; e += 256) {
+            // (an entry that holds an always-candidate row of the int8 copy, score -inf: its true score is unknown -- it
+            // bounds nothing and is not counted; the re-rank takes it whatever T'' is)
+            if (sc[e] == -__builtin_inff()) continue;
             const u32 ql = seg[e].y & 0xffffu;
             const float t1 = thr[g0 + ql], wbin = (t1 - traw[g0 + ql]) * 0.03125f;
             int bin = 0;

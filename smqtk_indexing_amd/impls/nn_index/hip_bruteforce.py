@@ -86,7 +86,10 @@ class HipBruteForceNearestNeighborsIndex(NearestNeighborsIndex):
     def _device(self) -> _lib.DenseIndex:
         if self._dev is None:
             _require_usable(self)
-            self._dev = _lib.DenseIndex(self._matrix, metric=self.METRICS[self.distance_method])
+            # an index built while the process-wide "dense_int8_wide" is 1 keeps the choice as its own: its int8 copy then
+            # survives a compaction (which builds it again) whatever the process-wide value is by that time
+            kw = {"options": {"dense_int8_wide": 1}} if _lib.process_option("dense_int8_wide", 0) == 1 else {}
+            self._dev = _lib.DenseIndex(self._matrix, metric=self.METRICS[self.distance_method], **kw)
         return self._dev
 
     @staticmethod
