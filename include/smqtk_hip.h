@@ -126,7 +126,16 @@ int sq_get_stats(sq_handle_t h, sq_stats_t* out);
  * `norm(x) - mean` in the promoted dtype of the two operands (itq.py:404), so
  * a float32 model applied to float32 descriptors subtracts in float32 (a model
  * ItqFunctor.fit trained on float32 descriptors has a float32 mean_vec); every
- * other combination subtracts in float64. */
+ * other combination subtracts in float64.
+ * Which kernel hashes the rows -- one rule: a float32 or float64 descriptor of up to 8192 elements whose row is a whole
+ * number of 16-byte pieces (float32: d % 4 == 0, float64: d % 2 == 0), 16-byte aligned, codes up to 256 bits,
+ * normalize None or 2, at least 32 rows, is hashed by a certified float16 filter, and only the bits the filter cannot
+ * decide are evaluated in float64; the codes are those of the float64 evaluation either way.  By width:
+ *   d % 64 == 0, d <= 256, float32, <= 128 bits   the narrow kernel (whole 256-byte row units, the HBM-rate path)
+ *   d % 64 == 0, d <= 512, otherwise              the wide kernel
+ *   every other width up to 8192 (4, 100, 300, 500, 1000, 2048, 4100 ...)   the slab ("extra-wide") kernel
+ * Everything else -- other normalize orders, option "itq_exact", fewer than 32 rows, rows that are no whole number of
+ * 16-byte pieces (50 float32 elements), unaligned pointers, wider codes -- is hashed by the all-float64 kernel. */
 int sq_itq_hash(const void* x, int x_dtype, int64_t n, int d,
                 const double* mean, int mean_dtype, const double* rotation, int bits, int norm_ord,
                 uint64_t* out_codes, int mem, void* stream);
@@ -320,9 +329,9 @@ int sq_dense_distances(const void* query, const void* rows, int dtype, int64_t n
  * rotation [d][bits] f64 are uploaded once; sq_itq_model_hash then moves only the rows and the codes (small
  * batches through pinned staging).  What ItqFunctor.get_hash costs per query vector in
  * LSHNearestNeighborIndex._nn (impls/nn_index/lsh.py:473): without this every call re-uploads the rotation.
- * Rows of 513 .. 8192 elements (whole 16-byte pieces, normalize None / 2, codes up to 256 bits, at least 32 rows) go
- * through the extra-wide certified filter; the model keeps that filter's image of the rotation from the first such
- * call on.
+ * The rows go through the filters of sq_itq_hash, by the same rule.  Where that is the slab ("extra-wide") filter --
+ * more than 512 elements, or a width that is no multiple of 64 -- the model keeps that filter's image of the rotation
+ * from the first such call on.
  * sq_get_stats on a model handle describes the last sq_itq_model_hash, in the fields of sq_stats_t:
  *   scan_launches     filter kernels that streamed the rows (0: the float64 kernel hashed them)
  *   candidates        bits the filter left undecided, evaluated in float64 (-1 after a SQ_MEM_DEVICE call, which is

@@ -724,10 +724,27 @@ static int itq_wide_path(const ItqArgs& a, hipStream_t st, int device, ItqCallCt
 #include "sq_itq_xwide.hpp"   // (needs ItqArgs, f64x4 and the numpy-order helpers above)
 namespace sq {
 
-// The extra-wide filter (sq_itq_xwide.hpp): 512 < d <= 8192, float32 or float64 rows of whole 16-byte pieces.
+// Which certified filter hashes a shape: a pure function of (element size, d, words of the code).  The rule: a float32
+// or float64 descriptor of up to 8192 elements whose row is a whole number of 16-byte pieces (float32: d % 4 == 0,
+// float64: d % 2 == 0), codes up to 256 bits, is hashed by a certified filter --
+//   d % 64 == 0, d <= 256, float32, <= 128 bits   the narrow kernel (sq_itq_fast.hpp, whole 256-byte row units)
+//   d % 64 == 0, d <= 512, otherwise              the wide kernel   (sq_itq_wide.hpp, whole 256-byte row units)
+//   every other d <= 8192                         the slab kernel   (sq_itq_xwide.hpp, 16-byte pieces guarded by k < d)
+// and everything else by the float64 kernel.  What a call adds (itq_launch): at least 32 rows, a 16-byte aligned
+// pointer, normalize None or 2, option itq_exact off -- otherwise the float64 kernel as well.
+// (measured, profiles/itq_any_width.txt: the slab kernel at d = 100 / 300 / 500 against the float64 kernel and against
+// the unit kernels on rows zero-padded to the next multiple of 64)
+enum ItqRoute { ITQ_ROUTE_F64 = 0, ITQ_ROUTE_NARROW, ITQ_ROUTE_WIDE, ITQ_ROUTE_XWIDE };
+static ItqRoute itq_filter_route(size_t esz, int d, int words) {
+    if (d < 1 || d > ITQX_MAX_D || words > 4 || ((size_t)d * esz) % 16 != 0) return ITQ_ROUTE_F64;
+    if (d % 64 == 0 && d <= 512) return esz == 4 && itq_fast_geometry(d, words).stages >= 2 ? ITQ_ROUTE_NARROW : ITQ_ROUTE_WIDE;
+    return ITQ_ROUTE_XWIDE;
+}
+
+// The extra-wide filter (sq_itq_xwide.hpp): d <= 8192, float32 or float64 rows of whole 16-byte pieces.
 template <class T>
 static bool itq_xwide_applies(const ItqArgs& a) {
-    return a.d >= ITQX_MIN_D && a.d <= ITQX_MAX_D && a.words <= 4 && a.n >= 32 && a.n < (1ll << 29) &&
+    return a.d >= 1 && a.d <= ITQX_MAX_D && a.words <= 4 && a.n >= 32 && a.n < (1ll << 29) &&
            (reinterpret_cast<uintptr_t>(a.x) & 15u) == 0 && ((size_t)a.d * sizeof(T)) % 16 == 0 && !a.exact &&
            (a.norm == SQ_NORM_NONE || a.norm == SQ_NORM_L2);
 }
@@ -845,14 +862,15 @@ static int itq_xwide_path(const ItqArgs& a, hipStream_t st, int device, ItqCallC
 template <class T>
 static int itq_launch(const ItqArgs& a0, hipStream_t st, int device, ItqCallCtx* ctx = nullptr) {
     ItqArgs a = a0;
+    const ItqRoute route = itq_filter_route(sizeof(T), a.d, a.words);
     if constexpr (sizeof(T) == 4) {
         const ItqFastGeom g = itq_fast_geometry(a.d, a.words);
-        if (g.stages >= 2 && a.n >= 32 && a.n < (1ll << 30) && (reinterpret_cast<uintptr_t>(a.x) & 15u) == 0 &&
+        if (route == ITQ_ROUTE_NARROW && a.n >= 32 && a.n < (1ll << 30) && (reinterpret_cast<uintptr_t>(a.x) & 15u) == 0 &&
             !a.exact && (a.norm == SQ_NORM_NONE || a.norm == SQ_NORM_L2))  // (the other orders: float64 kernel)
             return itq_fast_path(a, g, st, device, ctx);
     }
-    if (itq_wide_applies<T>(a)) return itq_wide_path<T>(a, st, device, ctx);
-    if (itq_xwide_applies<T>(a)) return itq_xwide_path<T>(a, st, device, ctx);
+    if ((route == ITQ_ROUTE_NARROW || route == ITQ_ROUTE_WIDE) && itq_wide_applies<T>(a)) return itq_wide_path<T>(a, st, device, ctx);
+    if (route == ITQ_ROUTE_XWIDE && itq_xwide_applies<T>(a)) return itq_xwide_path<T>(a, st, device, ctx);
     if (ctx) ctx->fallback_rows += a.n;
     void* nrm = nullptr;
     int rc = SQ_OK;

@@ -36,7 +36,7 @@ static constexpr int ITQW_MAX_CT = 8;                // column tiles of 32: <= 2
 struct ItqWideArgs {
     const void* x;         // [n][d] rows of T, 16-byte aligned
     long long n;
-    int d;                 // d % 64 == 0, d <= 512
+    int d;                 // d % 64 == 0, d <= 512 (whole 256-byte row units; every other width: sq_itq_xwide.hpp, see itq_filter_route)
     const uint4* rimage;   // itq_fast_prep_kernel's image: [pc][2 planes][dp*2 bytes]
     const float* colnorm;  // [pc] per-column error coefficients (sq_itq_fast.hpp)
     const float* cabs;

@@ -1,5 +1,7 @@
 // The certified float16 filter of ItqFunctor.get_hash for descriptors of 513 .. 8192 elements (the reference's own
-// examples hash 2048-d and 4096-d CNN descriptors), codes up to 256 bits, float32 or float64 rows, normalize None / 2.
+// examples hash 2048-d and 4096-d CNN descriptors) and for every width of 1 .. 512 that is no multiple of 64 (100-,
+// 200-, 300-d descriptors: itq_filter_route, sq_itq.hip), codes up to 256 bits, float32 or float64 rows of whole
+// 16-byte pieces, normalize None / 2.
 // sq_itq_wide.hpp keeps a 32-row tile's fragments resident (d/2 registers per lane: 256 at d = 512) and streams R past
 // them; that does not stretch.  Here BOTH operands are blocked over k, in slabs of 64:
 //
@@ -14,8 +16,11 @@
 //     tile][plane][k-step][lane] x 16 bytes -- so one LDS-DMA instruction moves one fragment (1 KB, contiguous in
 //     global memory and in LDS) and a fragment read is lane * 16: no bank conflict, no swizzle.  One s_barrier per
 //     slab (12 CT MFMAs per wave).
-//   * a d that is no multiple of 64 (1000, 2000, 4100): lanes beyond the row contribute zero fragments, and the image
-//     is zero there.
+//   * a d that is no multiple of 64 (1000, 2000, 4100; 4, 36, 100, 300, 500): a 16-byte piece is inside its row or
+//     beyond it (load_x), a piece beyond it is not read -- the last row of the caller's buffer ends the last access --
+//     and stands as zeros in the fragments, in |x|^2 and in max |x_k|; the image is zero there (the caller clears it),
+//     so the k-steps past d add exact zeros to the accumulators.  Nothing in the kernel depends on d >= 513: a row
+//     shorter than one slab (d < 64) is one slab with most pieces absent.
 //
 // Error bound.  As in sq_itq_fast.hpp, relative to |x||R_b| (Cauchy-Schwarz):
 //   2^-20 (x: two truncated float16 planes) + 2^-21 (the dropped x_lo R_lo) + 2^-20 (the reference's float32 x/|x|,
@@ -26,7 +31,9 @@
 //   (x_hi R_hi, x_lo R_hi, x_hi R_lo: 1.5 (192 + 8) 2^-24 of the slab's sum of |x_k R_kb| (1 + 2^-9), and the slabs'
 //   bounds add up to |x||R_b|) and is then added to the tile's running float32 sum on the vector unit:
 //   ceil(d / 64) additions, 1.5 (d / 64 + 1) 2^-24.  At d = 4096: 2.6e-5 in all, about 0.13 % of the bits undecided
-//   on normal data (z_b is spread over |x||R_b| / sqrt(d)); at d = 8192: 3.2e-5.
+//   on normal data (z_b is spread over |x||R_b| / sqrt(d)); at d = 8192: 3.2e-5; at d <= 512 (at most 8 slabs): at most
+//   2.1e-5 (the per-slab term dominates).  Zero-padded k is on neither side of the bound: the padded products are 0 * 0 with
+//   no rounding, |x| and |R_b| (itq_fast_prep_kernel sums k < d only) do not see them, and the slab count is ceil(d / 64).
 //   c_b = mean . R_b is subtracted last, once, in float32 (it does not ride through the accumulation); its rounding
 //   and float64 summation error are itq_fast_prep_kernel's cberr, R's own residual its colnorm, the float16
 //   subnormal part of the split its cabs: those coefficients carry over unchanged.
@@ -45,7 +52,7 @@ namespace sq {
 
 static constexpr int ITQX_WAVES = 4;
 static constexpr int ITQX_SLAB_K = 64;          // k per slab: 4 MFMA k-steps, one 256-byte unit of a float32 row
-static constexpr int ITQX_MIN_D = 513, ITQX_MAX_D = 8192;
+static constexpr int ITQX_MAX_D = 8192;   // (no lower limit: sq_itq.hip routes d <= 512, d % 64 != 0 here too)
 
 struct ItqXwideArgs {
     const void* x;         // [n][d] rows of T, 16-byte aligned rows
