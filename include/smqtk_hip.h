@@ -128,14 +128,20 @@ int sq_get_stats(sq_handle_t h, sq_stats_t* out);
  * ItqFunctor.fit trained on float32 descriptors has a float32 mean_vec); every
  * other combination subtracts in float64.
  * Which kernel hashes the rows -- one rule: a float32 or float64 descriptor of up to 8192 elements whose row is a whole
- * number of 16-byte pieces (float32: d % 4 == 0, float64: d % 2 == 0), 16-byte aligned, codes up to 256 bits,
+ * number of 16-byte pieces (float32: d % 4 == 0, float64: d % 2 == 0), 16-byte aligned, codes up to 1024 bits,
  * normalize None or 2, at least 32 rows, is hashed by a certified float16 filter, and only the bits the filter cannot
- * decide are evaluated in float64; the codes are those of the float64 evaluation either way.  By width:
+ * decide are evaluated in float64; the codes are those of the float64 evaluation either way.  By width and bits:
  *   d % 64 == 0, d <= 256, float32, <= 128 bits   the narrow kernel (whole 256-byte row units, the HBM-rate path)
- *   d % 64 == 0, d <= 512, otherwise              the wide kernel
- *   every other width up to 8192 (4, 100, 300, 500, 1000, 2048, 4100 ...)   the slab ("extra-wide") kernel
+ *   d % 64 == 0, d <= 512, <= 256 bits otherwise  the wide kernel
+ *   every other width up to 8192 (4, 100, 300, 500, 1000, 2048, 4100 ...) at up to 256 bits, and
+ *   every width up to 8192 at 257 .. 1024 bits    the slab ("extra-wide") kernel
+ * Beyond 256 bits the slab kernel runs the code's columns in groups of 256 bits (4 words of the code; the last group
+ * the remaining 1 .. 4 words), one pass over the rows per group: 512 bits are 2 passes, 1024 bits 4.  Measured
+ * (profiles/itq_wide_codes.txt: 512 .. 4096 elements, 512 and 1024 bits, float32 and float64 rows): 3.7 to 5.7 times
+ * the float64 kernel's speed at every shape, so the bit range has no exception by width.
  * Everything else -- other normalize orders, option "itq_exact", fewer than 32 rows, rows that are no whole number of
- * 16-byte pieces (50 float32 elements), unaligned pointers, wider codes -- is hashed by the all-float64 kernel. */
+ * 16-byte pieces (50 float32 elements), unaligned pointers, codes beyond 1024 bits -- is hashed by the all-float64
+ * kernel. */
 int sq_itq_hash(const void* x, int x_dtype, int64_t n, int d,
                 const double* mean, int mean_dtype, const double* rotation, int bits, int norm_ord,
                 uint64_t* out_codes, int mem, void* stream);
@@ -330,15 +336,20 @@ int sq_dense_distances(const void* query, const void* rows, int dtype, int64_t n
  * batches through pinned staging).  What ItqFunctor.get_hash costs per query vector in
  * LSHNearestNeighborIndex._nn (impls/nn_index/lsh.py:473): without this every call re-uploads the rotation.
  * The rows go through the filters of sq_itq_hash, by the same rule.  Where that is the slab ("extra-wide") filter --
- * more than 512 elements, or a width that is no multiple of 64 -- the model keeps that filter's image of the rotation
- * from the first such call on.
+ * more than 512 elements, a width that is no multiple of 64, or a code of 257 .. 1024 bits -- the model keeps that
+ * filter's image of the rotation, its float64 columns and the per-column error terms, of all column groups, from the
+ * first such call on (32 MB + 64 MB at 8192 elements x 1024 bits).  If that allocation fails the call answers
+ * SQ_ERR_NOMEM and nothing is kept; the model stays usable (option "itq_exact" on the handle hashes with the float64
+ * kernel, which needs no image).
  * sq_get_stats on a model handle describes the last sq_itq_model_hash, in the fields of sq_stats_t:
- *   scan_launches     filter kernels that streamed the rows (0: the float64 kernel hashed them)
+ *   scan_launches     filter passes over the rows (0: the float64 kernel hashed them): 1 for codes up to 256 bits; the
+ *                     slab filter beyond 256 bits is launched once per column group of 256 bits -- ceil(words / 4)
  *   candidates        bits the filter left undecided, evaluated in float64 (-1 after a SQ_MEM_DEVICE call, which is
  *                     asynchronous: the device counter is not read back)
  *   fallback_queries  rows hashed by the float64 kernel (all n with option "itq_exact", for fewer than 32 rows, for
  *                     shapes no filter takes)
- *   bytes_scanned     n * d * sizeof(element)
+ *   bytes_scanned     n * d * sizeof(element) per filter pass: times ceil(words / 4) for codes of 257 .. 1024 bits (the
+ *                     rows are streamed once per column group), times 1 otherwise (the float64 kernel included)
  * the other fields are 0. */
 int sq_itq_model_create(const double* mean, int mean_dtype, const double* rotation, int d, int bits,
                         int norm_ord, sq_handle_t* out);

@@ -342,10 +342,17 @@ class ItqModel(_Handle):
                    "sq_itq_model_hash")
         return out
 
+    def hash_device(self, x_ptr: int, x_dtype: int, n: int, out_ptr: int, stream: int = 0) -> None:
+        """Device pointers: ``n`` rows of ``x_dtype`` (``SQ_DTYPE_F32`` / ``SQ_DTYPE_F64``), 16-byte aligned for the
+        filters, codes to ``uint64[n, ceil(bits/64)]`` at ``out_ptr``; enqueued on ``stream``, not synchronised."""
+        _check(load().sq_itq_model_hash(self.handle, _ptr(x_ptr), int(x_dtype), int(n), _ptr(out_ptr), SQ_MEM_DEVICE,
+                                        ctypes.c_void_p(stream or None)), "sq_itq_model_hash")
+
     def stats(self) -> dict:
-        """Which path the last ``hash`` took (``sq_get_stats`` on a model handle): ``scan_launches`` filter kernels
-        that streamed the rows (0: the float64 kernel hashed them), ``candidates`` bits the filter left to float64,
-        ``fallback_queries`` rows hashed by the float64 kernel, ``bytes_scanned`` = n * d * itemsize."""
+        """Which path the last ``hash`` took (``sq_get_stats`` on a model handle): ``scan_launches`` filter passes
+        over the rows (0: the float64 kernel hashed them; codes of 257 .. 1024 bits: one pass per 256 bits),
+        ``candidates`` bits the filter left to float64 (-1 after ``hash_device``), ``fallback_queries`` rows hashed by
+        the float64 kernel, ``bytes_scanned`` = n * d * itemsize per pass."""
         return get_stats(self.handle)
 
 

@@ -527,12 +527,12 @@ static __global__ __launch_bounds__(256) void itq_count_undecided_kernel(const u
 
 // What a resident model (sq_itq_model_*) hands to a launch: where the statistics of the call go, and a home for the
 // extra-wide filter's image of R, which depends on the model alone (8 MB of float16 planes plus 16 MB of float64
-// columns at 8192 x 256 bits: built once per model, not once per call).  The one-shot sq_itq_hash passes none.
+// columns at 8192 x 256 bits, 32 MB + 64 MB at 8192 x 1024 bits: built once per model, not once per call).  The one-shot sq_itq_hash passes none.
 struct ItqCallCtx {
     DevBuf* prep = nullptr;        // the model part of the extra-wide filter's scratch
     bool* prep_valid = nullptr;
     unsigned long long* cand_dev = nullptr;   // device counter: bits left to float64 (zeroed by the caller)
-    long long filter_launches = 0;            // filter kernels that streamed the rows
+    long long filter_launches = 0;            // filter kernels that streamed the rows (the slab filter beyond 256 bits: one per column group)
     long long fallback_rows = 0;              // rows hashed by the float64 kernel
 };
 
@@ -726,25 +726,27 @@ namespace sq {
 
 // Which certified filter hashes a shape: a pure function of (element size, d, words of the code).  The rule: a float32
 // or float64 descriptor of up to 8192 elements whose row is a whole number of 16-byte pieces (float32: d % 4 == 0,
-// float64: d % 2 == 0), codes up to 256 bits, is hashed by a certified filter --
+// float64: d % 2 == 0), codes up to 1024 bits, is hashed by a certified filter --
 //   d % 64 == 0, d <= 256, float32, <= 128 bits   the narrow kernel (sq_itq_fast.hpp, whole 256-byte row units)
-//   d % 64 == 0, d <= 512, otherwise              the wide kernel   (sq_itq_wide.hpp, whole 256-byte row units)
-//   every other d <= 8192                         the slab kernel   (sq_itq_xwide.hpp, 16-byte pieces guarded by k < d)
-// and everything else by the float64 kernel.  What a call adds (itq_launch): at least 32 rows, a 16-byte aligned
+//   d % 64 == 0, d <= 512, <= 256 bits otherwise  the wide kernel   (sq_itq_wide.hpp, whole 256-byte row units)
+//   every other d <= 8192 up to 256 bits, and
+//   every d <= 8192 at 257 .. 1024 bits           the slab kernel   (sq_itq_xwide.hpp, 16-byte pieces guarded by k < d;
+//                                                 beyond 256 bits one pass over the rows per 256 bits of the code)
+// and everything else (codes beyond 1024 bits among it) by the float64 kernel.  What a call adds (itq_launch): at least 32 rows, a 16-byte aligned
 // pointer, normalize None or 2, option itq_exact off -- otherwise the float64 kernel as well.
 // (measured, profiles/itq_any_width.txt: the slab kernel at d = 100 / 300 / 500 against the float64 kernel and against
-// the unit kernels on rows zero-padded to the next multiple of 64)
+// the unit kernels on rows zero-padded to the next multiple of 64; profiles/itq_wide_codes.txt: 512 and 1024 bits)
 enum ItqRoute { ITQ_ROUTE_F64 = 0, ITQ_ROUTE_NARROW, ITQ_ROUTE_WIDE, ITQ_ROUTE_XWIDE };
 static ItqRoute itq_filter_route(size_t esz, int d, int words) {
-    if (d < 1 || d > ITQX_MAX_D || words > 4 || ((size_t)d * esz) % 16 != 0) return ITQ_ROUTE_F64;
-    if (d % 64 == 0 && d <= 512) return esz == 4 && itq_fast_geometry(d, words).stages >= 2 ? ITQ_ROUTE_NARROW : ITQ_ROUTE_WIDE;
+    if (d < 1 || d > ITQX_MAX_D || words > ITQX_MAX_WORDS || ((size_t)d * esz) % 16 != 0) return ITQ_ROUTE_F64;
+    if (d % 64 == 0 && d <= 512 && words <= 4) return esz == 4 && itq_fast_geometry(d, words).stages >= 2 ? ITQ_ROUTE_NARROW : ITQ_ROUTE_WIDE;
     return ITQ_ROUTE_XWIDE;
 }
 
 // The extra-wide filter (sq_itq_xwide.hpp): d <= 8192, float32 or float64 rows of whole 16-byte pieces.
 template <class T>
 static bool itq_xwide_applies(const ItqArgs& a) {
-    return a.d >= 1 && a.d <= ITQX_MAX_D && a.words <= 4 && a.n >= 32 && a.n < (1ll << 29) &&
+    return a.d >= 1 && a.d <= ITQX_MAX_D && a.words <= ITQX_MAX_WORDS && a.n >= 32 && a.n < (1ll << 29) &&
            (reinterpret_cast<uintptr_t>(a.x) & 15u) == 0 && ((size_t)a.d * sizeof(T)) % 16 == 0 && !a.exact &&
            (a.norm == SQ_NORM_NONE || a.norm == SQ_NORM_L2);
 }
@@ -755,19 +757,42 @@ static int itq_xwide_launch_t(const ItqXwideArgs& xa, int nrb, hipStream_t st) {
     return launch_lds<itq_xwide_kernel<T, NORMED, CT>>(160 * 1024, dim3((unsigned)nrb), dim3(ITQX_WAVES * 64), lds, st, xa);
 }
 
+// Codes of 257 .. 1024 bits run in column groups of at most ITQX_GROUP_CT column tiles (256 bits, 4 code words): one
+// filter pass over the rows per group (sq_itq_xwide.hpp, "Codes beyond 256 bits").  The passes are launched one
+// after the other on the call's stream, each followed by the float64 evaluation of its own undecided bits, so ONE
+// segment array serves every group: the stream orders pass g + 1 behind the fix kernel of pass g.
+struct ItqXwideGroupGeom {
+    int ct, nrb;
+    long long nwaves, seg_cap;
+};
+static ItqXwideGroupGeom itq_xwide_group_geometry(int ct, long long n_tiles, int device) {
+    ItqXwideGroupGeom g{};
+    g.ct = ct;
+    g.nrb = cu_count(device) * (ct <= 2 ? 2 : 1);   // (two workgroups per CU fit 256 registers only with two column tiles)
+    if ((long long)g.nrb * ITQX_WAVES > n_tiles) g.nrb = (int)((n_tiles + ITQX_WAVES - 1) / ITQX_WAVES);
+    g.nwaves = (long long)g.nrb * ITQX_WAVES;
+    const long long rounds = (n_tiles + g.nwaves - 1) / g.nwaves;
+    g.seg_cap = rounds * 32 * ct;   // every (row, column tile) of a wave's tiles
+    return g;
+}
+
 template <class T>
 static int itq_xwide_path(const ItqArgs& a, hipStream_t st, int device, ItqCallCtx* ctx) {
     const int pc = a.words * 64, ct = a.words * 2;
+    const int groups = (ct + ITQX_GROUP_CT - 1) / ITQX_GROUP_CT;
     const bool l2 = a.norm == SQ_NORM_L2;
     const long long n_tiles = (a.n + 31) / 32;
-    int nrb = cu_count(device) * (ct <= 2 ? 2 : 1);   // (two workgroups per CU fit 256 registers only with two column tiles)
-    if ((long long)nrb * ITQX_WAVES > n_tiles) nrb = (int)((n_tiles + ITQX_WAVES - 1) / ITQX_WAVES);
-    const long long nwaves = (long long)nrb * ITQX_WAVES;
-    const long long rounds = (n_tiles + nwaves - 1) / nwaves;
-    const long long seg_cap = rounds * 32 * ct;   // every (row, column tile) of a wave's tiles
+    // the segment array and its counts hold the largest group's (a last group of two column tiles runs twice the waves)
+    size_t seg_bytes = 0, cnt_bytes = 0;
+    for (int g = 0; g < groups; ++g) {
+        const ItqXwideGroupGeom gg = itq_xwide_group_geometry(std::min(ITQX_GROUP_CT, ct - g * ITQX_GROUP_CT), n_tiles, device);
+        seg_bytes = std::max(seg_bytes, (size_t)(gg.nwaves * gg.seg_cap * 8));
+        cnt_bytes = std::max(cnt_bytes, (size_t)gg.nwaves * 4);
+    }
     const int dp = (a.d + 127) / 128 * 128;
     const size_t img_bytes = (size_t)pc * dp * 4;
-    // the model part: colnorm | c_b | c_b error | cabs | slab image | R^T float64
+    const size_t group_img_bytes = (size_t)ITQX_GROUP_CT * 32 * dp * 4;   // a full group's slice of either image
+    // the model part: colnorm | c_b | c_b error | cabs | slab image, group after group | R^T float64
     size_t moff = 0;
     auto mtake = [&](size_t bytes) {
         const size_t at = moff;
@@ -785,13 +810,13 @@ static int itq_xwide_path(const ItqArgs& a, hipStream_t st, int device, ItqCallC
         coff += align256(bytes);
         return at;
     };
-    const size_t o_seg = ctake((size_t)nwaves * seg_cap * 8), o_cnt = ctake((size_t)nwaves * 4);
+    const size_t o_seg = ctake(seg_bytes), o_cnt = ctake(cnt_bytes);
     const size_t o_img = cached ? 0 : ctake(img_bytes);
     const size_t o_model = keep ? 0 : ctake(moff);
     unsigned char* cbase = nullptr;
     unsigned char* mbase = nullptr;
     if (keep) {
-        SQ_TRY(ctx->prep->reserve(moff));
+        SQ_TRY(ctx->prep->reserve(moff));   // (SQ_ERR_NOMEM: nothing is kept, the model stays usable)
         mbase = ctx->prep->as<unsigned char>();
     }
     SQ_HIP(scratch_alloc(reinterpret_cast<void**>(&cbase), coff, st, device));
@@ -804,7 +829,7 @@ static int itq_xwide_path(const ItqArgs& a, hipStream_t st, int device, ItqCallC
     if (!cached) {
         // relative error of x . R_b per unit |x||R_b| (sq_itq_xwide.hpp): the split, the dropped x_lo R_lo, the float32
         // accumulation flushed per 64-k slab (192 products each, then ceil(d / 64) additions), the float32 scale /
-        // subtract [+ 2^-18: |x|^2, normalize=2]
+        // subtract [+ 2^-18: |x|^2, normalize=2].  Per column: the same for every column group.
         const double u24 = 5.9604644775390625e-08;
         const int nslab = (a.d + ITQX_SLAB_K - 1) / ITQX_SLAB_K;
         const double eps_rel = ((9.5367431640625e-07 + 4.76837158203125e-07) * 1.001 +
@@ -816,47 +841,59 @@ static int itq_xwide_path(const ItqArgs& a, hipStream_t st, int device, ItqCallC
                                           reinterpret_cast<float*>(mbase + o_cb), reinterpret_cast<float*>(mbase + o_cbe),
                                           reinterpret_cast<double*>(mbase + o_rt), eps_rel, reinterpret_cast<float*>(mbase + o_cabs));
         if (rc != SQ_OK) return done(rc);
-        const long long chunks = (long long)(img_bytes / 16);
-        rc = launch<itq_xwide_relayout_kernel>(dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, st,
-                                               reinterpret_cast<const uint4*>(cbase + o_img), reinterpret_cast<uint4*>(mbase + o_ximg), dp, ct, chunks);
-        if (rc != SQ_OK) return done(rc);
+        // prep's image is [column][plane][dp]: a group's columns are one contiguous slice of it, and of the slab image
+        // (a group starts at a multiple of 256 columns, so prep's swizzle by column & 15 reads the same inside the slice)
+        for (int g = 0; g < groups; ++g) {
+            const int ctg = std::min(ITQX_GROUP_CT, ct - g * ITQX_GROUP_CT);
+            const long long chunks = (long long)ctg * 32 * dp * 4 / 16;
+            rc = launch<itq_xwide_relayout_kernel>(dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, st,
+                                                   reinterpret_cast<const uint4*>(cbase + o_img + (size_t)g * group_img_bytes),
+                                                   reinterpret_cast<uint4*>(mbase + o_ximg + (size_t)g * group_img_bytes), dp, ctg, chunks);
+            if (rc != SQ_OK) return done(rc);
+        }
         if (keep) *ctx->prep_valid = true;
     }
-    ItqXwideArgs xa{};
-    xa.x = a.x;
-    xa.n = a.n;
-    xa.d = a.d;
-    xa.ximage = reinterpret_cast<const uint4*>(mbase + o_ximg);
-    xa.colnorm = reinterpret_cast<const float*>(mbase + o_cn);
-    xa.cb32 = reinterpret_cast<const float*>(mbase + o_cb);
-    xa.cberr = reinterpret_cast<const float*>(mbase + o_cbe);
-    xa.cabs = reinterpret_cast<const float*>(mbase + o_cabs);
-    xa.out = a.out;
-    xa.words = a.words;
-    xa.pad = a.pad;
-    xa.bits = a.bits;
-    xa.seg = reinterpret_cast<u64*>(cbase + o_seg);
-    xa.seg_cnt = reinterpret_cast<u32*>(cbase + o_cnt);
-    xa.seg_cap = seg_cap;
-    xa.n_tiles = n_tiles;
-    xa.nslab = (a.d + ITQX_SLAB_K - 1) / ITQX_SLAB_K;
+    for (int g = 0; g < groups; ++g) {
+        const int col0 = g * ITQX_GROUP_CT * 32;   // first padded column of the group
+        const ItqXwideGroupGeom gg = itq_xwide_group_geometry(std::min(ITQX_GROUP_CT, ct - g * ITQX_GROUP_CT), n_tiles, device);
+        ItqXwideArgs xa{};
+        xa.x = a.x;
+        xa.n = a.n;
+        xa.d = a.d;
+        xa.ximage = reinterpret_cast<const uint4*>(mbase + o_ximg + (size_t)g * group_img_bytes);
+        xa.colnorm = reinterpret_cast<const float*>(mbase + o_cn) + col0;
+        xa.cb32 = reinterpret_cast<const float*>(mbase + o_cb) + col0;
+        xa.cberr = reinterpret_cast<const float*>(mbase + o_cbe) + col0;
+        xa.cabs = reinterpret_cast<const float*>(mbase + o_cabs) + col0;
+        xa.out = a.out;
+        xa.words = a.words;
+        xa.word0 = col0 / 64;
+        xa.pad = g == 0 ? a.pad : 0;   // (pad < 64: the leading zero columns lie in the first word, hence in group 0)
+        xa.bits = a.bits;
+        xa.seg = reinterpret_cast<u64*>(cbase + o_seg);
+        xa.seg_cnt = reinterpret_cast<u32*>(cbase + o_cnt);
+        xa.seg_cap = gg.seg_cap;
+        xa.n_tiles = n_tiles;
+        xa.nslab = (a.d + ITQX_SLAB_K - 1) / ITQX_SLAB_K;
 #define SQ_ITQX_CASE(CTv)                                                                              \
     case CTv:                                                                                          \
-        rc = l2 ? itq_xwide_launch_t<T, true, CTv>(xa, nrb, st) : itq_xwide_launch_t<T, false, CTv>(xa, nrb, st); \
+        rc = l2 ? itq_xwide_launch_t<T, true, CTv>(xa, gg.nrb, st) : itq_xwide_launch_t<T, false, CTv>(xa, gg.nrb, st); \
         break;
-    switch (ct) {
-        SQ_ITQX_CASE(2)
-        SQ_ITQX_CASE(4)
-        SQ_ITQX_CASE(6)
-        default:
-        SQ_ITQX_CASE(8)
-    }
+        switch (gg.ct) {
+            SQ_ITQX_CASE(2)
+            SQ_ITQX_CASE(4)
+            SQ_ITQX_CASE(6)
+            default:
+            SQ_ITQX_CASE(8)
+        }
 #undef SQ_ITQX_CASE
-    if (rc != SQ_OK) return done(rc);
-    rc = launch<itq_fix_bits_xwide_kernel<T>>(dim3((unsigned)nwaves, ITQ_FIX_PARTS), dim3(256), 0, st, a, xa.seg, xa.seg_cnt, seg_cap,
-                                              reinterpret_cast<const double*>(mbase + o_rt));
-    if (rc == SQ_OK) rc = itq_count_undecided(ctx, xa.seg, xa.seg_cnt, seg_cap, nwaves, st);
-    return done(rc);
+        if (rc != SQ_OK) return done(rc);
+        rc = launch<itq_fix_bits_xwide_kernel<T>>(dim3((unsigned)gg.nwaves, ITQ_FIX_PARTS), dim3(256), 0, st, a, xa.seg, xa.seg_cnt,
+                                                  gg.seg_cap, reinterpret_cast<const double*>(mbase + o_rt), col0);
+        if (rc == SQ_OK) rc = itq_count_undecided(ctx, xa.seg, xa.seg_cnt, gg.seg_cap, gg.nwaves, st);
+        if (rc != SQ_OK) return done(rc);
+    }
+    return done(SQ_OK);
 }
 
 template <class T>
@@ -1041,7 +1078,8 @@ extern "C" int sq_itq_model_hash(sq_handle_t hid, const void* x, int x_dtype, in
         h->stats.scan_launches = ctx.filter_launches;
         h->stats.fallback_queries = ctx.fallback_rows;
         h->stats.candidates = candidates;
-        h->stats.bytes_scanned = (int64_t)((size_t)n * h->d * esz);
+        // (the rows are streamed once per filter pass: the slab filter's column groups beyond 256 bits)
+        h->stats.bytes_scanned = (int64_t)((size_t)n * h->d * esz * (size_t)std::max<long long>(1, ctx.filter_launches));
     };
     if (mem == SQ_MEM_DEVICE) {
         a.x = x;

@@ -1,7 +1,8 @@
 // The certified float16 filter of ItqFunctor.get_hash for descriptors of 513 .. 8192 elements (the reference's own
 // examples hash 2048-d and 4096-d CNN descriptors) and for every width of 1 .. 512 that is no multiple of 64 (100-,
-// 200-, 300-d descriptors: itq_filter_route, sq_itq.hip), codes up to 256 bits, float32 or float64 rows of whole
-// 16-byte pieces, normalize None / 2.
+// 200-, 300-d descriptors: itq_filter_route, sq_itq.hip), codes up to 256 bits in one pass over the rows -- and for
+// every width up to 8192 at 257 .. 1024 bits, one pass per 256 bits ("Codes beyond 256 bits" below) --, float32 or
+// float64 rows of whole 16-byte pieces, normalize None / 2.
 // sq_itq_wide.hpp keeps a 32-row tile's fragments resident (d/2 registers per lane: 256 at d = 512) and streams R past
 // them; that does not stretch.  Here BOTH operands are blocked over k, in slabs of 64:
 //
@@ -45,6 +46,17 @@
 // An element of an MFMA result depends on its own row of A and column of B only, so each such z_b is the float64
 // kernel's z_b to the last bit, whatever cancels in it (rows that lie in the span of a few rotation columns leave
 // z_b of the order of the rounding error of the sum: a different summation order would flip those signs).
+//
+// Codes beyond 256 bits (5 .. 16 words).  A wave cannot own more than 8 column tiles of accumulators (256 registers),
+// so the columns run in groups of ITQX_GROUP_CT tiles: group g is words 4 g .. 4 g + 3 of the code, the last group the
+// remaining 1 .. 4 words (the CT = 2 / 4 / 6 / 8 instantiations).  One launch per group (itq_xwide_path, sq_itq.hip):
+// the kernel is the one above, handed the group's slice of the slab image (each slice is laid out
+// [slab][column tile][plane][k-step][lane] by itself) and of colnorm / cb32 / cberr / cabs, `word0` = 4 g as the word of
+// out[n][words] its first column tile belongs to, and the right-alignment pad in group 0 only (pad < 64).  The error
+// terms are per column, so the bound above holds unchanged.  The undecided entries keep their format -- the 3-bit tile
+// field is local to the group, n < 2^29 stays the limit --: each group's entries are evaluated by a launch of
+// itq_fix_bits_xwide_kernel with the group's first column (`col0`) before the next group's pass overwrites the
+// segments.  The rows are read once per group: see DESIGN.md for where that binds (many bits over narrow rows).
 #pragma once
 #include "sq_itq_fast.hpp"
 
@@ -53,6 +65,8 @@ namespace sq {
 static constexpr int ITQX_WAVES = 4;
 static constexpr int ITQX_SLAB_K = 64;          // k per slab: 4 MFMA k-steps, one 256-byte unit of a float32 row
 static constexpr int ITQX_MAX_D = 8192;   // (no lower limit: sq_itq.hip routes d <= 512, d % 64 != 0 here too)
+static constexpr int ITQX_GROUP_CT = 8;   // column tiles of one pass over the rows: 256 bits, 4 code words
+static constexpr int ITQX_MAX_WORDS = 16; // 1024 bits: four such passes
 
 struct ItqXwideArgs {
     const void* x;         // [n][d] rows of T, 16-byte aligned rows
@@ -64,7 +78,8 @@ struct ItqXwideArgs {
     const float* cb32;
     const float* cberr;
     u64* out;              // [n][words]
-    int words, pad, bits;
+    int words, pad, bits;  // words: of the whole code (the row stride of out); pad: leading zero columns of THIS launch's columns
+    int word0;             // first code word of this launch's column group (4 g: see "Codes beyond 256 bits" above)
     u64* seg;              // [waves of the launch][seg_cap] undecided entries: (row | column tile << 29) << 32 | 32-column mask
     u32* seg_cnt;
     long long seg_cap;
@@ -309,7 +324,7 @@ __global__ __launch_bounds__(ITQX_WAVES * 64, CT <= 2 ? 2 : 1) void itq_xwide_ke
             } else if (mine) {
                 u64 v = ((u64)word_hi << 32) | (u64)bits;
                 if ((ct >> 1) == 0 && a.pad > 0) v &= (~0ull) >> a.pad;
-                a.out[row * a.words + (ct >> 1)] = v;
+                a.out[row * a.words + a.word0 + (ct >> 1)] = v;
             }
             {
                 const bool need = mine && unc != 0;
@@ -330,10 +345,11 @@ __global__ __launch_bounds__(ITQX_WAVES * 64, CT <= 2 ? 2 : 1) void itq_xwide_ke
 // lane (i = lane & 15, g = lane >> 4) feeds entry i's v[c + 4 g + j] as A and R[c + 4 g + j][column of entry i] as B
 // to the j-th v_mfma_f64_16x16x4_f64 of 16-k step c, in itq_hash_kernel's order; element (i, i) of the result is
 // register i >> 2 of lane (i, g = i & 3).  v = x / |x| (x's dtype, numpy's norm) minus the mean in the promoted dtype.
+// col0: the first padded column of the column group the entries come from (0 for codes up to 256 bits).
 template <class T>
 static __global__ __launch_bounds__(256) void itq_fix_bits_xwide_kernel(ItqArgs a, const u64* __restrict__ seg,
                                                                          const u32* __restrict__ seg_cnt, long long seg_cap,
-                                                                         const double* __restrict__ rt64) {
+                                                                         const double* __restrict__ rt64, int col0) {
     const long long w = blockIdx.x;
     const long long cnt_raw = seg_cnt[w];
     const u32 cnt = (u32)(cnt_raw < seg_cap ? cnt_raw : seg_cap);
@@ -365,7 +381,7 @@ static __global__ __launch_bounds__(256) void itq_fix_bits_xwide_kernel(ItqArgs 
         }
         while (__ballot(mask != 0u) != 0ull) {   // nearly always one pass
             const bool live = mask != 0u;
-            const int pc = ct * 32 + (live ? __ffs((int)mask) - 1 : 0);   // padded column; the filter only flags pc >= pad
+            const int pc = col0 + ct * 32 + (live ? __ffs((int)mask) - 1 : 0);   // padded column of the whole code (col0: the entries' column group); the filter only flags pc >= pad
             mask &= mask - 1u;
             const double* rcol = rt64 + (long long)pc * a.d;   // column pc of R, contiguous (itq_fast_prep_kernel)
             f64x4 acc = f64x4{0.0, 0.0, 0.0, 0.0};

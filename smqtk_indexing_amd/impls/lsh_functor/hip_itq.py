@@ -231,7 +231,9 @@ class HipItqFunctor(LshFunctor):
         (bool ``[n, bits]``, computed on the GPU).  With ``fit_on_device`` (default) the products
         over the n descriptors run on the device when they fit its kernels (d <= 8192, <= 256 bits: the library's
         ``SQ_ITQFIT_MAX_D`` / ``SQ_ITQFIT_MAX_BITS``,
-        a real-valued PCA basis); otherwise, and always for the small dense linear algebra, numpy."""
+        a real-valued PCA basis); otherwise, and always for the small dense linear algebra, numpy.  A ``bit_length``
+        beyond 256 therefore trains with numpy; hashing the training set at the end goes through the device's
+        certified filter all the same (codes up to 1024 bits, see ``sq_itq_hash`` in include/smqtk_hip.h)."""
         if self.has_model():
             raise RuntimeError("Model components have already been loaded.")
         descr = descriptors if isinstance(descriptors, (list, tuple)) else list(descriptors)
