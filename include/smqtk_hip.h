@@ -53,6 +53,8 @@ extern "C" {
 #define SQ_MEM_HOST 0
 #define SQ_MEM_DEVICE 1
 #define SQ_MEM_DEVICE_ASYNC 2 /* sq_dense_search / sq_hamming_search: enqueue and return, results final one call later */
+#define SQ_MEM_PLAN 3         /* sq_hamming_search: search nothing, report what a blocking call of this shape would do */
+#define SQ_MEM_PLAN_ASYNC 4   /* sq_hamming_search: the same for a SQ_MEM_DEVICE_ASYNC call */
 
 #define SQ_METRIC_L2 0     /* utils/metrics.py:73-86 euclidean_distance */
 #define SQ_METRIC_COSINE 1 /* utils/metrics.py:89-137 cosine_distance (pos_vectors=True) */
@@ -191,12 +193,34 @@ int sq_hamming_search(sq_handle_t h, const uint64_t* queries, int nq, int k,
  * stay valid and untouched.  Options "hamming_async_depth" (2 .. 4), "hamming_async_wait", "hamming_async_order" as
  * their dense_* counterparts.  The shards of BASELINE config 5 (125 M x 256-bit codes per GPU) pipeline their
  * histogram / threshold / compaction / select kernels under the neighbouring calls' scans this way.
- * Calls of up to 32 queries over 64 .. 256-bit codes (k <= 2048) run as three launches -- sampled histogram, stream with
+ * Which path a code width takes (mem = SQ_MEM_PLAN reports it for a given call, below):
+ *   1 .. 16 words (64 .. 1024 bits, every multiple of 64): the register stream into per-workgroup mini-lists, no
+ *       global atomics; the all-keys scan and the sampled histogram are specialised for the same widths.
+ *   1 .. 7 words: also the three-launch call below, and the LDS-DMA ring -- automatically for up to 24 queries over
+ *       at least 256 MB of codes, or forced with option "hamming_ring" = 1 (0 = never); the ring needs a 16-byte
+ *       aligned code array.
+ *   8 and 16 words: the ring automatically for up to 64 queries (or forced), the register stream otherwise; no
+ *       three-launch call.      9 .. 15 words: the register stream only.
+ *   17 .. 64 words: one code per thread, survivors through global atomic counters.
+ * Calls of up to 32 queries over 64 .. 448-bit codes (k <= 2048) run as three launches -- sampled histogram, stream with
  * the thresholds computed in its prologue, one pick kernel per query (option "hamming_fused", 1 by default; 0 = the general
- * chain of five).  Their stream threshold is taken at a lower sample rank than k ("hamming_tighten", 1 by default): a bet
+ * chain of five); larger batches, up to one stream launch's queries, keep a threshold launch between the first two.  Their stream threshold is taken at a lower sample rank than k ("hamming_tighten", 1 by default): a bet
  * the pick kernel checks -- a call whose threshold admitted fewer than k codes is redone with the safe rule (counted in
  * sq_stats_t.fallback_queries); results are integer-exact either way. */
 int sq_hamming_sync(sq_handle_t h);
+/* The read-only view of the plan, "sq_hamming_plan": sq_hamming_search with mem = SQ_MEM_PLAN (a blocking call) or
+ * SQ_MEM_PLAN_ASYNC (a pipelined one) searches nothing and writes to out_idx what a search of `nq` queries and `k`
+ * results would do on this handle under its current options, without touching the device: the routing of
+ * LinearHashIndex._nn's replacement (impls/hash_index/linear.py:206-244) made visible.  `queries`, `out_dist` and `stream`
+ * are ignored (may be NULL); errors read "sq_hamming_plan: ...".  It is a mode of the search call, not an entry point
+ * of its own, because the set of exported symbols is pinned.  out_idx[SQ_HAMMING_PLAN_FIELDS]:
+ *   [0] chain      0 = all-keys scan (n <= candidate cap), 1 = general chain, 2 = three launches
+ *   [1] stream     0 = none of the two below (the all-keys scan, or beyond 1024 bits the one-kernel scan with global
+ *                  atomic counters), 1 = register stream into mini-lists, 2 = LDS-DMA ring into mini-lists
+ *   [2] 1 = the stream computes the thresholds in its prologue (hamming_body_kernel)
+ *   [3] workgroups of the stream   [4] slots per mini-list   [5] sample step (every step-th block of codes)
+ *   [6] candidate cap per query    [7] queries per stream launch */
+#define SQ_HAMMING_PLAN_FIELDS 8
 /* Incremental mutation of an index that owns its device copy (created from host memory, or from a device array of
  * at least 4096 codes, which is copied): what LinearHashIndex._update_index / _remove_from_index do with a set
  * union / difference (impls/hash_index/linear.py:167-204), without re-uploading the whole code array.  Row ids are

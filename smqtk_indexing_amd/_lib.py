@@ -21,6 +21,8 @@ SQ_OK = 0
 SQ_MEM_HOST = 0
 SQ_MEM_DEVICE = 1
 SQ_MEM_DEVICE_ASYNC = 2
+SQ_MEM_PLAN = 3             # sq_hamming_search: report the plan of a blocking call instead of searching
+SQ_MEM_PLAN_ASYNC = 4       # ... of a SQ_MEM_DEVICE_ASYNC call
 SQ_METRIC_L2 = 0
 SQ_METRIC_COSINE = 1
 SQ_DTYPE_F32 = 0
@@ -34,6 +36,7 @@ SQ_NORM_NEG_INF = -1000
 SQ_MAX_K = 16384
 SQ_ITQFIT_MAX_D = 8192      # sq_itqfit_*: widest descriptor / longest code the device fit takes (smqtk_hip.h)
 SQ_ITQFIT_MAX_BITS = 256
+SQ_HAMMING_PLAN_FIELDS = 8  # words of the plan report of sq_hamming_search (smqtk_hip.h)
 
 LIB_NAME = "libsmqtk_hip.so"
 # SMQTK_HIP_LIBRARY: another build of the same library (measurement: kernel variants side by side)
@@ -424,6 +427,18 @@ class HammingIndex(_Handle):
         _check(load().sq_hamming_search(self.handle, _ptr(q_ptr), int(nq), int(k), _ptr(out_dist_ptr),
                                         _ptr(out_idx_ptr), SQ_MEM_DEVICE_ASYNC, ctypes.c_void_p(stream or None)),
                "sq_hamming_search")
+
+    PLAN_FIELDS = ("chain", "stream", "thresholds_in_stream", "workgroups", "slots", "sample_step", "candidate_cap",
+                   "queries_per_launch")
+
+    def plan(self, nq: int, k: int, async_: bool = False) -> dict:
+        """The plan mode of ``sq_hamming_search`` (``SQ_MEM_PLAN``): what a search of ``nq`` queries and ``k`` results would do under the handle's current
+        options, nothing touched on the device.  ``chain``: 0 all-keys, 1 general, 2 three launches; ``stream``: 0 no
+        mini-list stream (all-keys scan, or the atomic scan beyond 1024 bits), 1 register stream, 2 LDS-DMA ring."""
+        out = (ctypes.c_int64 * SQ_HAMMING_PLAN_FIELDS)()
+        mem = SQ_MEM_PLAN_ASYNC if async_ else SQ_MEM_PLAN
+        _check(load().sq_hamming_search(self.handle, None, int(nq), int(k), None, out, mem, None), "sq_hamming_plan")
+        return dict(zip(self.PLAN_FIELDS, (int(v) for v in out)))
 
     def sync(self) -> None:
         """Finish every asynchronous search in flight (``sq_hamming_sync``)."""

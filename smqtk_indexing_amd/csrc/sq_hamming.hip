@@ -103,6 +103,18 @@ struct HammingHandle : HandleBase {
     }
 };
 
+// ------------------------------------------------------------------ per-width shapes of the register kernels
+// Codes per thread: a thread of the scan / histogram kernels holds 4 / W codes of W words (at least one), one of the
+// stream / body kernels 8 / W (at least one) -- twice over, because the next chunk is prefetched.  The stream kernel
+// takes the queries out of LDS `stream_queries(W)` at a time: 32 / W, between 1 and 8, so that the query words of a
+// group never outgrow the code words by much.  One rule per quantity for every width of 1 .. 16 words; the template
+// arguments and the host's block arithmetic both come from here.  DESIGN.md section 4.3 has the registers and the
+// occupancy each instantiation ends up with.
+constexpr int scan_codes(int W) { return W >= 4 ? 1 : 4 / W; }
+constexpr int stream_codes(int W) { return W >= 8 ? 1 : 8 / W; }
+constexpr int stream_queries(int W) { return W <= 4 ? 8 : 32 / W; }
+static constexpr int HS_MAX_WORDS = 16;   // widest code with register kernels (1024 bits)
+
 // ------------------------------------------------------------------ kernels
 // The host index keeps its codes SORTED (row id = rank of the code, which is what makes
 // (distance, row) the canonical (distance, code value) order).  In sorted order the codes near a
@@ -242,7 +254,7 @@ __global__ __launch_bounds__(256) void hamming_stream_kernel(const u64* __restri
                                                               const u64* __restrict__ qs, int nq,
                                                               const int* __restrict__ thr, u64* __restrict__ seg,
                                                               u32* __restrict__ bcnt, u32 S) {
-    constexpr int QG = 8;
+    constexpr int QG = stream_queries(W);
     extern __shared__ __attribute__((aligned(16))) unsigned char hsm[];
     u64* lq = reinterpret_cast<u64*>(hsm);                       // [nq][W]
     int* lthr = reinterpret_cast<int*>(lq + (size_t)nq * W);     // [nq]
@@ -327,23 +339,39 @@ __global__ __launch_bounds__(256) void hamming_stream_kernel(const u64* __restri
 // in-order queue as the DMA pieces: a counted wait then waits for a little more than it must (never for less).
 // Code widths 64 .. 1024 bits in powers of two; the array must be 16-byte aligned.  The last partial unit is read by
 // one wave with guarded register loads after its ring has drained.
+// 192, 320, 384 and 448 bits (W = 3, 5, 6, 7): 8 KiB hold no whole number of such codes, so a unit is W KiB -- 128 codes
+// in W DMA pieces, still lane-linear, the LDS image still the global image; eight waves' rings of two units take
+// 16 W KiB (112 KiB at W = 7).  Lane l owns codes 2 l and 2 l + 1 of the unit: 2 W words = W 16-byte chunks that start at
+// byte 16 W l, so the run is 16-byte aligned although an odd-W code alone is not, and is read with W ds_read_b128.
+// Banks: the 16-byte slot of lane l's chunk cc is (W l + cc) mod 16; the sixteen lanes of a ds_read_b128 group cover
+// every residue mod 16, so odd W reads conflict-free and W = 6 two-way (6 l mod 16 takes eight values) -- W reads per
+// unit and lane, paid once per unit, not per query.  (9 .. 15 words have no ring: whole codes in whole pieces would
+// need units of 9 .. 15 KiB, 144 .. 240 KiB for eight waves' rings.)
+constexpr bool ring_pow2(int W) { return (W & (W - 1)) == 0; }
+constexpr int ring_unit(int W) { return ring_pow2(W) ? 8192 : W * 1024; }   // bytes: whole codes, whole 1 KiB DMA pieces
+constexpr bool ring_width(int W) { return W <= 7 || W == 8 || W == 16; }
 template <int W>
 struct RingShape {
-    static constexpr int CPL = W >= 2 ? W / 2 : 1;   // 16-byte chunks a lane reads in a row (one code; W = 1: two codes)
-    static constexpr int NG = 8 / CPL;               // such groups per 8 KiB unit and lane
-    static constexpr int CODES = W == 1 ? 16 : NG;   // codes per lane and unit
-    static constexpr int UNIT_CODES = 1024 / W;      // codes per unit
-    static_assert(W == 1 || W == 2 || W == 4 || W == 8 || W == 16, "ring kernel: 64 .. 1024-bit codes, powers of two");
+    static constexpr bool POW2 = ring_pow2(W);
+    static constexpr int UNIT = ring_unit(W);
+    static constexpr int PIECES = UNIT / 1024;                       // DMA pieces per unit: the PER of the counted waits
+    static constexpr int CPL = !POW2 ? W : W >= 2 ? W / 2 : 1;       // 16-byte chunks a lane reads in a row (one code; W = 1 and W = 3, 5, 6, 7: two codes)
+    static constexpr int NG = PIECES / CPL;                          // such groups per unit and lane
+    static constexpr int CODES = W == 1 ? 16 : POW2 ? NG : 2;        // codes per lane and unit
+    static constexpr int UNIT_CODES = UNIT / (8 * W);                // codes per unit
+    static_assert(W >= 1 && ring_width(W), "ring kernel: 64 .. 448-bit codes, 512 and 1024 bits");
 };
-static constexpr int HR_WAVES = 8, HR_NSTAGE = 2, HR_UNIT = 8192;
+static constexpr int HR_WAVES = 8, HR_NSTAGE = 2;
 
 // row of code slot i of lane `lane` in the unit that starts at code `code0`
 template <int W>
 __device__ __forceinline__ long long ring_row(long long code0, int lane, int i) {
     if constexpr (W == 1)
         return code0 + ((long long)(i >> 1) * 64 + lane) * 2 + (i & 1);
-    else
+    else if constexpr (ring_pow2(W))
         return code0 + (long long)i * 64 + lane;
+    else
+        return code0 + (long long)lane * 2 + i;
 }
 
 // popcount(x) + acc as two v_bcnt_u32_b32 with their accumulate operand: one serial chain per code.  (Left to hipcc the
@@ -365,6 +393,7 @@ __global__ __launch_bounds__(HR_WAVES * 64, 1) void hamming_ring_kernel(const u6
     extern __shared__ __attribute__((aligned(16))) unsigned char hsm[];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    constexpr int HR_UNIT = R::UNIT;
     u32* lcnt = reinterpret_cast<u32*>(hsm + (size_t)HR_WAVES * HR_NSTAGE * HR_UNIT);   // [nq]
     for (int i = threadIdx.x; i < nq; i += HR_WAVES * 64) lcnt[i] = 0u;
     __syncthreads();
@@ -436,13 +465,13 @@ __global__ __launch_bounds__(HR_WAVES * 64, 1) void hamming_ring_kernel(const u6
         const unsigned char* src = gbase + u * HR_UNIT;
         const u32 dst = ring_base + (u32)(issued % HR_NSTAGE) * HR_UNIT;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) glds16<NT>(src + j * 1024, voff, dst + (u32)j * 1024);
+        for (int j = 0; j < R::PIECES; ++j) glds16<NT>(src + j * 1024, voff, dst + (u32)j * 1024);
         ++issued;
     };
     for (int p = 0; p < HR_NSTAGE; ++p)
         if (issued < mine) issue_unit();
     for (long long it = 0; it < mine; ++it) {
-        wait_units_in_flight<HR_NSTAGE, 8>((int)(issued - it - 1));   // younger units may stay in flight
+        wait_units_in_flight<HR_NSTAGE, R::PIECES>((int)(issued - it - 1));   // younger units may stay in flight
         const unsigned char* sl = ring_ptr + (it % HR_NSTAGE) * HR_UNIT;
         u64 c[R::CODES][W];
 #pragma unroll
@@ -453,9 +482,12 @@ __global__ __launch_bounds__(HR_WAVES * 64, 1) void hamming_ring_kernel(const u6
                 if constexpr (W == 1) {
                     c[2 * g][0] = v.x;
                     c[2 * g + 1][0] = v.y;
-                } else {
+                } else if constexpr (R::POW2) {
                     c[g][2 * cc] = v.x;
                     c[g][2 * cc + 1] = v.y;
+                } else {   // the lane's two codes are one run of 2 W words
+                    c[(2 * cc) / W][(2 * cc) % W] = v.x;
+                    c[(2 * cc + 1) / W][(2 * cc + 1) % W] = v.y;
                 }
             }
         }
@@ -547,7 +579,7 @@ __global__ __launch_bounds__(256) void hamming_compact_kernel(const u64* __restr
     if (threadIdx.x == 0 && blockIdx.y == 0) cnt[q] = s_over ? cap + 1u : total;
 }
 
-// Generic word count (W not specialised): one code per thread.
+// Generic word count (beyond HS_MAX_WORDS = 16 words): one code per thread.
 __global__ __launch_bounds__(256) void hamming_scan_generic_kernel(const u64* __restrict__ codes, long long n, RowPerm pmul,
                                                                     int W, const u64* __restrict__ qs, int nq,
                                                                     const int* __restrict__ thr,
@@ -677,12 +709,6 @@ struct HammingFinalize {
 namespace sq {
 
 // ------------------------------------------------------------- host driver
-// Codes per thread of the register kernels: a thread of the scan / histogram kernels holds 4 / W codes of W words,
-// one of the stream / body kernels twice as many.  The template arguments and the host's block arithmetic both
-// come from here.
-constexpr int scan_codes(int W) { return W == 1 ? 4 : W == 2 ? 2 : 1; }
-constexpr int stream_codes(int W) { return 2 * scan_codes(W); }
-
 // Runtime code width -> compile-time: f(std::integral_constant<int, W>) for the one of Ws... that W equals,
 // otherwise() for every other width.
 template <int... Ws, class F, class Other>
@@ -692,9 +718,19 @@ static int with_width(int W, F&& f, Other&& otherwise) {
     return hit ? rc : otherwise();
 }
 
+// every width with register kernels (1 .. HS_MAX_WORDS words), and those with the three-launch call (HF_MAX_WORDS)
+template <class F, class Other>
+static int with_stream_width(int W, F&& f, Other&& otherwise) {
+    return with_width<1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16>(W, f, otherwise);
+}
+template <class F, class Other>
+static int with_fused_width(int W, F&& f, Other&& otherwise) {
+    return with_width<1, 2, 3, 4, 5, 6, 7>(W, f, otherwise);
+}
+
 static int scan_dispatch(const HammingHandle* h, const u64* qs, int nq, const int* thr, u64* keys, u32* cnt, u32 cap,
                          long long key_stride, int mode, hipStream_t st) {
-    return with_width<1, 2, 4>(
+    return with_stream_width(
         h->words,
         [&](auto w) {
             constexpr int W = decltype(w)::value, C = scan_codes(W);
@@ -718,7 +754,7 @@ static unsigned hist_blocks(const HammingHandle* h, int step) {
 
 static int hist_dispatch(const HammingHandle* h, const u64* qs, int nq, int bits, u32* hist, int step, hipStream_t st) {
     const unsigned blocks = hist_blocks(h, step);
-    return with_width<1, 2, 4>(
+    return with_stream_width(
         h->words,
         [&](auto w) {
             constexpr int W = decltype(w)::value;
@@ -732,6 +768,14 @@ static int hist_dispatch(const HammingHandle* h, const u64* qs, int nq, int bits
         },
         [&] { return launch<hamming_hist_generic_kernel>(dim3(blocks), dim3(256), 0, st, h->codes, h->n, h->words, qs, nq, bits, hist, step); });
 }
+
+// Queries per launch of the register stream: nq * (8 W + 8) bytes of LDS once per resident workgroup, sized for eight
+// of them at every width.  Beyond 4 words only 3 or 4 are resident (stream_wgs_per_cu), so the batch there is safe and
+// about half of what would fit.
+constexpr int stream_qbatch(int W) { return W <= 2 ? 1024 : W <= 5 ? 384 : 2048 / W; }
+// Workgroups of the register stream a CU holds at once (= waves per SIMD), by the registers of the width's
+// instantiation: DESIGN.md section 4.3 has the table this summarises.
+constexpr int stream_wgs_per_cu(int W) { return W <= 4 ? 8 : W <= 14 ? 4 : 3; }
 
 // Everything a search decides before it touches the device, from the handle, its options and the call's shape.
 // hamming_enqueue launches what the plan says; hamming_resolve replays parts of it (HammingCall::plan).
@@ -762,23 +806,23 @@ static HammingPlan hamming_plan(const HammingHandle* h, int nq, int k, bool use_
     if (h->opt.sample_stride <= 0)
         while (step > 1 && (long long)step * kk * 8 > (long long)cap) step >>= 1;
     p.step = step;
-    const bool stream_ok = p.stream_ok = W == 1 || W == 2 || W == 4;
+    const bool stream_ok = p.stream_ok = W <= HS_MAX_WORDS;
     // LDS-DMA ring (hamming_ring_kernel): HBM bound batches over arrays the MALL cannot hold.  Beyond ~24 queries
     // the inner loop is VALU bound and the register kernel's 32 waves per CU win.
     const size_t code_bytes = (size_t)n * W * 8;
-    const bool ring_shape = (W == 1 || W == 2 || W == 4 || W == 8 || W == 16) && (reinterpret_cast<uintptr_t>(h->codes) & 15u) == 0 &&
-                            n * (long long)W * 8 >= 2ll * HR_UNIT * HR_WAVES;
+    const bool ring_shape = ring_width(W) && (reinterpret_cast<uintptr_t>(h->codes) & 15u) == 0 &&
+                            n * (long long)W * 8 >= 2ll * ring_unit(W) * HR_WAVES;
     const bool ring = p.ring = ring_shape && (h->opt.hamming_ring == 1 ||
                                               (h->opt.hamming_ring < 0 && nq <= 24 && code_bytes >= ((size_t)256 << 20)) ||
-                                              (h->opt.hamming_ring < 0 && !stream_ok && nq <= 64));
+                                              (h->opt.hamming_ring < 0 && (W == 8 || W == 16) && nq <= 64));
     // non-temporal stream for arrays far beyond the MALL (read once per call)
     p.nt = code_bytes >= ((size_t)512 << 20);
     // Small batches in three launches (sq_hamming_fused.hpp): head (sampled histogram + thresholds by the last
     // workgroup), the stream, pick (prefix sum over the mini-lists, exact k-th distance, gather, sort, results).
     // (calls beyond 32 queries -- up to one stream launch's batch -- keep the threshold launch: hamming_body_kernel then reads
     // the thresholds instead of computing them in its prologue)
-    const int fused_max_nq = ring ? HF_MAX_NQ : (W == 4 ? 384 : 1024);
-    const bool fused = p.fused = h->opt.hamming_fused != 0 && !h->no_fused && stream_ok && nq <= fused_max_nq && 2 * kk <= HF_SORT_CAP;
+    const int fused_max_nq = ring ? HF_MAX_NQ : stream_qbatch(W);
+    const bool fused = p.fused = h->opt.hamming_fused != 0 && !h->no_fused && W <= HF_MAX_WORDS && nq <= fused_max_nq && 2 * kk <= HF_SORT_CAP;
     // The fused call's threshold: the general chain takes the smallest t whose SAMPLE count reaches k -- safe (the sample
     // is a subset) and loose: ~step x k codes pass (7.8 k per query at 10 M x 64 bits, k = 100), and with 0.4 survivors
     // per wave and chunk the emission path, not the popcounts, is half of the stream's time.  The pick kernel counts what
@@ -802,29 +846,32 @@ static HammingPlan hamming_plan(const HammingHandle* h, int nq, int k, bool use_
     if (!stream_ok && !ring) return p;   // the one-kernel scan with global counters: no mini-lists
 
     // streaming scan into per-(block, query) mini-lists, then a prefix-sum compaction: no global atomics
-    // register kernel: 8 workgroups per CU (32 waves: the VALU-bound inner loop wants full occupancy); the LDS copy
-    // of the queries (nq * (8W+8) bytes) must fit 8 times, so wide codes take the queries in smaller batches.
+    // register kernel: 8 workgroups per CU (32 waves: the VALU-bound inner loop wants full occupancy) up to 256 bits,
+    // as many as the registers of the width allow beyond (stream_wgs_per_cu); the LDS copy of the queries
+    // (nq * (8W+8) bytes) must fit 8 times, so wide codes take the queries in smaller batches.
     // ring kernel: one 512-thread workgroup per CU -- on three quarters of the CUs when calls are pipelined and the
     // pass is HBM bound: the neighbouring calls' select needs most of a CU's LDS, and such a stream loses
     // nothing on 192 CUs
-    p.qbatch = ring ? 64 : (W == 4 ? 384 : 1024);
+    p.qbatch = ring ? 64 : stream_qbatch(W);
     const int cus = cu_count(h->device);
     // (from ~8 queries per pass the ring kernel is VALU bound and wants every CU; the neighbours' short kernels
     // then simply queue behind it)
-    int G = ring ? (use_event && nq <= 4 ? cus * 3 / 4 : cus) : 8 * cus;
+    const int wgs = stream_wgs_per_cu(W);
+    int G = ring ? (use_event && nq <= 4 ? cus * 3 / 4 : cus) : wgs * cus;
     if (G > 2048) G = 2048;
     if (ring) {
-        const long long units = (n * (long long)W * 8) / HR_UNIT;
+        const long long units = (n * (long long)W * 8) / ring_unit(W);
         if ((long long)G * HR_WAVES > units) G = (int)std::max<long long>(1, units / HR_WAVES);
     } else {
         const long long per_chunk = 256ll * stream_codes(W);
         const long long nchunks = (n + per_chunk - 1) / per_chunk;
-        if (fused && nchunks > (long long)8 * cus && 8 * cus <= 2048) {
+        if (fused && nchunks > (long long)wgs * cus && wgs * cus <= 2048) {
             // every CU holds j workgroups that walk ceil(nchunks / (j CUs)) chunks each: the pass lasts j * that many
             // chunk times on the fullest CU.  10 M x 64-bit codes = 4883 chunks: 8 workgroups per CU -> 8 x 3 = 24
             // chunk times where 4883 / 256 = 19.1 would do; 5 per CU -> 5 x 4 = 20
-            // (at most 6 workgroups of the body kernel fit a CU: 80 VGPRs, and nq * (8 W + 8) bytes of LDS each)
-            int jmax = 6;
+            // (at most 6 workgroups of the body kernel fit a CU: 80 VGPRs, and nq * (8 W + 8) bytes of LDS each; beyond 32
+            // queries a fused call streams with hamming_stream_kernel, which fits fewer of the wide codes)
+            int jmax = p.body_kernel || wgs > 6 ? 6 : wgs;
             const size_t lds_wg = (size_t)nq * (W * 8 + 8);
             if (lds_wg * jmax > (size_t)160 * 1024) jmax = (int)((size_t)160 * 1024 / lds_wg);
             if (jmax < 3) jmax = 3;
@@ -870,8 +917,8 @@ static int select_finalize(const HammingHandle* h, HammingSlot& s, u32 cap, hipS
 static int stream_launch(const HammingHandle* h, const HammingPlan& p, const u64* qc, int nqc, const int* thr, u64* seg, u32* bcnt,
                          hipStream_t st) {
     if (p.ring) {
-        const size_t lds = (size_t)HR_WAVES * HR_NSTAGE * HR_UNIT + (size_t)nqc * 4;
-        return with_width<1, 2, 4, 8, 16>(
+        const size_t lds = (size_t)HR_WAVES * HR_NSTAGE * ring_unit(h->words) + (size_t)nqc * 4;
+        return with_width<1, 2, 3, 4, 5, 6, 7, 8, 16>(
             h->words,
             [&](auto w) {
                 constexpr int W = decltype(w)::value;
@@ -881,7 +928,7 @@ static int stream_launch(const HammingHandle* h, const HammingPlan& p, const u64
             },
             [&] { return fail(SQ_ERR_UNSUPPORTED, "hamming ring: %d-word codes", h->words); });
     }
-    return with_width<1, 2, 4>(
+    return with_stream_width(
         h->words,
         [&](auto w) {
             constexpr int W = decltype(w)::value;
@@ -911,12 +958,18 @@ static int enqueue_fused(HammingHandle* h, HammingSlot& s, const HammingPlan& p,
     SQ_TRY(reserve_zeroed(s.fhist, s.fhist_zeroed, (size_t)(nq > HF_MAX_NQ ? nq : HF_MAX_NQ) * (bits + 1) * 4, st));
     u32* hist = s.fhist.as<u32>();
     if (nq > 8 && nq <= HF_MAX_NQ) {   // a lane per query: no same-address LDS atomics (sq_hamming_fused.hpp)
-        SQ_TRY(with_width<1, 2, 4>(
+        SQ_TRY(with_fused_width(
             h->words,
             [&](auto w) {
                 constexpr int W = decltype(w)::value;
-                return launch<hamming_hist_by_query_kernel<W, scan_codes(W)>>(dim3(hist_blocks(h, p.step)), dim3(256), (size_t)32 * (bits + 1) * 4, st,
-                                                                              h->codes, h->n, c.qs, nq, bits, hist, p.step);
+                // (7 words: the 32 histogram rows and the block's codes are 70.1 KiB, beyond the 64 KiB of a plain launch;
+                // 5 and 6 words, 50.1 and 60.1 KiB, would fit one and take the same call)
+                if constexpr (W > 4)
+                    return launch_lds<hamming_hist_by_query_kernel<W, scan_codes(W)>>(32 * (W * 64 + 1) * 4, dim3(hist_blocks(h, p.step)), dim3(256),
+                                                                                      (size_t)32 * (bits + 1) * 4, st, h->codes, h->n, c.qs, nq, bits, hist, p.step);
+                else
+                    return launch<hamming_hist_by_query_kernel<W, scan_codes(W)>>(dim3(hist_blocks(h, p.step)), dim3(256), (size_t)32 * (bits + 1) * 4, st,
+                                                                                  h->codes, h->n, c.qs, nq, bits, hist, p.step);
             },
             [&] { return fail(SQ_ERR_UNSUPPORTED, "hamming fused: %d-word codes", h->words); }));
     } else {
@@ -929,7 +982,7 @@ static int enqueue_fused(HammingHandle* h, HammingSlot& s, const HammingPlan& p,
     u64* seg = s.seg.as<u64>();
     u32* bcnt = s.bcnt.as<u32>();
     if (p.body_kernel) {
-        SQ_TRY(with_width<1, 2, 4>(
+        SQ_TRY(with_fused_width(
             h->words,
             [&](auto w) {
                 constexpr int W = decltype(w)::value;
@@ -1279,9 +1332,30 @@ extern "C" int sq_hamming_create(const uint64_t* codes, int64_t n, int words, in
     return SQ_OK;
 }
 
+// The read-only view of the plan (sq_hamming_search with mem = SQ_MEM_PLAN / SQ_MEM_PLAN_ASYNC): what a search of that
+// shape would do on this handle under its current options, out[SQ_HAMMING_PLAN_FIELDS].  Nothing touches the device.
+static int hamming_plan_report(HammingHandle* h, int nq, int k, bool use_event, int64_t* out) {
+    if (!h) return fail(SQ_ERR_INVALID, "sq_hamming_plan: unknown handle");
+    if (!out || nq <= 0 || k <= 0) return fail(SQ_ERR_INVALID, "sq_hamming_plan: bad argument");
+    std::lock_guard<std::mutex> lock(h->mu);
+    h->refresh_options();
+    const HammingPlan p = hamming_plan(h, nq, k, use_event);
+    const bool mini_lists = !p.small && (p.stream_ok || p.ring);
+    out[0] = p.small ? 0 : p.fused ? 2 : 1;
+    out[1] = !mini_lists ? 0 : p.ring ? 2 : 1;
+    out[2] = p.body_kernel ? 1 : 0;
+    out[3] = p.G;
+    out[4] = (int64_t)p.S;
+    out[5] = p.step;
+    out[6] = (int64_t)p.cap;
+    out[7] = p.qbatch;
+    return SQ_OK;
+}
+
 extern "C" int sq_hamming_search(sq_handle_t hid, const uint64_t* queries, int nq, int k, int32_t* out_dist,
                                  int64_t* out_idx, int mem, void* stream) {
     auto* h = static_cast<HammingHandle*>(lookup_handle(hid, H_HAMMING));
+    if (mem == SQ_MEM_PLAN || mem == SQ_MEM_PLAN_ASYNC) return hamming_plan_report(h, nq, k, mem == SQ_MEM_PLAN_ASYNC, out_idx);
     if (!h) return fail(SQ_ERR_INVALID, "sq_hamming_search: unknown handle");
     if (!queries || !out_dist || !out_idx || nq <= 0 || k <= 0)
         return fail(SQ_ERR_INVALID, "sq_hamming_search: bad argument");

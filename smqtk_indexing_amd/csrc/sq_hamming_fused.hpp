@@ -25,7 +25,7 @@
 
 namespace sq {
 
-static constexpr int HF_MAX_NQ = 32;      // queries per fused call (LDS histogram of the head: nq x (bits + 1) counters)
+static constexpr int HF_MAX_NQ = 32;      // queries per fused call with the thresholds in the stream's prologue (LDS histogram of the head: nq x (bits + 1) counters)
 static constexpr int HF_SORT_CAP = 4096;  // keys the pick kernel sorts in LDS (k + the tie group at the k-th distance)
 static constexpr int HF_MAX_BINS = 1025;  // code widths up to 1024 bits
 
@@ -44,6 +44,9 @@ __device__ __forceinline__ u32 hf_wave_incl(u32 v, int lane) {
 // the two half-waves take two codes at a time, broadcast from an LDS copy of the block's codes): the lanes of an atomic
 // hit 32 different rows, at most two lanes per address.  Same sample (every block_step-th block of 256 * C codes), same
 // counts, same output as hamming_hist_kernel.  hist: [nq][bits + 1].
+// LDS: 32 x (bits + 1) x 4 bytes of histogram rows (dynamic) + the block's codes lc[256 C W] (static), together
+//   W = 1: 16.1 KiB   W = 2: 24.1 KiB   W = 3: 30.1 KiB   W = 4: 40.1 KiB   W = 5: 50.1 KiB   W = 6: 60.1 KiB   W = 7: 70.1 KiB
+// of the CU's 160 KiB (W = 7 is beyond the 64 KiB of a plain launch; the host launches W = 5, 6, 7 through launch_lds).
 template <int W, int C>
 __global__ __launch_bounds__(256) void hamming_hist_by_query_kernel(const u64* __restrict__ codes, long long n,
                                                                      const u64* __restrict__ qs, int nq, int bits,
@@ -89,13 +92,16 @@ __global__ __launch_bounds__(256) void hamming_hist_by_query_kernel(const u64* _
 
 // Threshold of one query from its sampled histogram (hamming_thr_kernel's rule: the smallest t whose cumulative sample
 // count reaches k; `bits` when the sample holds fewer than k codes), computed by ONE WAVE: lane l owns bins
-// [l * per, (l + 1) * per), per = ceil((bits + 1) / 64) <= HF_PER.  Every lane returns the threshold.
-static constexpr int HF_PER = 5;   // 256-bit codes: 257 bins
+// [l * per, (l + 1) * per), per = ceil((bits + 1) / 64) <= PER.  Every lane returns the threshold.
+static constexpr int HF_PER = 5;        // codes of up to 256 bits: 257 bins
+static constexpr int HF_MAX_WORDS = 7;  // widest code of the three-launch call: 448 bits, 449 bins, 8 per lane
+constexpr int hf_per(int W) { return W + 1 > HF_PER ? W + 1 : HF_PER; }
+template <int PER = HF_PER>
 __device__ __forceinline__ int hf_wave_threshold(const u32* __restrict__ h, int nb, int bits, int kk, int lane) {
     const int per = (nb + 63) / 64;
-    u32 v[HF_PER], sum = 0;
+    u32 v[PER], sum = 0;
 #pragma unroll
-    for (int j = 0; j < HF_PER; ++j) {
+    for (int j = 0; j < PER; ++j) {
         const int b = lane * per + j;
         v[j] = (j < per && b < nb) ? h[b] : 0u;
         sum += v[j];
@@ -106,7 +112,7 @@ __device__ __forceinline__ int hf_wave_threshold(const u32* __restrict__ h, int 
         u32 cum = exc;
         bool found = false;
 #pragma unroll
-        for (int j = 0; j < HF_PER; ++j) {
+        for (int j = 0; j < PER; ++j) {
             cum += v[j];
             if (!found && cum >= (u32)kk) {
                 t = lane * per + j;
@@ -150,7 +156,7 @@ __global__ __launch_bounds__(256) void hamming_body_kernel(const u64* __restrict
                                                             const u64* __restrict__ qs, int nq, const u32* __restrict__ hist,
                                                             int bits, int rank, int* __restrict__ thr_out,
                                                             u64* __restrict__ seg, u32* __restrict__ bcnt, u32 S) {
-    static_assert(W * 64 + 1 <= HF_PER * 64, "one wave per histogram row");
+    static_assert(W <= HF_MAX_WORDS && W * 64 + 1 <= hf_per(W) * 64, "one wave per histogram row");
     extern __shared__ __attribute__((aligned(16))) unsigned char hbm[];
     u64* lq = reinterpret_cast<u64*>(hbm);                      // [nq][W]
     int* lthr = reinterpret_cast<int*>(lq + (size_t)nq * W);    // [nq]
@@ -163,7 +169,7 @@ __global__ __launch_bounds__(256) void hamming_body_kernel(const u64* __restrict
     if ((long long)blockIdx.x < nchunks) load_codes<W, C>(codes, n, (long long)blockIdx.x * per_chunk, tid, cn, validn);
     if (hist) {
         for (int q = wv; q < nq; q += 4) {
-            const int t = hf_wave_threshold(hist + (long long)q * (bits + 1), bits + 1, bits, rank, lane);
+            const int t = hf_wave_threshold<hf_per(W)>(hist + (long long)q * (bits + 1), bits + 1, bits, rank, lane);
             if (lane == 0) {
                 lthr[q] = t;
                 if (blockIdx.x == 0) thr_out[q] = t;
