@@ -1,5 +1,5 @@
 // ITQ hash codes at the HBM rate: a certified half-precision filter (f16x3) in
-// front of the float64 kernel (sq_itq.hip).
+// front of the float64 kernel (sq_itq_exact.hpp; the driver is sq_itq.hip).
 //
 // ItqFunctor.get_hash (smqtk_indexing/impls/lsh_functor/itq.py:389-408) only
 // keeps the SIGN of z = (v - mean) . R, v = x or x/|x|, but evaluates z in
@@ -13,7 +13,7 @@
 // or 1 and c_b = mean . R_b is a float64 product rounded once.  Bits with
 // |z~| > eps(tile, column) are final; the others are listed as (row, column
 // tile, mask) entries and evaluated in float64 one bit at a time
-// (itq_fix_bits_kernel, sq_itq.hip), so every code is exactly what the float64
+// (itq_fix_bits_kernel, below), so every code is exactly what the float64
 // evaluation gives.
 //
 // Why float16 planes (round 1 used bfloat16).  The kernel is bound by vector
@@ -46,6 +46,7 @@
 // scale (|x| << 1e-2) stays correct but leaves more bits to float64.
 #pragma once
 #include "sq_dma.hpp"
+#include "sq_itq_exact.hpp"
 
 namespace sq {
 
@@ -557,6 +558,141 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void itq_fast_kernel(ItqFast
         ++epi_total;
     }
     if (lane == 0) a.seg_cnt[wave_id] = wcount;
+}
+
+typedef float f32x4_t __attribute__((ext_vector_type(4)));
+typedef double f64x2_t __attribute__((ext_vector_type(2)));
+
+// The filter's undecided bits, one float64 evaluation each: z_b = sum_k v_k R[k][b], v as the float64
+// kernel (itq_hash_kernel, sq_itq_exact.hpp) forms it (x / |x| in float32 with numpy's norm, minus the mean in the promoted dtype).
+// Workgroups (w, 0..3) share segment w of the filter's output; 32 lanes per entry (row, column tile,
+// mask of undecided columns): lane l holds elements 4l..4l+3 of every 128-element stretch, so the row
+// (a random 512-byte read) and the column of the column-major float64 copy of R arrive as whole
+// cache lines.  The filter already stored the sign of its own estimate; the bit is set to the float64
+// sign in place.  (A whole-row float64 MFMA recompute of the ~4 % of rows owning such a bit cost
+// 0.31 ms at 10 M x 128 -> 64 bits -- 64x the flops needed; one or eight lanes per entry cost as much:
+// every 16-byte piece of a row then pulls its own cache line through L2.)
+#ifndef SQ_ITQ_FIX_PARTS
+#define SQ_ITQ_FIX_PARTS 4
+#endif
+static constexpr int ITQ_FIX_PARTS = SQ_ITQ_FIX_PARTS;
+static __global__ __launch_bounds__(256) void itq_fix_bits_kernel(ItqArgs a, const u64* __restrict__ seg,
+                                                                  const u32* __restrict__ seg_cnt, long long seg_cap,
+                                                                  const double* __restrict__ rt64) {
+    const long long w = blockIdx.x;
+    const u32 cnt = seg_cnt[w];
+    const int l32 = threadIdx.x & 31, slot = (threadIdx.x >> 5) + 8 * blockIdx.y;
+    const float* X = reinterpret_cast<const float*>(a.x);
+    constexpr u32 STEP = 8 * ITQ_FIX_PARTS;
+    u64 ent_next = slot < (int)cnt ? seg[w * seg_cap + slot] : 0ull;
+    for (u32 e = slot; e < cnt; e += STEP) {  // uniform within a 32-lane half wave
+        // per entry the dependent chain is entry -> (row | R column) -> sum: the next entry is requested a turn
+        // early and the result goes out as a fire-and-forget atomic
+        const u64 ent = ent_next;
+        if (e + STEP < cnt) ent_next = seg[w * seg_cap + e + STEP];
+        const long long row = (long long)((u32)(ent >> 32) & 0x3fffffffu);
+        const int ct = (int)(ent >> 62);
+        u32 mask = (u32)ent;
+        const float* xr = X + row * a.d;
+        // the first (usually only) undecided column's slice of R: requested together with the row
+        f64x2_t rfirst[2][2];
+        {
+            const double* rcol = rt64 + (long long)(ct * 32 + __ffs((int)mask) - 1) * a.d;
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                const int k = 128 * t + 4 * l32;
+                rfirst[t][0] = rfirst[t][1] = f64x2_t{0.0, 0.0};
+                if (k < a.d) {
+                    rfirst[t][0] = *reinterpret_cast<const f64x2_t*>(rcol + k);
+                    rfirst[t][1] = *reinterpret_cast<const f64x2_t*>(rcol + k + 2);
+                }
+            }
+        }
+        // this lane's elements: 4 l32 + 128 t + 0..3, t < d/128 rounded up; v = x/|x| - mean formed once
+        double v[2][4];  // d <= 256
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            const int k = 128 * t + 4 * l32;
+            const bool in = k < a.d;
+            f32x4_t xv = f32x4_t{0.f, 0.f, 0.f, 0.f};
+            if (in) xv = *reinterpret_cast<const f32x4_t*>(xr + k);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[t][j] = (double)xv[j];  // raw value for now
+        }
+        float nrm = 1.f;
+        if (a.norm == SQ_NORM_L2) {
+            // numpy's pairwise order needs the row's own layout: eight cooperating lanes (np_pairwise_sum), every
+            // aligned group of 8 computes the same value
+            auto term = [xr](int i) { return mul_rn(xr[i], xr[i]); };
+            nrm = sqrt_rn(np_pairwise_sum<float>(term, a.d, threadIdx.x & 7));
+            if (nrm == 0.f) nrm = 1.f;
+        }
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            const int k = 128 * t + 4 * l32;
+            if (k < a.d) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    float xe = (float)v[t][j];
+                    if (a.norm == SQ_NORM_L2) xe = div_rn(xe, nrm);
+                    v[t][j] = a.sub32 ? (double)__fsub_rn(xe, (float)a.mean[k + j]) : __dsub_rn((double)xe, a.mean[k + j]);
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) v[t][j] = 0.0;
+            }
+        }
+        bool first = true;
+        while (mask) {  // nearly always one bit
+            const int pc = ct * 32 + __ffs((int)mask) - 1;   // padded column; the filter only flags pc >= pad
+            mask &= mask - 1;
+            const double* rcol = rt64 + (long long)pc * a.d;   // column pc of R, contiguous (itq_fast_prep_kernel)
+            double z = 0.0;
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                const int k = 128 * t + 4 * l32;
+                if (k < a.d) {
+                    f64x2_t r0 = rfirst[t][0], r1 = rfirst[t][1];
+                    if (!first) {
+                        r0 = *reinterpret_cast<const f64x2_t*>(rcol + k);
+                        r1 = *reinterpret_cast<const f64x2_t*>(rcol + k + 2);
+                    }
+                    z = __fma_rn(v[t][0], r0[0], z);
+                    z = __fma_rn(v[t][1], r0[1], z);
+                    z = __fma_rn(v[t][2], r1[0], z);
+                    z = __fma_rn(v[t][3], r1[1], z);
+                }
+            }
+            z += __shfl_xor(z, 16);
+            z += __shfl_xor(z, 8);
+            z += __shfl_xor(z, 4);
+            z += __shfl_xor(z, 2);
+            z += __shfl_xor(z, 1);
+            first = false;
+            if (l32 == 0) {  // set the bit to the float64 sign (no read of the word: nothing to wait for)
+                unsigned long long* word = reinterpret_cast<unsigned long long*>(a.out + row * a.words + (pc >> 6));
+                const unsigned long long bit = 1ull << (63 - (pc & 63));
+                if (z >= 0.0)
+                    atomicOr(word, bit);
+                else
+                    atomicAnd(word, ~bit);
+            }
+        }
+    }
+}
+
+// Bits a filter left to float64: the set mask bits of every segment's entries (statistics of a model handle).  The
+// 32-column mask is the low word of the entry in all three filters, so one kernel counts for each of them.
+static __global__ __launch_bounds__(256) void itq_count_undecided_kernel(const u64* __restrict__ seg, const u32* __restrict__ seg_cnt,
+                                                                          long long seg_cap, unsigned long long* __restrict__ total) {
+    const long long w = blockIdx.x;
+    const long long cnt_raw = seg_cnt[w];
+    const u32 cnt = (u32)(cnt_raw < seg_cap ? cnt_raw : seg_cap);
+    u32 c = 0;
+    for (u32 e = threadIdx.x; e < cnt; e += 256) c += (u32)__popc((u32)seg[w * seg_cap + e]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
+    if ((threadIdx.x & 63) == 0 && c) atomicAdd(total, (unsigned long long)c);
 }
 
 }  // namespace sq

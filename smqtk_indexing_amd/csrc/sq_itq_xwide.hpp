@@ -41,7 +41,7 @@
 // Range: a tile with an element not below 60000 in magnitude, or a non-finite |x|^2, sends all its bits to float64.
 //
 // The undecided bits -- (row, column tile, mask) entries as in sq_itq_wide.hpp -- are evaluated by
-// itq_fix_bits_xwide_kernel on v_mfma_f64_16x16x4_f64 with the operand order of itq_hash_kernel (sq_itq.hip): 16
+// itq_fix_bits_xwide_kernel on v_mfma_f64_16x16x4_f64 with the operand order of itq_hash_kernel (sq_itq_exact.hpp): 16
 // entries per wave, entry i's row as row i of A and its column of R as column i of B, the diagonal of the product kept.
 // An element of an MFMA result depends on its own row of A and column of B only, so each such z_b is the float64
 // kernel's z_b to the last bit, whatever cancels in it (rows that lie in the span of a few rotation columns leave

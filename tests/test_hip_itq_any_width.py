@@ -254,6 +254,41 @@ def test_itq_rows_off_the_16_byte_grid_keep_the_float64_kernel():
     model.close()
 
 
+def test_itq_model_second_call_and_misaligned_device_rows():
+    """Two per-call decisions at the smallest slab shape (4129 x 100 -> 64 bits).  A second call on one model runs on
+    the image of the rotation the first call left on the handle: the same codes AND the same statistics (the count of
+    undecided bits moves with any change of that image or of the error bound).  Device rows whose pointer is advanced
+    by one element are not 16-byte aligned: the float64 kernel hashes them, to the same codes."""
+    import torch
+    n, d, bits = 4129, 100, 64
+    rng = np.random.default_rng(d + bits + 1)
+    x = _rows(rng, n, d, np.float32)
+    mean = x[:2000].mean(axis=0).astype(np.float64)
+    rot = _rotation(d, bits, d + bits)
+    model = _lib.ItqModel(mean, rot, _lib.SQ_NORM_L2)
+    first, st_first = model.hash(x), model.stats()
+    second, st_second = model.hash(x), model.stats()
+    print("first:", st_first, "second:", st_second)
+    assert st_first["scan_launches"] == 1 and st_first["fallback_queries"] == 0 and st_first["candidates"] > 0
+    assert st_second == st_first
+    np.testing.assert_array_equal(second, first)
+    np.testing.assert_array_equal(first, _exact(x, mean, rot, _lib.SQ_NORM_L2))
+    dev = torch.device("cuda", 0)
+    flat = torch.zeros(n * d + 1, dtype=torch.float32, device=dev)
+    stream = torch.cuda.current_stream().cuda_stream
+    for shift, launches, fallback in ((0, 1, 0), (1, 0, n)):
+        rows = flat[shift:shift + n * d]
+        rows.copy_(torch.from_numpy(x.reshape(-1)))
+        assert rows.data_ptr() % 16 == 4 * shift
+        out = torch.zeros((n, 1), dtype=torch.int64, device=dev)
+        model.hash_device(rows.data_ptr(), _lib.SQ_DTYPE_F32, n, out.data_ptr(), stream)
+        torch.cuda.synchronize()
+        st = model.stats()
+        assert st["scan_launches"] == launches and st["fallback_queries"] == fallback, (shift, st)
+        np.testing.assert_array_equal(out.cpu().numpy().view(np.uint64), first)
+    model.close()
+
+
 # ---------------------------------------------------------------- f. through the plugin
 @pytest.mark.parametrize("dt", [np.float32, np.float64])
 def test_itq_functor_hashes_300_d_descriptors(dt):
