@@ -257,12 +257,14 @@ int sq_dense_create(const float* db, int64_t n, int d, int metric, int mem,
 /* The same with options of THIS index given at create, as name / value arrays: they become the handle's overrides
  * (sq_handle_set_option) BEFORE anything is built, so create-time choices are per index as the reference's are per
  * instance (constructor arguments: impls/nn_index/faiss.py:182-258) -- "dense_int8" = 0: no int8 copy is built or
- * kept (footprint 1.5x the matrix instead of 1.77x), "dense_no_center" = 1.  Two indexes of one process may differ. */
+ * kept (footprint 1.5x the matrix instead of 1.77x), "dense_no_center" = 1, "dense_bf16" = -1 / 0: the bfloat16 copy is
+ * built by the first search that streams it / never (footprint 1.3x the matrix for deployments of small batches: float32
+ * rows, int8 copy, statistics).  Two indexes of one process may differ. */
 int sq_dense_create_opts(const float* db, int64_t n, int d, int metric, int mem, int64_t id_base,
                          const char* const* opt_names, const int64_t* opt_values, int n_opts, sq_handle_t* out);
 /* What the index keeps resident and what its build cost; out[SQ_DENSE_INFO_FIELDS] =
  * { rows, d, bytes of the float32 rows, 1 if the library owns them (0: borrowed from the caller), bytes of the
- *   bfloat16 scan copy, bytes of the int8 scan copy + its row terms, bytes of the row statistics, 1 if the int8 first
+ *   bfloat16 scan copy (0 while the index keeps none: option "dense_bf16"), bytes of the int8 scan copy + its row terms, bytes of the row statistics, 1 if the int8 first
  *   stage is in use, microseconds sq_dense_create took, microseconds of that spent on the int8 copy }.
  * (The build side of FaissNearestNeighborsIndex._build_index, impls/nn_index/faiss.py:486-559.) */
 #define SQ_DENSE_INFO_FIELDS 10
@@ -343,7 +345,21 @@ int sq_dense_search(sq_handle_t h, const float* queries, int nq, int k,
  * float32 rows (L2 and cosine, d <= 512, 16-byte aligned rows) before the exact all-rows path; after three calls
  * in a row in which most candidate lists overflowed, calls skip the first filter and start there (it is tried again after
  * 16 such calls, then 32, 64 ... 1024 while it keeps overflowing; the first probe that does not overflow re-arms it).  0: uncertified queries go straight to the exact path.  Answers are the same bits either way
- * (metrics.py:73-86, 120-137 arithmetic in the re-rank; every tier certifies or hands on). */
+ * (metrics.py:73-86, 120-137 arithmetic in the re-rank; every tier certifies or hands on).
+ * Option "dense_bf16" (1 by default): whether the index keeps the bfloat16 scan copy (rows of up to 8192 padded
+ * dimensions), process-wide or for one index through sq_dense_create_opts.  1: sq_dense_create and sq_dense_compact build
+ * it and it follows every append.  -1, on demand: create and compact neither build nor allocate it; the first search that
+ * takes the bfloat16 chain (a batch the int8 stage does not take, on an index above the candidate cap) finishes the calls
+ * in flight, builds the copy from the resident float32 rows -- the bytes create would have written: the same kernels, the
+ * L2 origin chosen at create, the removed rows' terms -- and then runs; an asynchronous call that does so is final one
+ * call later, as ever.  From then on the copy stays and follows appends and removals as under 1, until sq_dense_compact
+ * sheds it again.  No memory for the copy is not an error: that call is answered as under 0 and a later one tries again.
+ * 0, never: calls the int8 stage does not take are answered by the later tiers (the middle tier where its shape rule
+ * allows, else the exact path) -- the same bits, slower; the smallest footprint for an index that only sees small
+ * batches.  The option is read when copies are built: create, compact, and the search that builds the copy.  While the
+ * copy is absent appends build statistics and the int8 copy only, and sq_dense_info reports 0 bytes for it.  0 on a
+ * handle that has the copy means "do not use it": nothing is freed (only sq_dense_compact under -1 frees it); a handle
+ * that goes from 0 back to 1 or -1 builds the copy at its next search that wants it. */
 int sq_dense_sync(sq_handle_t h);
 int sq_dense_destroy(sq_handle_t h);
 

@@ -210,8 +210,9 @@ def device_name(device: int = 0) -> Tuple[str, int, int]:
 
 
 # Options sq_dense_create reads when it decides which copies an index keeps ("dense_int8" = 0: no int8 copy at all;
-# "dense_int8_wide" = 1: rows of 513 to 8192 dimensions keep one too).  ``DenseIndex(options=...)`` makes them the index's own.
-DENSE_CREATE_OPTIONS = ("dense_int8", "dense_int8_wide", "dense_no_center")
+# "dense_int8_wide" = 1: rows of 513 to 8192 dimensions keep one too; "dense_bf16" = -1 / 0: the bfloat16 copy is built by
+# the first search that streams it / never).  ``DenseIndex(options=...)`` makes them the index's own.
+DENSE_CREATE_OPTIONS = ("dense_int8", "dense_int8_wide", "dense_no_center", "dense_bf16")
 
 _process_options: dict = {}   # what set_option was last given, by name (the library has no getter)
 
@@ -452,7 +453,8 @@ class DenseIndex(_Handle):
     def __init__(self, db, n: Optional[int] = None, d: Optional[int] = None, metric: int = SQ_METRIC_L2,
                  device_ptr: bool = False, id_base: int = 0, keepalive=None, options: Optional[dict] = None):
         """``options``: options of THIS index known at create (``sq_dense_create_opts``), e.g. ``{"dense_int8": 0}`` --
-        no int8 copy is built or kept; they stay the handle's overrides afterwards."""
+        no int8 copy is built or kept, or ``{"dense_bf16": -1}`` -- the bfloat16 copy is built by the first search that
+        streams it (``0``: never); they stay the handle's overrides afterwards."""
         super().__init__()
         if device_ptr:
             assert n is not None and d is not None
@@ -477,7 +479,8 @@ class DenseIndex(_Handle):
         self.handle = int(h.value)
 
     def info(self) -> dict:
-        """What the index keeps resident (bytes per copy) and what its build cost (``sq_dense_info``)."""
+        """What the index keeps resident (bytes per copy) and what its build cost (``sq_dense_info``).
+        ``bf16_copy_bytes`` is 0 while the index keeps no bfloat16 copy (option ``dense_bf16``)."""
         out = (ctypes.c_int64 * 10)()
         _check(load().sq_dense_info(self.handle, out, 10), "sq_dense_info")
         return {"rows": int(out[0]), "d": int(out[1]), "f32_rows_bytes": int(out[2]), "f32_rows_owned": bool(out[3]),

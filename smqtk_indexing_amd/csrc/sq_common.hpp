@@ -80,6 +80,7 @@ struct Options {
     int dense_graph = 1;         // pipelined int8 calls: the call's kernels as one captured graph launch (0 = eager launches)
     int dense_int8 = -1;         // int8 first-stage filter (L2, d <= 128, one query tile): -1 = automatic, 0 = never (bf16 filter), 1 = whenever the copy exists
     int dense_int8_wide = 0;     // int8 first-stage filter for rows of 513 to 8192 dimensions (sq_dense_i8_wide.hpp; L2 and cosine, one query tile): read when an index is created, appended to or compacted -- 1 = such an index of at least 65536 rows keeps the int8 copy and its calls of up to 32 queries stream it ("dense_int8" = 0 on the handle turns the stage off); 0 = no copy, the bfloat16 filter as before
+    int dense_bf16 = 1;          // the bfloat16 scan copy of a dense index (rows of up to 8192 dimensions), read when copies are built (create, compact, the first search that wants the copy): 1 = built at create / compact; -1 = on demand -- built by the first search that takes the bfloat16 chain, kept from then on, shed again by sq_dense_compact; 0 = never -- calls the int8 stage does not take go to the later tiers (set on a handle that has the copy: the copy is left alone, not freed)
     int dense_mid_tier = 1;      // 1 = queries the first filter could not certify get a second, tighter filter pass (L2 and cosine: bf16 planes of the float32 rows built on the fly) before the exact all-rows path, and calls start there once the first filter's lists overflow call after call; 0 = straight to the exact path
     int hamming_async_depth = 2; // asynchronous Hamming searches in flight (2..4), as dense_async_depth
     int hamming_async_wait = 1;  // as dense_async_wait

@@ -102,6 +102,7 @@ int Options::*option_member(const char* name) {
         {"dense_mid_tier", &Options::dense_mid_tier},
         {"dense_int8", &Options::dense_int8},
         {"dense_int8_wide", &Options::dense_int8_wide},
+        {"dense_bf16", &Options::dense_bf16},
         {"dense_graph", &Options::dense_graph},
         {"dense_fused", &Options::dense_fused},
         {"dense_tighten", &Options::dense_tighten},

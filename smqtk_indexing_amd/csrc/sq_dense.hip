@@ -524,6 +524,8 @@ static int dense8_wide_enqueue(DenseHandle* h, DenseSlot& s, const float* q, int
     return select_launch_t<u64>(s.keys.as<u64>(), cnt, cap, key_stride, k, nq, s.out_keys.as<u64>(), fin, st, s.sort_tmp, 4 * stride * kk);
 }
 
+static int dense_bf16_materialize(DenseHandle* h);   // (option "dense_bf16": the scan copy built by the first call that streams it)
+
 // Enqueue one search (nq <= kDenseQueryChunk queries) on `st` with the workspace of slot `s`; nothing is
 // waited for.  dense_resolve() finishes the call: it waits for the kernels, reads the status words and
 // sends uncertified queries down the exact path.
@@ -541,7 +543,8 @@ static int dense_enqueue(DenseHandle* h, DenseSlot& s, const float* q, int nq, i
     const bool small = n <= (long long)cap;
     // k beyond the one-workgroup select (16384; cosine 7168): every query takes the exact path, whose select sorts
     // (the reference has no limit on n: lsh.py:513-518)
-    const bool scan_ok = h->scan.p != nullptr && !small && kk <= (cosine ? kSelectLdsKeys128 : kSelectLdsKeys64);
+    // filter_ok: the shape allows a first-stage filter at all (rows wider than MAX_DPAD have no scan copy of any kind)
+    const bool filter_ok = !small && kk <= (cosine ? kSelectLdsKeys128 : kSelectLdsKeys64) && d_pad <= MAX_DPAD;
     const int qt = scan_query_tiles(h->opt, d_pad, (nq + TILE_ROWS - 1) / TILE_ROWS);  // query tiles per wave
     // query planes: the multi-tile configuration is MFMA bound, so it drops q_lo (half the MFMAs, twice the
     // product bound: ~1.4x more rows pass the filter) unless asked otherwise
@@ -551,6 +554,19 @@ static int dense_enqueue(DenseHandle* h, DenseSlot& s, const float* q, int nq, i
     const int group_q = qt * TILE_ROWS;                                           // queries per scan workgroup
     const int nqt = (nq + group_q - 1) / group_q;                                 // groups of qt query tiles
     const int nq_pad = nqt * group_q;
+    // Which first stage takes the call.  The shortcut past a suspended filter and the two int8 stages need no bfloat16
+    // copy; the bfloat16 chain does, and builds it here when option "dense_bf16" left it for the first call that wants it.
+    const bool int8_on = filter_ok && h->use8 && h->opt.dense_int8 != 0 && !(h->suspended8 && h->opt.dense_int8 < 0);
+    const bool take_mid = filter_ok && h->first_suspended && h->opt.dense_mid_tier != 0 && !h->opt.force_fallback && dense_mid_shape_ok(h) &&
+                          ++h->direct_calls % h->probe_interval != 0;
+    const bool take_i8_wide = !take_mid && int8_on && h->row8 > I8_MAX_ROW_BYTES && nq <= TILE_ROWS;
+    const bool take_i8 = !take_mid && int8_on && h->row8 <= I8_MAX_ROW_BYTES &&
+                         (nq <= TILE_ROWS || (h->row8 == 128 && (qt == 2 || qt == 4) && nq <= h->opt.dense_int8_batch));
+    bool take_bf16 = filter_ok && !take_mid && !take_i8_wide && !take_i8 && h->opt.dense_bf16 != 0;
+    if (take_bf16 && !h->scan.p) {
+        SQ_TRY(dense_bf16_materialize(h));   // (finishes the calls in flight first; no memory for the copy is no error)
+        take_bf16 = h->scan.p != nullptr;
+    }
     DenseCall& c = s.call;
     c = DenseCall{};
     c.q = q;
@@ -635,13 +651,12 @@ static int dense_enqueue(DenseHandle* h, DenseSlot& s, const float* q, int nq, i
                                                                   (float*)out_dist, out_idx, hs_dev, hs_raw_dev, nullptr, 0}, h->deadp()),
                                         st, s.sort_tmp));
         }
-    } else if (scan_ok && h->first_suspended && h->opt.dense_mid_tier != 0 && !h->opt.force_fallback && dense_mid_shape_ok(h) &&
-               ++h->direct_calls % h->probe_interval != 0) {
+    } else if (take_mid) {
         c.all_fallback = true;   // (nothing enqueued: dense_resolve starts every query at the middle tier)
         c.mid_direct = true;
-    } else if (scan_ok && h->use8 && h->row8 > I8_MAX_ROW_BYTES && h->opt.dense_int8 != 0 && !(h->suspended8 && h->opt.dense_int8 < 0) && nq <= TILE_ROWS) {
+    } else if (take_i8_wide) {
         // ---- rows of 513 to 8192 dimensions, one query tile: the int8 first stage of sq_dense_i8_wide.hpp
-        // (scan_ok: kk is inside the one-workgroup select; larger batches take the bfloat16 chain below)
+        // (filter_ok: kk is inside the one-workgroup select; larger batches take the bfloat16 chain below)
         c.int8 = true;
         if (h->suspended8) {   // dense_int8 = 1 on the handle: the filter is armed again (and judged again from the next calls)
             h->suspended8 = false;
@@ -650,8 +665,7 @@ static int dense_enqueue(DenseHandle* h, DenseSlot& s, const float* q, int nq, i
         c.stats.scan_launches = 2;
         c.stats.bytes_scanned = h->n_pad64 * ((long long)h->row8 + 4);
         SQ_TRY(dense8_wide_enqueue(h, s, q, nq, k, kk, out_dist, out_idx, st, prof, cap, hs_dev, hs_raw_dev));
-    } else if (scan_ok && h->use8 && h->row8 <= I8_MAX_ROW_BYTES && h->opt.dense_int8 != 0 && !(h->suspended8 && h->opt.dense_int8 < 0) && kk <= (cosine ? kSelectLdsKeys128 : kSelectLdsKeys64) &&
-               (nq <= TILE_ROWS || (h->row8 == 128 && (qt == 2 || qt == 4) && nq <= h->opt.dense_int8_batch))) {
+    } else if (take_i8) {
         // ---- the int8 first-stage filter (sq_dense_i8.hpp): half the bytes per row, measured error bound
         c.int8 = true;
         if (h->suspended8) {   // dense_int8 = 1 on the handle: the filter is armed again (and judged again from the next calls)
@@ -920,7 +934,7 @@ static int dense_enqueue(DenseHandle* h, DenseSlot& s, const float* q, int nq, i
             ind = nullptr;
             SQ_TRY(chain(st));
         }
-    } else if (scan_ok) {
+    } else if (take_bf16) {
         const long long n_tiles = (n + TILE_ROWS - 1) / TILE_ROWS;
         // Sample every stride-th tile.  The sample pass costs ~ n * groups / stride, the re-rank + select
         // ~ nq * stride * k (candidates per query ~ stride * k * slack); with groups ~ nq / (32 qt) the
@@ -1126,6 +1140,8 @@ static int dense_enqueue(DenseHandle* h, DenseSlot& s, const float* q, int nq, i
         }
     } else {
         c.all_fallback = true;  // rows wider than the MFMA scan covers: exact path for every query
+        // no bfloat16 copy to stream ("dense_bf16" = 0, or no memory for it): the middle tier first where its shape rule allows
+        c.mid_direct = filter_ok && h->opt.dense_mid_tier != 0 && !h->opt.force_fallback && dense_mid_shape_ok(h);
     }
     if (prof) SQ_HIP(hipEventRecord(s.ev[3], st));
     if (use_event) {
@@ -1562,10 +1578,16 @@ static int dense_search_chunked(DenseHandle* h, const float* q, int nq, int k, v
 // Row statistics and the bfloat16 scan copy of rows [row_base, n) -- row_base a multiple of 32 -- plus the padding
 // rows of the last tile: the whole matrix at create (row_base = 0), the new rows on append.  The buffers are
 // already large enough (dense_grow); the largest squared norm accumulates across calls.
-static int dense_build_rows(DenseHandle* h, long long row_base) {
+// `parts`: the statistics, the copy, or both.  The copy part runs only where the handle keeps a copy (h->scan: option
+// "dense_bf16"); on its own (dense_bf16_materialize) it leaves the statistics as they are -- cosine recomputes the rows'
+// 1/|x| with the kernel that made them at create (it writes the same `norms` again), L2 reads the origin chosen at create.
+enum : int { ROWS_STATS = 1, ROWS_COPY = 2 };
+static int dense_build_rows(DenseHandle* h, long long row_base, int parts = ROWS_STATS | ROWS_COPY) {
     const long long n = h->n, n_pad = h->n_pad;
     const int d = h->d, d_pad = h->d_pad;
     const bool cosine = h->metric == SQ_METRIC_COSINE;
+    const bool stats = (parts & ROWS_STATS) != 0;
+    const bool copy = (parts & ROWS_COPY) != 0 && h->scan.p != nullptr && d_pad <= MAX_DPAD;
     SQ_TRY(h->scratch.reserve(256));
     float prev = (float)h->xn2_max;
     SQ_HIP(hipMemset(h->scratch.p, 0, 256));
@@ -1575,8 +1597,9 @@ static int dense_build_rows(DenseHandle* h, long long row_base) {
     if (cosine) {
         SQ_TRY(inv.reserve((size_t)(n_pad - row_base) * 4));
         invp = inv.as<float>() - row_base;
-        hipLaunchKernelGGL(dense_cos_norm_kernel, dim3((unsigned)((n - row_base + 255) / 256)), dim3(256), 0, 0, h->db, n,
-                           h->ld, d, h->cos_nx.as<double>(), row_base);
+        if (stats)
+            hipLaunchKernelGGL(dense_cos_norm_kernel, dim3((unsigned)((n - row_base + 255) / 256)), dim3(256), 0, 0, h->db, n,
+                               h->ld, d, h->cos_nx.as<double>(), row_base);
     }
     float* centerp = h->center.p ? h->center.as<float>() : nullptr;
     float* norms1p = nullptr;
@@ -1587,10 +1610,11 @@ static int dense_build_rows(DenseHandle* h, long long row_base) {
         shrink2 = 1.0 - filter_bound(0, kEpsA2, dense_eps_b(d_pad), 0.0).alpha;
         shrink1 = 1.0 - filter_bound(0, kEpsA1, dense_eps_b(d_pad), 0.0).alpha;
     }
-    hipLaunchKernelGGL(dense_rowstats_kernel, dim3((unsigned)((n_pad - row_base) / 32)), dim3(256), 0, 0, h->db, n, h->ld,
-                       d, n_pad, h->scratch.as<u32>(), h->norms.as<float>(), invp, centerp, norms1p, shrink2, shrink1,
-                       row_base);
-    if (d_pad <= MAX_DPAD) {
+    if (stats || (copy && cosine))
+        hipLaunchKernelGGL(dense_rowstats_kernel, dim3((unsigned)((n_pad - row_base) / 32)), dim3(256), 0, 0, h->db, n, h->ld,
+                           d, n_pad, h->scratch.as<u32>(), h->norms.as<float>(), invp, centerp, norms1p, shrink2, shrink1,
+                           row_base);
+    if (copy) {
         const long long chunks = (n_pad - row_base) * (long long)(d_pad / 8);
         hipLaunchKernelGGL(dense_build_scan_kernel, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, 0, h->db, n,
                            h->ld, d, d_pad, n_pad, invp, centerp, h->scan.as<uint4>(), row_base);
@@ -1604,6 +1628,25 @@ static int dense_build_rows(DenseHandle* h, long long row_base) {
     memcpy(&f, &bits, 4);
     h->xn2_max = (double)f;
     return SQ_OK;
+}
+
+// Option "dense_bf16" = -1 (or a handle whose option went from 0 to non-zero): the bfloat16 scan copy, built from the
+// resident float32 rows by the first search that takes the bfloat16 chain -- the bytes sq_dense_create would have written
+// (the same kernels, the origin and the statistics of the handle), with the removed rows' terms on top.  Called under the
+// handle's lock before the call is enqueued: the calls in flight are finished first, as sq_dense_append does.  No memory
+// for the copy is not an error: h->scan stays null, the call is answered by the later tiers and a later call tries again.
+static int dense_bf16_materialize(DenseHandle* h) {
+    if (h->scan.p || h->d_pad > MAX_DPAD) return SQ_OK;
+    SQ_TRY(dense_sync_all(h));
+    if (h->scan.reserve((size_t)h->n_pad * h->d_pad * 2) != SQ_OK) {
+        (void)hipGetLastError();
+        return SQ_OK;
+    }
+    int rc = dense_build_rows(h, 0, ROWS_COPY);
+    if (rc == SQ_OK) rc = dense_dead_reapply(h, 0, nullptr);
+    if (rc == SQ_OK && hipDeviceSynchronize() != hipSuccess) rc = fail(SQ_ERR_HIP, "dense index: building the bfloat16 copy failed");
+    if (rc != SQ_OK) h->scan.release();
+    return rc;
 }
 
 // The int8 first-stage copy (sq_dense_i8.hpp), built at create for L2 matrices of up to 128 dimensions: the clamp and the
@@ -1813,7 +1856,8 @@ static int dense_build_all(DenseHandle* h) {
         rc = h->zeros.reserve(256);
         if (rc == SQ_OK && hipMemset(h->zeros.p, 0, 256) != hipSuccess) rc = fail(SQ_ERR_HIP, "dense index build: memset failed");
     }
-    if (rc == SQ_OK && d_pad <= MAX_DPAD) rc = h->scan.reserve((size_t)h->n_pad * d_pad * 2);
+    // ("dense_bf16" = 1 only: -1 leaves the copy to the first search that streams it, 0 builds none)
+    if (rc == SQ_OK && d_pad <= MAX_DPAD && h->opt.dense_bf16 == 1) rc = h->scan.reserve((size_t)h->n_pad * d_pad * 2);
     if (rc == SQ_OK) rc = dense_build_rows(h, 0);
     if (rc == SQ_OK && hipDeviceSynchronize() != hipSuccess) rc = fail(SQ_ERR_HIP, "dense index build failed");
     const auto t8 = std::chrono::steady_clock::now();
@@ -1932,7 +1976,8 @@ static int dense_grow(DenseHandle* h, long long n_new) {
     SQ_TRY(grow_keep(h->norms, (size_t)h->n_pad * 4, (size_t)n_pad_new * 4));
     if (!cosine) SQ_TRY(grow_keep(h->norms1, (size_t)h->n_pad * 4, (size_t)n_pad_new * 4));
     if (cosine) SQ_TRY(grow_keep(h->cos_nx, (size_t)h->n * 8, (size_t)n_new * 8));
-    if (h->d_pad <= MAX_DPAD) SQ_TRY(grow_keep(h->scan, (size_t)h->n_pad * h->d_pad * 2, (size_t)n_pad_new * h->d_pad * 2));
+    // (an index without the bfloat16 copy -- "dense_bf16" -- is appended to without one)
+    if (h->scan.p) SQ_TRY(grow_keep(h->scan, (size_t)h->n_pad * h->d_pad * 2, (size_t)n_pad_new * h->d_pad * 2));
     return SQ_OK;
 }
 

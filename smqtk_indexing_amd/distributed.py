@@ -91,14 +91,17 @@ class ShardedIndex:
         return allgather_merge(d, i, k, self.group, merge_on, self.packed)
 
 
-def dense_shard(db_shard, row0: int, metric: int = 0, group=None) -> ShardedIndex:
+def dense_shard(db_shard, row0: int, metric: int = 0, group=None, options: Optional[dict] = None) -> ShardedIndex:
     """Shard from a CUDA float32 tensor ``[n_local, d]`` (borrowed, d % 64 == 0).  ``shard.index.remove(ids)`` takes
-    rows out in place (``sq_dense_remove``, global ids ``row0 + row``); the tensor is not written."""
+    rows out in place (``sq_dense_remove``, global ids ``row0 + row``); the tensor is not written.  ``options``: options
+    of the shard's index at create (``DenseIndex(options=...)``), e.g. ``{"dense_bf16": 0}`` for shards that only ever
+    see small batches: no bfloat16 copy, 1.3 x the matrix resident instead of 1.87 x."""
     import torch
     from . import _lib
 
+    kw = {"options": dict(options)} if options else {}
     index = _lib.DenseIndex(db_shard.data_ptr(), n=db_shard.shape[0], d=db_shard.shape[1], metric=metric,
-                            device_ptr=True, id_base=row0, keepalive=db_shard)
+                            device_ptr=True, id_base=row0, keepalive=db_shard, **kw)
     ddt = torch.float64 if metric == _lib.SQ_METRIC_COSINE else torch.float32
 
     def local_search(queries, k):
@@ -271,15 +274,17 @@ class MutableShardedIndex:
 
 
 
-def dense_local_builder(metric: int = 0) -> Callable:
-    """``build_local`` for :class:`MutableShardedIndex` over CUDA float32 rows (HIP dense index, local row ids)."""
+def dense_local_builder(metric: int = 0, options: Optional[dict] = None) -> Callable:
+    """``build_local`` for :class:`MutableShardedIndex` over CUDA float32 rows (HIP dense index, local row ids).
+    ``options``: options of every index it builds (``DenseIndex(options=...)``, e.g. ``{"dense_bf16": -1}``)."""
     import torch
     from . import _lib
     ddt = torch.float64 if metric == _lib.SQ_METRIC_COSINE else torch.float32
+    kw = {"options": dict(options)} if options else {}
 
     def build(rows):
         index = _lib.DenseIndex(rows.data_ptr(), n=rows.shape[0], d=rows.shape[1], metric=metric, device_ptr=True,
-                                keepalive=rows)
+                                keepalive=rows, **kw)
 
         def search(queries, k):
             q = queries.to(rows.device, torch.float32).contiguous()

@@ -88,7 +88,13 @@ class HipBruteForceNearestNeighborsIndex(NearestNeighborsIndex):
             _require_usable(self)
             # an index built while the process-wide "dense_int8_wide" is 1 keeps the choice as its own: its int8 copy then
             # survives a compaction (which builds it again) whatever the process-wide value is by that time
-            kw = {"options": {"dense_int8_wide": 1}} if _lib.process_option("dense_int8_wide", 0) == 1 else {}
+            # (likewise "dense_bf16" = -1 / 0: the bfloat16 copy on demand / never)
+            own = {}
+            if _lib.process_option("dense_int8_wide", 0) == 1:
+                own["dense_int8_wide"] = 1
+            if _lib.process_option("dense_bf16", 1) != 1:
+                own["dense_bf16"] = _lib.process_option("dense_bf16")
+            kw = {"options": own} if own else {}
             self._dev = _lib.DenseIndex(self._matrix, metric=self.METRICS[self.distance_method], **kw)
         return self._dev
 
