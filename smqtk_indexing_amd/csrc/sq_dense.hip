@@ -24,7 +24,11 @@
 //   3. select_topk_kernel sorts the keys; its post-op (DenseFinalize*) converts and
 //      CERTIFIES each query against the filter's error bound.  Queries that fail
 //      (or overflow their list) are redone on the exact full-keys path.
+//
+// Host driver: dense_enqueue chooses the stage that takes a call (dense_small_ / dense8_wide_ / dense8_ / dense_bf16_enqueue);
+// the chains end in dense_survivor_tail.  dense_resolve: dense_resolve_wait, dense_mid_tier, dense_exact_path.
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 #include <cmath>
 
@@ -171,11 +175,89 @@ struct HostProf {
 static HostProf g_hostprof;
 
 // -------------------------------------------------------------- host driver
+// the int8 kernels of a row width of 128, 256 or 512 bytes: f(KS), KS = row bytes / 32 (sq_dense_i8.hpp I8Geom<KS>; the
+// prep and build kernels take EPL = KS / 2; `chunks`: wide rows go in chunks of 512 bytes) -- the Hamming driver's with_width
 template <class F>
-static F with_dead(F f, const u32* dead) {   // a finalisation whose keys may hold removed rows (the exact paths)
-    f.dead = dead;
-    return f;
+static int with_row8(int row8, F&& f, bool chunks = false) {
+    switch (chunks && row8 > 512 ? 512 : row8) {
+        case 128: return f(std::integral_constant<int, 4>{});
+        case 256: return f(std::integral_constant<int, 8>{});
+        case 512: return f(std::integral_constant<int, 16>{});
+    }
+    return fail(SQ_ERR_INVALID, "int8: no kernel for rows of %d bytes", row8);
 }
+
+// What the stages of a call (dense_enqueue) and its later tiers (dense_resolve) share beside DenseCall.
+struct DenseCtx {
+    int kk;
+    bool cosine;
+    u32 cap;
+    int qt, qp, nqt, group_q;   // first stage: query tiles per wave, query planes, groups of qt tiles, queries per scan workgroup
+    long long key_stride;
+    size_t key_bytes;
+    long long id_base;
+    void* out_dist;
+    long long* out_idx;
+    u32* cnt;
+    float* thr;
+    double* qn2;
+    u32* oflag;
+    const double* cnq;
+    // per-query candidate counts and status words land in pinned host memory straight from the finalisation (no copy
+    // launch): [cnt (nq_pad) | status (nq)], by their host and by their device address
+    u32 *hs_cnt, *hs, *hs_cnt_dev, *hs_dev;
+    int bind(const DenseHandle* h, DenseSlot& s) {   // (s.call is filled, the slot's buffers are reserved)
+        const DenseCall& c = s.call;
+        kk = (int)(c.k < h->n_live ? c.k : h->n_live);   // (removed rows are no neighbours: sq_dense_remove)
+        cosine = h->metric == SQ_METRIC_COSINE;
+        key_bytes = cosine ? sizeof(K128) : sizeof(u64);
+        cap = c.cap;
+        id_base = h->id_base;
+        out_dist = c.out_dist;
+        out_idx = c.out_idx;
+        cnt = s.cnt.as<u32>();
+        thr = s.thr.as<float>();
+        qn2 = s.qn2.as<double>();
+        oflag = s.oflag.as<u32>();
+        cnq = s.cos_nq.as<double>();
+        hs_cnt = reinterpret_cast<u32*>(s.status_host.p);
+        hs = hs_cnt + c.nq_pad;
+        SQ_TRY(s.status_host.device_ptr(reinterpret_cast<void**>(&hs_cnt_dev)));
+        hs_dev = hs_cnt_dev + c.nq_pad;
+        return SQ_OK;
+    }
+    // the finalisation of a filter stage: counts and the filter bound certified, the counts copied out
+    template <class M>
+    typename M::Fin filter_fin(double slack = 0.0) const {
+        auto f = M::finalize(*this, cnt, cap, 1, slack);
+        f.cnt_out = hs_cnt_dev;
+        f.overflow = oflag;
+        return f;
+    }
+};
+
+// What the two metrics do not share on the host: key and distance types and the select's finalisation (sq_dense_exact.hpp).
+// finalize() fills what the structs take by position; the members after q0 have the same names in both and are set by name.
+template <bool COSINE>
+struct DenseMetric {
+    static constexpr bool cosine = COSINE;
+    using Key = std::conditional_t<COSINE, K128, u64>;
+    using Dist = std::conditional_t<COSINE, double, float>;
+    using Fin = std::conditional_t<COSINE, DenseFinalizeCos, DenseFinalizeL2>;
+    // slack: FilterBound::beta (L2), eps of the filter's similarity (cosine)
+    static Fin finalize(const DenseCtx& e, const u32* cnt, u32 cap, int certify, double slack = 0.0) {
+        Dist* dist = static_cast<Dist*>(e.out_dist);
+        if constexpr (COSINE)
+            return Fin{cnt, cap, e.kk, e.id_base, e.thr, slack, certify, dist, e.out_idx, e.hs_dev, nullptr, nullptr, 0};
+        else
+            return Fin{cnt, cap, e.kk, e.id_base, e.thr, e.qn2, slack, certify, dist, e.out_idx, e.hs_dev, nullptr, nullptr, 0};
+    }
+};
+template <class F>
+static int by_metric(bool cosine, F&& f) {
+    return cosine ? f(DenseMetric<true>{}) : f(DenseMetric<false>{});
+}
+
 // The per-row terms of the handle's copies that say "never emitted" (sq_dense_remove.hpp)
 static DenseDeadTerms dense_dead_terms(const DenseHandle* h) {
     const bool cosine = h->metric == SQ_METRIC_COSINE;
@@ -198,10 +280,8 @@ static DenseDeadTerms dense_dead_terms(const DenseHandle* h) {
 // ... written again for the removed rows from `row_from` on, after a build kernel has rewritten the terms there
 static int dense_dead_reapply(DenseHandle* h, long long row_from, hipStream_t st) {
     if (!h->dead.p || row_from >= h->n) return SQ_OK;
-    hipLaunchKernelGGL(dense_dead_reapply_kernel, dim3((unsigned)((h->n - row_from + 255) / 256)), dim3(256), 0, st, h->deadp(), row_from,
-                       h->n, dense_dead_terms(h));
-    SQ_HIP(hipGetLastError());
-    return SQ_OK;
+    return launch<dense_dead_reapply_kernel>(dim3((unsigned)((h->n - row_from + 255) / 256)), dim3(256), 0, st, h->deadp(), row_from, h->n,
+                                             dense_dead_terms(h));
 }
 template <int WAVES, int NSTAGE, int KU, int QT, int QP, bool AB, bool SAMPLE, bool NT = false>
 static int scan_launch_t(const DenseScanArgs& a, size_t lds, hipStream_t st) {
@@ -265,23 +345,13 @@ template <bool SAMPLE>
 static int scan_launch(const Options& o, const DenseScanArgs& a, int d_pad, int qt, int qp, hipStream_t st) {
     if (d_pad > RING_MAX_DPAD) {   // rows beyond the ring kernels: one query tile per wave, fragments straight from global memory
         if (qt != 1 && qt != 2 && qt != 4) return fail(SQ_ERR_UNSUPPORTED, "dense scan: d_pad=%d takes one, two or four query tiles per wave", d_pad);
-        const dim3 grid((unsigned)(a.nrb * a.nqt)), block(WIDE_WAVES * 64);
-        if (qt == 4) {
-            if (qp == 2)
-                hipLaunchKernelGGL((dense_wide_scan_kernel<2, 4, SAMPLE>), grid, block, 0, st, a, d_pad / KT);
-            else
-                hipLaunchKernelGGL((dense_wide_scan_kernel<1, 4, SAMPLE>), grid, block, 0, st, a, d_pad / KT);
-        } else if (qt == 2) {
-            if (qp == 2)
-                hipLaunchKernelGGL((dense_wide_scan_kernel<2, 2, SAMPLE>), grid, block, 0, st, a, d_pad / KT);
-            else
-                hipLaunchKernelGGL((dense_wide_scan_kernel<1, 2, SAMPLE>), grid, block, 0, st, a, d_pad / KT);
-        } else if (qp == 2) {
-            hipLaunchKernelGGL((dense_wide_scan_kernel<2, 1, SAMPLE>), grid, block, 0, st, a, d_pad / KT);
-        } else {
-            hipLaunchKernelGGL((dense_wide_scan_kernel<1, 1, SAMPLE>), grid, block, 0, st, a, d_pad / KT);
-        }
-        return SQ_OK;
+        auto go = [&](auto t) {
+            constexpr int QT = decltype(t)::value;
+            const dim3 grid((unsigned)(a.nrb * a.nqt)), block(WIDE_WAVES * 64);
+            return qp == 2 ? launch<dense_wide_scan_kernel<2, QT, SAMPLE>>(grid, block, 0, st, a, d_pad / KT)
+                           : launch<dense_wide_scan_kernel<1, QT, SAMPLE>>(grid, block, 0, st, a, d_pad / KT);
+        };
+        return qt == 4 ? go(std::integral_constant<int, 4>{}) : qt == 2 ? go(std::integral_constant<int, 2>{}) : go(std::integral_constant<int, 1>{});
     }
     const ScanGeom g = scan_geometry(o, d_pad, qt, qp);
     if (g.stages < 2 || ((qt > 1 || qp == 1) && g.waves == 4 && g.stages != 4))
@@ -295,7 +365,7 @@ static int scan_launch(const Options& o, const DenseScanArgs& a, int d_pad, int 
     }
 }
 
-// Error coefficients of the filter score (derivation at their use in dense_search_device); the index build
+// Error coefficients of the filter score (derivation at their use in dense_bf16_enqueue); the index build
 // needs them too: the L2 scan starts from row norms shrunk by the row's share of the bound.
 static constexpr double kEpsA2 = 0.0078125 + 6.103515625e-05;   // two query planes: 2^-7 + 2^-14
 static constexpr double kEpsA1 = 0.015625 + 1.220703125e-04;    // one query plane:  2^-6 + 2^-13
@@ -318,66 +388,38 @@ static int scan_query_tiles(const Options& o, int d_pad, int nqt) {
     return want;
 }
 
-// the int8 scan for a row width (sq_dense_i8.hpp I8Geom): launch, and the attribute every instantiation needs once
-template <int KS, bool SAMPLE>
-static int dense8_scan_launch_t(const Dense8ScanArgs& a, hipStream_t st) {
+// Launch of an int8 ring kernel for the row width KS (sq_dense_i8.hpp I8Geom<KS>) on `nrb` workgroups.  (The kernels have a
+// few bytes of static LDS of their own: the attribute every instantiation needs once is the ring, not the CU's 160 KiB.)
+template <int KS, auto Kernel, class... A>
+static int i8_ring_launch(int nrb, hipStream_t st, const A&... a) {
     using G = I8Geom<KS>;
     constexpr int ring = G::WAVES * G::NSTAGE * G::SLOT_BYTES;
-    // (the kernel has a few bytes of static LDS of its own: the attribute is the ring, not the CU's 160 KiB)
-    return launch_lds<dense8_scan_kernel<KS, SAMPLE>>(ring, dim3((unsigned)a.nrb), dim3(G::WAVES * 64), ring, st, a);
+    return launch_lds<Kernel>(ring, dim3((unsigned)nrb), dim3(G::WAVES * 64), ring, st, a...);
 }
 template <bool SAMPLE>
 static int dense8_scan_launch(int row_bytes, const Dense8ScanArgs& a, hipStream_t st) {
-    switch (row_bytes) {
-        case 128: return dense8_scan_launch_t<4, SAMPLE>(a, st);
-        case 256: return dense8_scan_launch_t<8, SAMPLE>(a, st);
-        case 512: return dense8_scan_launch_t<16, SAMPLE>(a, st);
-    }
-    return fail(SQ_ERR_INVALID, "int8 scan: unsupported row width %d", row_bytes);
-}
-template <int QT, bool SAMPLE>
-static int dense8_scan_mt_launch_t(const Dense8ScanArgs& a, hipStream_t st) {
-    using G = I8Geom<4>;
-    return launch_lds<dense8_scan_mt_kernel<QT, SAMPLE>>(160 * 1024, dim3((unsigned)(a.nrb * a.nqt)), dim3(G::WAVES * 64),
-                                                         (size_t)G::WAVES * G::NSTAGE * G::SLOT_BYTES, st, a);
+    return with_row8(row_bytes, [&](auto ks) { return i8_ring_launch<ks(), dense8_scan_kernel<ks(), SAMPLE>>(a.nrb, st, a); });
 }
 // one query tile per wave: dense8_scan_kernel for the row width; 2 or 4 tiles (128-byte rows): dense8_scan_mt_kernel
 template <bool SAMPLE>
 static int dense8_scan_any(int row_bytes, int qt, const Dense8ScanArgs& a, hipStream_t st) {
+    using G = I8Geom<4>;
+    const dim3 grid((unsigned)(a.nrb * a.nqt)), block(G::WAVES * 64);
+    const size_t ring = (size_t)G::WAVES * G::NSTAGE * G::SLOT_BYTES;
     if (qt == 1) return dense8_scan_launch<SAMPLE>(row_bytes, a, st);
-    if (row_bytes == 128 && qt == 2) return dense8_scan_mt_launch_t<2, SAMPLE>(a, st);
-    if (row_bytes == 128 && qt == 4) return dense8_scan_mt_launch_t<4, SAMPLE>(a, st);
+    if (row_bytes == 128 && qt == 2) return launch_lds<dense8_scan_mt_kernel<2, SAMPLE>>(160 * 1024, grid, block, ring, st, a);
+    if (row_bytes == 128 && qt == 4) return launch_lds<dense8_scan_mt_kernel<4, SAMPLE>>(160 * 1024, grid, block, ring, st, a);
     return fail(SQ_ERR_INVALID, "int8 scan: %d query tiles per wave over %d-byte rows", qt, row_bytes);
 }
 // the three-launch form of a one-tile int8 call (sq_dense_i8.hpp): head and body per row width / metric
-template <int KS>
-static int dense8_head_launch_t(const Dense8HeadArgs& a, hipStream_t st) {
-    using G = I8Geom<KS>;
-    constexpr int ring = G::WAVES * G::NSTAGE * G::SLOT_BYTES;
-    // (the kernel has static LDS of its own: the attribute is the ring, not the CU's 160 KiB)
-    return launch_lds<dense8_head_kernel<KS>>(ring, dim3((unsigned)a.s.nrb), dim3(G::WAVES * 64), ring, st, a);
-}
 static int dense8_head_launch(int row_bytes, const Dense8HeadArgs& a, hipStream_t st) {
-    switch (row_bytes) {
-        case 128: return dense8_head_launch_t<4>(a, st);
-        case 256: return dense8_head_launch_t<8>(a, st);
-        case 512: return dense8_head_launch_t<16>(a, st);
-    }
-    return fail(SQ_ERR_INVALID, "int8 head: unsupported row width %d", row_bytes);
-}
-template <int KS, bool COSINE>
-static int dense8_body_launch_t(const Dense8ScanArgs& a, const Dense8TailArgs& t, hipStream_t st) {
-    using G = I8Geom<KS>;
-    constexpr int ring = G::WAVES * G::NSTAGE * G::SLOT_BYTES;
-    return launch_lds<dense8_body_kernel<KS, COSINE>>(ring, dim3((unsigned)a.nrb), dim3(G::WAVES * 64), ring, st, a, t);
+    return with_row8(row_bytes, [&](auto ks) { return i8_ring_launch<ks(), dense8_head_kernel<ks()>>(a.s.nrb, st, a); });
 }
 static int dense8_body_launch(int row_bytes, bool cosine, const Dense8ScanArgs& a, const Dense8TailArgs& t, hipStream_t st) {
-    switch (row_bytes) {
-        case 128: return cosine ? dense8_body_launch_t<4, true>(a, t, st) : dense8_body_launch_t<4, false>(a, t, st);
-        case 256: return cosine ? dense8_body_launch_t<8, true>(a, t, st) : dense8_body_launch_t<8, false>(a, t, st);
-        case 512: return cosine ? dense8_body_launch_t<16, true>(a, t, st) : dense8_body_launch_t<16, false>(a, t, st);
-    }
-    return fail(SQ_ERR_INVALID, "int8 body: unsupported row width %d", row_bytes);
+    return with_row8(row_bytes, [&](auto ks) {
+        return cosine ? i8_ring_launch<ks(), dense8_body_kernel<ks(), true>>(a.nrb, st, a, t)
+                      : i8_ring_launch<ks(), dense8_body_kernel<ks(), false>>(a.nrb, st, a, t);
+    });
 }
 static int i8_waves(int row_bytes) { return row_bytes == 512 ? I8Geom<16>::WAVES : I8Geom<4>::WAVES; }
 
@@ -388,66 +430,221 @@ static bool dense_mid_shape_ok(const DenseHandle* h) {
            (cosine ? h->cos_nx.p != nullptr : h->norms.p != nullptr);
 }
 
-// The int8 first stage of a call of up to 32 queries over rows of 513 to 8192 dimensions (sq_dense_i8_wide.hpp): query
-// prep, sample pass, threshold, full pass, second-level threshold, re-rank, select -- the wide bfloat16 chain with the
-// int8 kernels in the places of its prep and its two passes, and the int8 certificate (Dense8ThrPost, DenseFinalize*::lin)
-// in the place of the bfloat16 bound.
-static int dense8_wide_enqueue(DenseHandle* h, DenseSlot& s, const float* q, int nq, int k, int kk, void* out_dist, long long* out_idx,
-                               hipStream_t st, bool prof, u32 cap, u32* hs_dev, u32* hs_raw_dev) {
-    const long long n = h->n;
-    const int d = h->d, row8 = h->row8, ku = i8w_units(row8), qw = ku * I8W_UNIT;
-    const bool cosine = h->metric == SQ_METRIC_COSINE;
-    const size_t key_bytes = cosine ? sizeof(K128) : sizeof(u64);
-    const long long key_stride = (long long)cap;
-    const long long n_tiles = (n + TILE_ROWS - 1) / TILE_ROWS;
-    // every stride-th tile is sampled: the bfloat16 chain's balance of sample pass against re-rank (dense_enqueue)
-    long long stride = h->opt.sample_stride;
+// ---- rules the first-stage chains share
+// Every stride-th 32-row tile is sampled (the bfloat16 chain and the wide int8 chain).  The sample pass costs
+// ~ n * groups / stride, the re-rank + select ~ nq * stride * k (candidates per query ~ stride * k * slack); with
+// groups ~ nq / (32 qt) the balance is stride ~ sqrt(n / (qt k)), independent of the batch: 20 at 10 M rows, k = 100,
+// one query tile per wave (measured optimum 16-24; 8-12 with four tiles; 4 on a 1.25 M-row shard).
+static long long dense_tile_stride(const Options& o, long long n, long long n_tiles, int kk, int qt, bool cosine, u32 cap) {
+    long long stride = o.sample_stride;
     if (stride <= 0) {
-        stride = (long long)(20.0 * sqrt((double)n / 1e7 * 100.0 / (double)kk) / (cosine ? 1.9 : 1.0) + 0.5);
+        // (the float64 cosine re-rank costs ~3.6x the float32 L2 one per candidate: sqrt of that off the stride)
+        stride = (long long)(20.0 * sqrt((double)n / 1e7 * 100.0 / (double)kk / (double)qt) / (cosine ? 1.9 : 1.0) + 0.5);
         if (stride > 24) stride = 24;
         if (stride < 2) stride = 2;
-        if (stride > (long long)cap / (8ll * kk)) stride = (long long)cap / (8ll * kk);
+        if (stride > (long long)cap / (8ll * kk)) stride = (long long)cap / (8ll * kk);  // room in the key lists
     }
     if (stride > 64) stride = 64;
     if (stride < 1) stride = 1;
     while (stride > 1 && (n_tiles / stride) * 2 < 8ll * kk) stride >>= 1;
+    return stride;
+}
+// Non-temporal row stream ("dense_nt"): automatic mode turns it on for a copy far beyond the MALL (`auto_ok`: the int8
+// chain only with one query group -- several groups re-read the rows from L2) and leaves a head of `keep_mb_default` MB
+// ("dense_nt_keep_mb") on the default cache policy.
+static void dense_nt_policy(const Options& o, size_t copy_bytes, long long row_bytes, long long keep_mb_default, bool auto_ok, int& nt,
+                            long long& nt_from_row) {
+    const long long keep_mb = o.dense_nt_keep_mb > 0 ? o.dense_nt_keep_mb : keep_mb_default;
+    nt = o.dense_nt >= 0 ? o.dense_nt : (copy_bytes > ((size_t)512 << 20) && auto_ok ? 1 : 0);
+    nt_from_row = o.dense_nt == 0 ? 0x7fffffffffffffffll : o.dense_nt == 1 ? 0ll : (keep_mb << 20) / row_bytes;
+}
+// Workgroups of the full pass (returned) and of the sample pass.  One scan workgroup per CU fills the chip -- and
+// leaves nothing for the other call slot's short kernels (re-rank, select of the previous call; query prep, sample pass,
+// threshold of the next), whose workgroups need LDS of their own.  When the two slots run on their own streams the scan
+// takes three quarters of the CUs: alone it is as fast (HBM bound: 0.433 ms on 160 workgroups against 0.439 on 256 at
+// 10 M x 128), and the pipelined step drops from 0.50 to 0.46 ms (tools/step_sweep.py dense_blocks=...).
+// (one query tile group only: the multi-tile configurations are MFMA bound and want every CU; `own` > 0: the kernel's own
+// count where option dense_blocks leaves the choice)
+// Pipelined one-group calls: the sample pass is a scan kernel too (one workgroup wants most of a CU's LDS), so on
+// as many workgroups as the full pass it cannot run BESIDE the neighbouring call's full pass (192 of the 256
+// CUs) -- its tail queues behind that pass and the two scans of a step serialise (a 1.25 M-row shard: 16 + 63 us
+// of an 83 us step).  On the spare quarter of the CUs it runs wholly under the neighbour's full pass.
+static int dense_pass_blocks(const Options& o, bool use_event, int nqt, int cus, int own, int& nrb_sample) {
+    const bool pipelined = use_event && o.dense_async_streams == 2 && nqt == 1;
+    const int nrb = ((o.dense_blocks > 0 ? o.dense_blocks : own > 0 ? own : pipelined ? cus * 3 / 4 : cus) + 7) / 8 * 8;
+    nrb_sample = nrb;
+    if (pipelined && o.dense_blocks <= 0) {
+        const int sb = ((o.dense_sample_blocks > 0 ? o.dense_sample_blocks : (o.dense_sample_blocks < 0 ? nrb : cus - nrb)) + 7) / 8 * 8;
+        if (sb >= 8 && sb < nrb) nrb_sample = sb;
+    }
+    return nrb;
+}
+// The second-level threshold's scratch in the slot (sq_dense_tighten.hpp): [hist | raw thresholds | T'' | keys of T''],
+// a fixed layout (the histogram region never meets old thresholds).  A new allocation is wiped once;
+// dense_tighten_thr_kernel leaves the histogram clean.
+struct DenseTighten {
+    u32 *hist = nullptr, *thr2k = nullptr;
+    float *traw = nullptr, *thr2 = nullptr;
+};
+static int dense_tighten_scratch(DenseSlot& s, size_t entries, hipStream_t st, DenseTighten& t) {
+    SQ_TRY(s.wave_score.reserve(entries * 4));
+    SQ_TRY(s.tg.reserve((size_t)TG_CAP_Q * (TG_BINS + 3) * 4));
+    if (s.tg_zeroed != s.tg.p) {
+        SQ_HIP(hipMemsetAsync(s.tg.p, 0, s.tg.cap, st));
+        s.tg_zeroed = s.tg.p;
+    }
+    t.hist = s.tg.as<u32>();
+    t.traw = reinterpret_cast<float*>(t.hist + (size_t)TG_CAP_Q * TG_BINS);
+    t.thr2 = t.traw + TG_CAP_Q;
+    t.thr2k = reinterpret_cast<u32*>(t.thr2 + TG_CAP_Q);
+    return SQ_OK;
+}
+// an int8 stage takes a call although automatic mode had suspended it (dense_int8 = 1 on the handle): the filter is armed
+// again (and judged again from the next calls)
+static void dense8_rearm(DenseHandle* h) {
+    if (h->suspended8) {
+        h->suspended8 = false;
+        h->overflow8 = 0;
+    }
+}
+static constexpr u32 kWaveCap = 2048;   // entries of a wave's survivor segment
+
+// The survivors of a pass -- per-wave segments of (first row, mask, query) entries -- and where their keys go: exact
+// re-rank from the float32 rows (wave segments -> per-query keys), select, certify.
+// A re-rank workgroup takes `wpb` survivor segments of one scan workgroup (its waves share the query
+// group), 128 threads per segment (512 at most).  Many small workgroups win: the kernel is a chain of dependent
+// memory round trips per workgroup, not the per-query atomics (2 vs 8 segments: 37 vs 50 us at 10 M rows).
+struct DenseSurvivors {
+    const uint2* wave_out;
+    const u32* wave_cnt;
+    long long n_waves;
+    int wpb;
+    const float* q_al;   // the queries, [nq][ldq] float32
+    int ldq, nq;
+    void *keys, *out_keys;   // [nq][cap], [nq][k]
+    DevBuf* sort_tmp;
+    int debug = 0;
+    long long expect = 0;               // the select's hint: candidates per query
+    const float *wave_score = nullptr, *thr2 = nullptr;   // a second-level threshold (sq_dense_tighten.hpp): the entries' scores, T'' ...
+    const u32* thr2k = nullptr;                           // ... and its keys
+    hipEvent_t ev_rerank = nullptr;     // profiling: recorded between the re-rank and the select
+};
+// (e: the counters, thresholds, overflow flag and query norms the lists belong to, and the queries per scan workgroup)
+template <class M>
+static int dense_survivor_tail(const DenseHandle* h, const DenseCtx& e, const DenseSurvivors& v, int k, typename M::Fin fin, hipStream_t st) {
+    using K = typename M::Key;
+    const dim3 grid((unsigned)((v.n_waves + v.wpb - 1) / v.wpb)), block((unsigned)std::min(512, 128 * v.wpb));
+    const size_t lds = (e.group_q == TILE_ROWS && v.ldq <= 156) ? (size_t)32 * (v.ldq + 4) * 4 : 0;  // the query tile in LDS (rerank_block)
+    K* keys = static_cast<K*>(v.keys);
+    const double* cnx = M::cosine ? h->cos_nx.as<double>() : nullptr;
+    const double* cnq = M::cosine ? e.cnq : nullptr;
+    if (v.thr2)
+        SQ_TRY(launch<dense_rerank_filtered_kernel<K, M::cosine>>(grid, block, lds, st, h->db, h->ld, h->d, v.q_al, v.ldq, v.wave_out, v.wave_cnt,
+                                                                  kWaveCap, v.n_waves, v.wpb, v.nq, e.group_q, keys, e.cnt, e.cap, e.oflag, cnx, cnq,
+                                                                  v.debug, v.wave_score, v.thr2));
+    else if constexpr (M::cosine)
+        SQ_TRY(launch<dense_rerank_cos_kernel>(grid, block, lds, st, h->db, h->ld, h->d, v.q_al, v.ldq, v.wave_out, v.wave_cnt, kWaveCap, v.n_waves,
+                                               v.wpb, v.nq, e.group_q, keys, e.cnt, e.cap, e.oflag, cnx, cnq, v.debug));
+    else
+        SQ_TRY(launch<dense_rerank_l2_kernel>(grid, block, lds, st, h->db, h->ld, h->d, v.q_al, v.ldq, v.wave_out, v.wave_cnt, kWaveCap, v.n_waves,
+                                              v.wpb, v.nq, e.group_q, keys, e.cnt, e.cap, e.oflag, v.debug));
+    if (v.ev_rerank) SQ_HIP(hipEventRecord(v.ev_rerank, st));
+    fin.thr2k = v.thr2k;
+    return select_launch_t<K>(keys, e.cnt, e.cap, (long long)e.cap, k, v.nq, static_cast<K*>(v.out_keys), fin, st, *v.sort_tmp, v.expect);
+}
+static DenseSurvivors dense_survivors(const DevBuf& wave_out, const DevBuf& wave_cnt, const DevBuf& q_al, const DevBuf& keys, const DevBuf& out_keys,
+                                      DevBuf& sort_tmp, long long n_waves, int wpb, int ldq, int nq, const DenseTighten& tg = DenseTighten{}) {
+    DenseSurvivors v{};
+    v.wave_out = wave_out.as<uint2>();
+    v.wave_cnt = wave_cnt.as<u32>();
+    v.n_waves = n_waves;
+    v.wpb = wpb;
+    v.q_al = q_al.as<float>();
+    v.ldq = ldq;
+    v.nq = nq;
+    v.keys = keys.p;
+    v.out_keys = out_keys.p;
+    v.sort_tmp = &sort_tmp;
+    v.thr2 = tg.thr2;
+    v.thr2k = tg.thr2k;
+    return v;
+}
+// ... of a first-stage chain: the slot's lists (with a second-level threshold: its entries' scores), the call's queries
+static DenseSurvivors dense_slot_survivors(const DenseHandle* h, DenseSlot& s, long long n_waves, int wpb, int ldq, const DenseTighten& tg = DenseTighten{}) {
+    DenseSurvivors v = dense_survivors(s.wave_out, s.wave_cnt, s.q_al, s.keys, s.out_keys, s.sort_tmp, n_waves, wpb, ldq, s.call.nq, tg);
+    v.wave_score = tg.thr2 ? s.wave_score.as<float>() : nullptr;
+    v.debug = h->opt.dense_debug;
+    if (s.call.prof) v.ev_rerank = s.ev[4];
+    return v;
+}
+
+// ---- every row is a candidate (n <= cap): exact keys for all rows, no scan
+static int dense_small_enqueue(DenseHandle* h, DenseSlot& s, const DenseCtx& e) {
+    const long long n = h->n;
+    const int d = h->d;
+    DenseCall& c = s.call;
+    hipStream_t st = c.st;
+    SQ_TRY(s.keys.reserve((size_t)c.nq * e.key_stride * e.key_bytes));
+    SQ_TRY(launch<fill_u32_kernel>(dim3((c.nq_pad + 255) / 256), dim3(256), 0, st, e.cnt, (long long)c.nq_pad, (u32)n));
+    const dim3 grid((unsigned)((n + 255) / 256), c.nq);
+    if (c.prof) SQ_HIP(hipEventRecord(s.ev[1], st));
+    c.stats.scan_launches = 1;
+    c.stats.bytes_scanned = n * (long long)d * 4;
+    return by_metric(e.cosine, [&](auto m) {
+        using M = decltype(m);
+        using K = typename M::Key;
+        K* keys = s.keys.as<K>();
+        if constexpr (M::cosine)
+            SQ_TRY(launch<dense_exact_cos_kernel>(grid, dim3(256), 0, st, h->db, h->ld, d, c.q, nullptr, e.cnt, (u32)n, n, 0ll, keys, e.key_stride,
+                                                  h->cos_nx.as<double>(), e.cnq, nullptr, 0, h->deadp()));
+        else
+            SQ_TRY(launch<dense_exact_l2_kernel>(grid, dim3(256), (size_t)((d + 3) / 4 * 4) * 4, st, h->db, h->ld, d, c.q, nullptr, e.cnt, (u32)n, n,
+                                                 0ll, keys, e.key_stride, nullptr, 0, h->deadp()));
+        if (c.prof) SQ_HIP(hipEventRecord(s.ev[2], st));
+        auto fin = M::finalize(e, e.cnt, (u32)n, 0);
+        fin.cnt_out = e.hs_cnt_dev;
+        fin.dead = h->deadp();   // (the keys hold removed rows)
+        return select_launch_t<K>(keys, e.cnt, (u32)n, e.key_stride, c.k, c.nq, s.out_keys.as<K>(), fin, st, s.sort_tmp);
+    });
+}
+
+// The int8 first stage of a call of up to 32 queries over rows of 513 to 8192 dimensions (sq_dense_i8_wide.hpp): query
+// prep, sample pass, threshold, full pass, second-level threshold, re-rank, select -- the wide bfloat16 chain with the
+// int8 kernels in the places of its prep and its two passes, and the int8 certificate (Dense8ThrPost, DenseFinalize*::lin)
+// in the place of the bfloat16 bound.
+// (filter_ok: kk is inside the one-workgroup select; larger batches take the bfloat16 chain)
+static int dense8_wide_enqueue(DenseHandle* h, DenseSlot& s, const DenseCtx& e) {
+    const long long n = h->n;
+    DenseCall& c = s.call;
+    const int d = h->d, row8 = h->row8, ku = i8w_units(row8), qw = ku * I8W_UNIT;
+    hipStream_t st = c.st;
+    c.int8 = true;
+    dense8_rearm(h);
+    c.stats.scan_launches = 2;
+    c.stats.bytes_scanned = h->n_pad64 * ((long long)row8 + 4);
+    const long long n_tiles = (n + TILE_ROWS - 1) / TILE_ROWS;
+    const long long stride = dense_tile_stride(h->opt, n, n_tiles, e.kk, 1, e.cosine, e.cap);
     const long long ns_tiles = (n_tiles + stride - 1) / stride;
     const long long ns = ns_tiles * 2;   // one sample (a 16-row group minimum) per lane half and tile
     const int cus = cu_count(h->device);
     int nrb = h->opt.dense_blocks > 0 ? h->opt.dense_blocks : 2 * cus;   // (32 KB of LDS: two eight-wave workgroups per CU)
     nrb = (nrb + 7) / 8 * 8;
     const long long n_waves = (long long)nrb * WIDE_WAVES;
-    const u32 wave_cap = 2048;
     const int ldq = (d + 3) / 4 * 4;
     const bool tighten = h->opt.dense_tighten != 0;
     SQ_TRY(s.sample.reserve((size_t)TILE_ROWS * ns * 4));
-    SQ_TRY(s.keys.reserve((size_t)nq * key_stride * key_bytes));
+    SQ_TRY(s.keys.reserve((size_t)c.nq * e.key_stride * e.key_bytes));
     SQ_TRY(s.q8.reserve((size_t)2 * TILE_ROWS * qw));
     SQ_TRY(s.par8.reserve((size_t)TILE_ROWS * 8));
-    SQ_TRY(s.wave_out.reserve((size_t)n_waves * wave_cap * 8));
+    SQ_TRY(s.wave_out.reserve((size_t)n_waves * kWaveCap * 8));
     SQ_TRY(s.wave_cnt.reserve((size_t)n_waves * 8));
-    SQ_TRY(s.q_al.reserve((size_t)nq * ldq * 4));
-    u32 *tg_hist = nullptr, *tg_thr2k = nullptr;
-    float *tg_traw = nullptr, *tg_thr2 = nullptr;
-    if (tighten) {
-        SQ_TRY(s.wave_score.reserve((size_t)n_waves * wave_cap * 4));
-        SQ_TRY(s.tg.reserve((size_t)TG_CAP_Q * (TG_BINS + 3) * 4));
-        if (s.tg_zeroed != s.tg.p) {   // a new allocation: wiped once, dense_tighten_thr_kernel leaves the histogram clean
-            SQ_HIP(hipMemsetAsync(s.tg.p, 0, s.tg.cap, st));
-            s.tg_zeroed = s.tg.p;
-        }
-        tg_hist = s.tg.as<u32>();
-        tg_traw = reinterpret_cast<float*>(tg_hist + (size_t)TG_CAP_Q * TG_BINS);
-        tg_thr2 = tg_traw + TG_CAP_Q;
-        tg_thr2k = reinterpret_cast<u32*>(tg_thr2 + TG_CAP_Q);
-    }
-    u32* cnt = s.cnt.as<u32>();
-    float* thr = s.thr.as<float>();
-    double* qn2 = s.qn2.as<double>();
-    u32* oflag = s.oflag.as<u32>();
-    const float* centerp = (!cosine && h->center.p) ? h->center.as<float>() : nullptr;
-    hipLaunchKernelGGL(dense8_wide_prep_queries_kernel, dim3(TILE_ROWS), dim3(256), 0, st, q, nq, d, centerp, h->dx8, h->rmax8, h->xmax8,
-                       s.q8.as<signed char>(), qw, s.par8.as<float2>(), qn2, thr, cnt, oflag, s.q_al.as<float>(), ldq, cosine ? 1 : 0);
+    SQ_TRY(s.q_al.reserve((size_t)c.nq * ldq * 4));
+    DenseTighten tg;
+    if (tighten) SQ_TRY(dense_tighten_scratch(s, (size_t)n_waves * kWaveCap, st, tg));
+    const float* centerp = (!e.cosine && h->center.p) ? h->center.as<float>() : nullptr;
+    SQ_TRY(launch<dense8_wide_prep_queries_kernel>(dim3(TILE_ROWS), dim3(256), 0, st, c.q, c.nq, d, centerp, h->dx8, h->rmax8, h->xmax8,
+                                                   s.q8.as<signed char>(), qw, s.par8.as<float2>(), e.qn2, e.thr, e.cnt, e.oflag, s.q_al.as<float>(), ldq,
+                                                   e.cosine ? 1 : 0));
     Dense8WideArgs a{};
     a.scan8 = h->scan8.as<signed char>();
     a.nrow = h->nrow8.as<float>();
@@ -457,10 +654,10 @@ static int dense8_wide_enqueue(DenseHandle* h, DenseSlot& s, const float* q, int
     a.n_tiles = n_tiles;
     a.qs8 = s.q8.as<signed char>();
     a.par = s.par8.as<float2>();
-    a.thr = thr;
+    a.thr = e.thr;
     a.wave_out = s.wave_out.as<uint2>();
     a.wave_cnt = s.wave_cnt.as<u32>();
-    a.wave_cap = wave_cap;
+    a.wave_cap = kWaveCap;
     a.sample_out = s.sample.as<float>();
     a.ns = ns;
     // sample pass
@@ -469,66 +666,430 @@ static int dense8_wide_enqueue(DenseHandle* h, DenseSlot& s, const float* q, int
     a.nrb = nrb;
     if (ns_tiles < (long long)nrb * WIDE_WAVES) a.nrb = (int)(((ns_tiles + WIDE_WAVES - 1) / WIDE_WAVES + 7) / 8 * 8);
     SQ_TRY(launch<dense8_wide_scan_kernel<true>>(dim3((unsigned)a.nrb), dim3(WIDE_WAVES * 64), 0, st, a));
-    const Dense8WideThrPost tp{Dense8ThrPost{s.par8.as<float2>(), qn2}, tg_traw};
-    hipLaunchKernelGGL((kth_threshold_f32_kernel<Dense8WideThrPost>), dim3(nq), dim3(1024), 0, st, a.sample_out, ns, kk, thr, tp);
+    const Dense8WideThrPost tp{Dense8ThrPost{s.par8.as<float2>(), e.qn2}, tg.traw};
+    SQ_TRY(launch<kth_threshold_f32_kernel<Dense8WideThrPost>>(dim3(c.nq), dim3(1024), 0, st, a.sample_out, ns, e.kk, e.thr, tp));
     // full pass
     a.tile_step = 1;
     a.n_sel = n_tiles;
     a.nrb = nrb;
     a.wave_score = tighten ? s.wave_score.as<float>() : nullptr;
-    if (prof) SQ_HIP(hipEventRecord(s.ev[1], st));
+    if (c.prof) SQ_HIP(hipEventRecord(s.ev[1], st));
     SQ_TRY(launch<dense8_wide_scan_kernel<false>>(dim3((unsigned)nrb), dim3(WIDE_WAVES * 64), 0, st, a));
-    if (prof) SQ_HIP(hipEventRecord(s.ev[2], st));
+    if (c.prof) SQ_HIP(hipEventRecord(s.ev[2], st));
     if (tighten) {
         const Dense8WideThrPost tp2{tp.base, nullptr};   // (the same slack rule, nothing else)
-        hipLaunchKernelGGL(dense_tighten_hist_kernel, dim3(64, 1), dim3(256), 0, st, a.wave_out, a.wave_score, a.wave_cnt, wave_cap, n_waves,
-                           (const float*)thr, (const float*)tg_traw, TILE_ROWS, tg_hist);
-        hipLaunchKernelGGL((dense_tighten_thr_kernel<Dense8WideThrPost>), dim3(1), dim3(64), 0, st, tg_hist, (const float*)thr,
-                           (const float*)tg_traw, nq, TILE_ROWS, kk, tp2, tg_thr2, tg_thr2k);
+        SQ_TRY(launch<dense_tighten_hist_kernel>(dim3(64, 1), dim3(256), 0, st, a.wave_out, a.wave_score, a.wave_cnt, kWaveCap, n_waves,
+                                                 (const float*)e.thr, (const float*)tg.traw, TILE_ROWS, tg.hist));
+        SQ_TRY(launch<dense_tighten_thr_kernel<Dense8WideThrPost>>(dim3(1), dim3(64), 0, st, tg.hist, (const float*)e.thr, (const float*)tg.traw, c.nq,
+                                                                   TILE_ROWS, e.kk, tp2, tg.thr2, tg.thr2k));
     }
     // exact re-rank of the survivors from the float32 rows, select, certify: the bfloat16 chain's kernels
-    const int wpb = 2;
-    const unsigned rr_threads = 128 * wpb;
-    const size_t rr_lds = ldq <= 156 ? (size_t)32 * (ldq + 4) * 4 : 0;
-    const unsigned gxr = (unsigned)((n_waves + wpb - 1) / wpb);
-    const double* cnx = h->cos_nx.as<double>();
-    const double* cnq = s.cos_nq.as<double>();
-    if (cosine) {
-        if (tighten)
-            hipLaunchKernelGGL((dense_rerank_filtered_kernel<K128, true>), dim3(gxr), dim3(rr_threads), rr_lds, st, h->db, h->ld, d,
-                               s.q_al.as<float>(), ldq, a.wave_out, a.wave_cnt, wave_cap, n_waves, wpb, nq, TILE_ROWS, s.keys.as<K128>(), cnt,
-                               cap, oflag, cnx, cnq, h->opt.dense_debug, (const float*)a.wave_score, (const float*)tg_thr2);
-        else
-            hipLaunchKernelGGL(dense_rerank_cos_kernel, dim3(gxr), dim3(rr_threads), rr_lds, st, h->db, h->ld, d, s.q_al.as<float>(), ldq,
-                               a.wave_out, a.wave_cnt, wave_cap, n_waves, wpb, nq, TILE_ROWS, s.keys.as<K128>(), cnt, cap, oflag, cnx, cnq,
-                               h->opt.dense_debug);
-        if (prof) SQ_HIP(hipEventRecord(s.ev[4], st));
-        DenseFinalizeCos fin{cnt, cap, kk, h->id_base, thr, 0.0, 1, (double*)out_dist, out_idx, hs_dev, hs_raw_dev, oflag, 0};
+    DenseSurvivors v = dense_slot_survivors(h, s, n_waves, 2, ldq, tg);
+    return by_metric(e.cosine, [&](auto m) {
+        using M = decltype(m);
+        auto fin = e.filter_fin<M>();
         fin.lin = s.par8.as<float2>();
-        if (tighten) fin.thr2k = tg_thr2k;
-        return select_launch_t<K128>(s.keys.as<K128>(), cnt, cap, key_stride, k, nq, s.out_keys.as<K128>(), fin, st, s.sort_tmp);
+        v.expect = M::cosine ? 0 : 4 * stride * e.kk;
+        return dense_survivor_tail<M>(h, e, v, c.k, fin, st);
+    });
+}
+
+// The int8 chain eagerly or as a captured graph.  A launch costs ~2.8 us of host time
+// (tools/micro/launch_cost.hip: 19.3 us for a chain of seven, 5.6-6.3 us for one hipGraphLaunch of the same chain; in
+// this call 20 against 9.5 us, tools/host_sections.py).  It does not shorten a 1.25 M-row shard's ~55 us step -- that
+// is the latency of the chain itself, three deep -- but frees the host thread for the gather / merge work of a
+// sharded search.  The slot's first call of a shape runs eagerly (it sizes the workspace and sets the kernels'
+// attributes), the second captures, later ones launch the graph; the caller's pointers travel through a pinned
+// block (DenseCallPtrs), which `chain(stream, ind)` hands to its first and last kernel.
+// `by_value`: everything the captured launches were given by value (shapes, the slot's and the handle's buffers).
+template <class Chain>
+static int dense8_launch_chain(DenseHandle* h, DenseSlot& s, std::initializer_list<u64> by_value, Chain&& chain) {
+    const DenseCall& c = s.call;
+    hipStream_t st = c.st;
+    if (c.use_event && !c.prof && h->opt.dense_graph != 0 && !h->graph_broken && st != nullptr && st == s.own) {   // (never a capture on the caller's stream)
+        u64 key = 0xcbf29ce484222325ull;
+        for (u64 v : by_value) key = (key ^ v) * 0x100000001b3ull;
+        if (key == 0) key = 1;
+        if (s.gexec && s.gkey != key) {
+            (void)hipGraphExecDestroy(s.gexec);
+            s.gexec = nullptr;
+        }
+        if (!s.gexec && s.seen_key == key) {   // second call of this shape on this slot: capture
+            SQ_TRY(s.call_ptrs.reserve(sizeof(DenseCallPtrs)));
+            void* ind_dev = nullptr;
+            SQ_TRY(s.call_ptrs.device_ptr(&ind_dev));
+            // (a capture that fails is no reason to fail the search: the handle goes back to eager launches for good)
+            hipGraph_t g = nullptr;
+            bool ok = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess;
+            if (ok) {
+                const int rc = chain(st, static_cast<const DenseCallPtrs*>(ind_dev));
+                const hipError_t ec = hipStreamEndCapture(st, &g);
+                ok = rc == SQ_OK && ec == hipSuccess && g != nullptr;
+            }
+            if (ok) ok = hipGraphInstantiate(&s.gexec, g, nullptr, nullptr, 0) == hipSuccess;
+            if (g) (void)hipGraphDestroy(g);
+            if (!ok) {
+                (void)hipGetLastError();
+                s.gexec = nullptr;
+                h->graph_broken = true;
+            } else {
+                s.gkey = key;
+                if (getenv("SQ_INT8_REPORT")) fprintf(stderr, "[smqtk_hip] call graph captured (%d queries, k = %d)\n", c.nq, c.k);
+            }
+        }
+        s.seen_key = key;
+        if (s.gexec) {
+            *static_cast<DenseCallPtrs*>(s.call_ptrs.p) = DenseCallPtrs{c.q, c.out_dist, c.out_idx};
+            SQ_HIP(hipGraphLaunch(s.gexec, st));
+            return SQ_OK;
+        }
     }
-    if (tighten)
-        hipLaunchKernelGGL((dense_rerank_filtered_kernel<u64, false>), dim3(gxr), dim3(rr_threads), rr_lds, st, h->db, h->ld, d,
-                           s.q_al.as<float>(), ldq, a.wave_out, a.wave_cnt, wave_cap, n_waves, wpb, nq, TILE_ROWS, s.keys.as<u64>(), cnt, cap,
-                           oflag, (const double*)nullptr, (const double*)nullptr, h->opt.dense_debug, (const float*)a.wave_score,
-                           (const float*)tg_thr2);
-    else
-        hipLaunchKernelGGL(dense_rerank_l2_kernel, dim3(gxr), dim3(rr_threads), rr_lds, st, h->db, h->ld, d, s.q_al.as<float>(), ldq,
-                           a.wave_out, a.wave_cnt, wave_cap, n_waves, wpb, nq, TILE_ROWS, s.keys.as<u64>(), cnt, cap, oflag,
-                           h->opt.dense_debug);
-    if (prof) SQ_HIP(hipEventRecord(s.ev[4], st));
-    DenseFinalizeL2 fin{cnt, cap, kk, h->id_base, thr, qn2, 0.0, 1, (float*)out_dist, out_idx, hs_dev, hs_raw_dev, oflag, 0};
-    fin.lin = s.par8.as<float2>();
-    if (tighten) fin.thr2k = tg_thr2k;
-    return select_launch_t<u64>(s.keys.as<u64>(), cnt, cap, key_stride, k, nq, s.out_keys.as<u64>(), fin, st, s.sort_tmp, 4 * stride * kk);
+    return chain(st, nullptr);
+}
+
+// ---- the int8 first-stage filter (sq_dense_i8.hpp): half the bytes per row, measured error bound
+static int dense8_enqueue(DenseHandle* h, DenseSlot& s, const DenseCtx& e) {
+    const long long n = h->n;
+    DenseCall& c = s.call;
+    const int d = h->d;
+    c.int8 = true;
+    dense8_rearm(h);
+    // (128-byte rows stream in ring units of 64 rows on eight waves.  Two other geometries were built and measured --
+    // commit 5048766: 128-row units on four waves 0.197 against 0.204 ms per pass alone but 0.244-0.251 against 0.223-0.226 ms
+    // per pipelined step; 32-row units on sixteen waves 0.236 -- and removed again.)
+    const int row8 = h->row8, unit_rows = i8_unit_rows(row8), spu = 2 * (unit_rows / 32), waves8 = i8_waves(row8);   // samples per unit
+    const long long n_units = (n + unit_rows - 1) / unit_rows;
+    long long stride = h->opt.sample_stride;
+    if (stride <= 0) {
+        // units of 64 rows, four samples per unit: the bf16 path's cost model in units of two tiles
+        // (measured at 10 M x 128, k = 100: 0.293 / 0.269 / 0.262 / 0.258 / 0.257 / 0.257 / 0.263 ms per step at 6 / 8 / 10 / 12 / 16 / 20 / 24)
+        // 256- and 512-byte rows: flat from 8 to 14, best at 10 (0.471 / 0.988 ms per step at 10 M x 256 / 512); the float64 cosine
+        // re-rank costs ~3.6x the float32 one per candidate: sqrt of that off the stride, as in the bf16 path
+        stride = (long long)((row8 == 128 ? 14.0 : 10.0) * sqrt((double)n / 1e7 * 100.0 / (double)e.kk / (double)e.qt) / (e.cosine ? 1.9 : 1.0) + 0.5);
+        if (stride > 16) stride = 16;
+        // The fused call with the tightened threshold (sq_dense_i8.hpp): the sample only has to keep the first-level
+        // entries inside the wave segments -- what is re-ranked no longer depends on it -- so it is several times sparser
+        const bool will_tighten = h->opt.dense_fused != 0 && h->opt.dense_tighten != 0 && e.qt == 1 && e.nqt == 1;
+        if (will_tighten) {
+            stride = (long long)(40.0 * sqrt((double)n / 1e7 * 100.0 / (double)e.kk) + 0.5);
+            if (stride > 64) stride = 64;
+        }
+        if (stride < 1) stride = 1;
+        if (stride > (long long)e.cap / (16ll * e.kk)) stride = std::max<long long>(1, (long long)e.cap / (16ll * e.kk));
+    }
+    while (stride > 1 && (n_units / stride) * spu < 8ll * e.kk) stride >>= 1;
+    const long long ns_units = (n_units + stride - 1) / stride;
+    const long long ns = ns_units * spu;
+    SQ_TRY(s.keys.reserve((size_t)c.nq * e.key_stride * e.key_bytes));
+    SQ_TRY(s.q8.reserve((size_t)2 * c.nq_pad * row8));
+    SQ_TRY(s.par8.reserve((size_t)c.nq_pad * 8));
+    const int cus = cu_count(h->device);
+    int nrb_sample = 0;
+    const int nrb = dense_pass_blocks(h->opt, c.use_event, e.nqt, cus, 0, nrb_sample);
+    const long long n_waves = (long long)nrb * e.nqt * waves8;
+    const int ldq = (d + 3) / 4 * 4;
+    SQ_TRY(s.wave_out.reserve((size_t)n_waves * kWaveCap * 8));
+    SQ_TRY(s.wave_cnt.reserve((size_t)n_waves * 8));
+    SQ_TRY(s.q_al.reserve((size_t)c.nq * ldq * 4));
+    const float* centerp = (!e.cosine && h->center.p) ? h->center.as<float>() : nullptr;
+    Dense8ScanArgs a{};
+    a.scan8 = h->scan8.as<signed char>();
+    a.nrow = h->nrow8.as<float>();
+    a.n = n;
+    a.n_units = n_units;
+    a.qs8 = s.q8.as<signed char>();
+    a.par = s.par8.as<float2>();
+    a.thr = e.thr;
+    a.wave_out = s.wave_out.as<uint2>();
+    a.wave_cnt = s.wave_cnt.as<u32>();
+    a.wave_cap = kWaveCap;
+    a.sample_out = s.sample.as<float>();
+    a.ns = ns;
+    a.nqt = e.nqt;
+    a.plane_rows = c.nq_pad;
+    a.debug = h->opt.dense_debug;
+    // (cacheable head: 32-64 MB measured best here -- 0.244 ms per step at 10 M rows against 0.250 at the bf16 copy's 192 MB)
+    dense_nt_policy(h->opt, (size_t)h->n_pad64 * row8, row8, 64, e.nqt == 1, a.nt, a.nt_from_row);
+    if (ns_units < (long long)nrb_sample * waves8) nrb_sample = (int)(((ns_units + waves8 - 1) / waves8 + 7) / 8 * 8);
+    // Three launches instead of six (sq_dense_i8.hpp, "a call in three launches"): one query tile, and a head grid whose
+    // M = workgroups x waves x 2 lane minima per query number at least 4 k (the threshold is then within a few per cent of
+    // the k-th smallest sample) and at most 2048 (what the last workgroup's waves hold in registers).
+    bool fused = h->opt.dense_fused != 0 && e.qt == 1 && e.nqt == 1 && ns_units >= 2ll * e.kk;
+    const bool tighten = fused && h->opt.dense_tighten != 0;
+    if (fused) {
+        const int lanes_per_wg = waves8 * 2;
+        const int wg_min = ((4 * e.kk + lanes_per_wg - 1) / lanes_per_wg + 7) / 8 * 8, wg_max = 2048 / lanes_per_wg;
+        if (wg_min > wg_max || wg_min > cus)
+            fused = false;
+        else
+            nrb_sample = std::min(std::max(nrb_sample, wg_min), std::min(wg_max, (cus + 7) / 8 * 8));
+    }
+    // minima a head workgroup hands over per query: the k best of a call fall on a workgroup k / workgroups at a time
+    int keep8 = waves8 * 2;
+    if (fused) {
+        const double per_wg = (double)e.kk / nrb_sample;
+        if (per_wg <= 1.7 && keep8 > 4) keep8 = 4;
+        else if (per_wg <= 4.5 && keep8 > 8) keep8 = 8;
+    }
+    const long long lane_m = (long long)nrb_sample * keep8;
+    SQ_TRY(s.sample.reserve(fused ? (size_t)TILE_ROWS * lane_m * 4 : (size_t)c.nq_pad * ns * 4));
+    a.sample_out = s.sample.as<float>();
+    if (fused) {
+        SQ_TRY(s.wave_score.reserve((size_t)n_waves * kWaveCap * 4));
+        SQ_TRY(s.hist8.reserve((size_t)I8_HIST_WORDS * 4));
+        a.wave_score = s.wave_score.as<float>();
+        a.hist = s.hist8.as<u32>();
+    }
+    int wpb = 2;   // survivor segments per re-rank workgroup: four at the most here
+    if (!e.cosine && h->opt.dense_rerank_segments > 0 && waves8 % h->opt.dense_rerank_segments == 0 && h->opt.dense_rerank_segments <= 4)
+        wpb = h->opt.dense_rerank_segments;
+    const double* cnx = h->cos_nx.as<double>();
+    // the chain of three or six launches
+    auto chain = [&](hipStream_t cs, const DenseCallPtrs* ind) -> int {
+        if (fused) {
+            // head: query prep + sample pass (lane minima) + thresholds by the last workgroup
+            Dense8HeadArgs ha{};
+            ha.s = a;
+            ha.s.unit_step = stride;
+            ha.s.n_sel = ns_units;
+            ha.s.nrb = nrb_sample;
+            ha.q = c.q;
+            ha.nq = c.nq;
+            ha.d = d;
+            ha.center = centerp;
+            ha.dx = h->dx8;
+            ha.r_max = h->rmax8;
+            ha.x_max = h->xmax8;
+            ha.cosine = e.cosine ? 1 : 0;
+            ha.qn2 = e.qn2;
+            ha.cnt = e.cnt;
+            ha.oflag = e.oflag;
+            ha.q_al = s.q_al.as<float>();
+            ha.ldq = ldq;
+            ha.ind = ind;
+            ha.lane_min = s.sample.as<float>();
+            ha.keep = keep8;
+            ha.kk = e.kk;
+            SQ_TRY(dense8_head_launch(row8, ha, cs));
+            // body: the full pass; its workgroups re-rank their own survivors when the stream has drained
+            Dense8ScanArgs b = a;
+            b.unit_step = 1;
+            b.n_sel = n_units;
+            b.nrb = nrb;
+            Dense8TailArgs ta{h->db, h->ld, d, s.q_al.as<float>(), ldq, c.nq, s.keys.p, e.cnt, e.cap, e.oflag, cnx, e.cnq, h->opt.dense_debug, e.qn2, e.kk,
+                              tighten ? 1 : 0, nullptr};
+            s.clk8_wgs = 0;
+            if ((h->opt.dense_debug & 8192) && !c.use_event) {   // (blocking calls only: read and printed by dense_body_clocks)
+                SQ_TRY(s.clk8.reserve((size_t)nrb * 64));
+                SQ_HIP(hipMemsetAsync(s.clk8.p, 0, (size_t)nrb * 64, cs));
+                ta.clk = s.clk8.as<long long>();
+                s.clk8_wgs = nrb;
+            }
+            if (c.prof) SQ_HIP(hipEventRecord(s.ev[1], cs));
+            SQ_TRY(dense8_body_launch(row8, e.cosine, b, ta, cs));
+            if (c.prof) {
+                SQ_HIP(hipEventRecord(s.ev[2], cs));
+                SQ_HIP(hipEventRecord(s.ev[4], cs));
+            }
+            return by_metric(e.cosine, [&](auto m) {
+                using M = decltype(m);
+                using K = typename M::Key;
+                auto fin = e.filter_fin<M>();
+                fin.lin = s.par8.as<float2>();
+                fin.ind = ind;
+                if (tighten) fin.thr2k = a.hist + TILE_ROWS * I8_HIST_BINS;
+                fin.cnt_shift = I8_CNT_SHIFT;
+                return select_launch_t<K>(s.keys.as<K>(), e.cnt, e.cap, e.key_stride, c.k, c.nq, s.out_keys.as<K>(), fin, cs, s.sort_tmp, 8 * stride * e.kk,
+                                          I8_CNT_SHIFT);
+            });
+        }
+        SQ_TRY(with_row8(row8, [&](auto ks) {
+            return launch<dense8_prep_queries_kernel<decltype(ks)::value / 2>>(dim3(c.nq_pad / 4), dim3(64), 0, cs, c.q, c.nq, d, centerp, h->dx8, h->rmax8,
+                                                                               h->xmax8, s.q8.as<signed char>(), s.par8.as<float2>(), e.qn2, e.thr, e.cnt,
+                                                                               e.oflag, s.q_al.as<float>(), ldq, ind, e.cosine ? 1 : 0, c.nq_pad);
+        }));
+        Dense8ScanArgs b = a;
+        b.unit_step = stride;   // sample pass (on the CUs the pipelined full pass leaves free)
+        b.n_sel = ns_units;
+        b.nrb = nrb_sample;
+        SQ_TRY(dense8_scan_any<true>(row8, e.qt, b, cs));
+        SQ_TRY(launch<kth_threshold_f32_kernel<Dense8ThrPost>>(dim3(c.nq), dim3(1024), 0, cs, a.sample_out, ns, e.kk, e.thr,
+                                                               Dense8ThrPost{s.par8.as<float2>(), e.qn2}));
+        b.unit_step = 1;        // full pass
+        b.n_sel = n_units;
+        b.nrb = nrb;
+        if (c.prof) SQ_HIP(hipEventRecord(s.ev[1], cs));
+        SQ_TRY(dense8_scan_any<false>(row8, e.qt, b, cs));
+        if (c.prof) SQ_HIP(hipEventRecord(s.ev[2], cs));
+        DenseSurvivors v = dense_slot_survivors(h, s, n_waves, wpb, ldq);
+        v.expect = 8 * stride * e.kk;
+        return by_metric(e.cosine, [&](auto m) {
+            using M = decltype(m);
+            auto fin = e.filter_fin<M>();
+            fin.lin = s.par8.as<float2>();
+            fin.ind = ind;
+            return dense_survivor_tail<M>(h, e, v, c.k, fin, cs);
+        });
+    };
+    c.stats.scan_launches = 2;
+    c.stats.bytes_scanned = h->n_pad64 * ((long long)row8 + 4) * e.nqt;
+    return dense8_launch_chain(
+        h, s,
+        {(u64)(fused ? 1 : 0), (u64)(tighten ? 1 : 0), (u64)(uintptr_t)s.wave_score.p, (u64)(uintptr_t)s.hist8.p, (u64)lane_m, (u64)c.nq, (u64)c.k, (u64)row8,
+         (u64)e.qt, (u64)e.nqt, (u64)wpb, (u64)stride, (u64)nrb, (u64)nrb_sample, (u64)ns, (u64)a.nt, (u64)a.nt_from_row, (u64)n, (u64)h->n_live, (u64)e.cap,
+         (u64)h->opt.dense_debug, (u64)h->id_base, (u64)(uintptr_t)c.st, (u64)(uintptr_t)h->db, (u64)(uintptr_t)centerp, (u64)(uintptr_t)h->scan8.p,
+         (u64)(uintptr_t)h->nrow8.p, (u64)(uintptr_t)s.q8.p, (u64)(uintptr_t)s.par8.p, (u64)(uintptr_t)s.sample.p, (u64)(uintptr_t)s.keys.p,
+         (u64)(uintptr_t)s.wave_out.p, (u64)(uintptr_t)s.wave_cnt.p, (u64)(uintptr_t)s.q_al.p, (u64)(uintptr_t)e.cnt, (u64)(uintptr_t)e.thr,
+         (u64)(uintptr_t)e.qn2, (u64)(uintptr_t)e.oflag, (u64)(uintptr_t)s.out_keys.p, (u64)(uintptr_t)e.hs_cnt_dev, (u64)(uintptr_t)cnx,
+         (u64)(uintptr_t)e.cnq, (u64)(e.cosine ? 1 : 0)},
+        chain);
+}
+
+// ---- the bfloat16 chain: sample pass, threshold, full pass, [second-level threshold,] re-rank, select
+static int dense_bf16_enqueue(DenseHandle* h, DenseSlot& s, const DenseCtx& e) {
+    const long long n = h->n;
+    DenseCall& c = s.call;
+    const int d = h->d, d_pad = h->d_pad;
+    hipStream_t st = c.st;
+    uint4* qs = s.q_scaled.as<uint4>();
+    // error bound of the bf16 filter score (sq_dense_exact.hpp filter_eps, DESIGN.md 4.1):
+    //   products: |x q' - x_hi (q'_hi + q'_lo)| <= (2^-8 + 2^-15) |x||q'|, q' = -2q  ->  eps_a = 2^-7 + 2^-14 (times X|q|)
+    //             (cosine: unit vectors and q' = -q^ without the factor 2: half of that)
+    //   float32 accumulation of 2d+1 terms and the float32 norm                     ->  eps_b = (3d+8) 2^-23
+    //   one query plane: |x q' - x_hi q'_hi| <= (2^-8 + 2^-8 + 2^-16) |x||q'|                 ->  eps_a = 2^-6 + 2^-13
+    const double eps_a = (e.qp == 2 ? kEpsA2 : kEpsA1) * (e.cosine ? 0.5 : 1.0);
+    const double eps_b = dense_eps_b(d_pad);
+    const long long n_tiles = (n + TILE_ROWS - 1) / TILE_ROWS;
+    const long long stride = dense_tile_stride(h->opt, n, n_tiles, e.kk, e.qt, e.cosine, e.cap);
+    const long long ns_tiles = (n_tiles + stride - 1) / stride;
+    // one sample (a 16-row group minimum) per lane half per tile; the four-tile sample pass writes runs of four
+    // tiles ([query][half][tiles rounded up to 4], +inf in the padding: dense_scan_kernel CHUNK)
+    const bool sample_runs = e.qt == 4 && e.qp == 1 && d_pad == KT;
+    const long long ns = (sample_runs ? (ns_tiles + 3) / 4 * 4 : ns_tiles) * 2;
+    SQ_TRY(s.sample.reserve((size_t)c.nq_pad * ns * 4));
+    SQ_TRY(s.keys.reserve((size_t)c.nq * e.key_stride * e.key_bytes));
+    const int cus = cu_count(h->device);
+    // (the wide kernel, 122 registers and 32 KB of LDS: two eight-wave workgroups per CU -- twice the row bytes in flight;
+    // two tiles per wave: one workgroup per CU)
+    int nrb_sample = 0;
+    const int nrb = dense_pass_blocks(h->opt, c.use_event, e.nqt, cus, d_pad <= RING_MAX_DPAD ? 0 : e.qt == 1 ? 2 * cus : cus, nrb_sample);
+    const int wv = d_pad > RING_MAX_DPAD ? WIDE_WAVES : scan_geometry(h->opt, d_pad, e.qt, e.qp).waves;
+    // survivors leave the scan as per-wave segments; the re-rank kernel turns them into per-query key lists
+    const long long n_waves = (long long)nrb * e.nqt * wv;
+    const int ldq = (d + 3) / 4 * 4;
+    SQ_TRY(s.wave_out.reserve((size_t)n_waves * kWaveCap * 8));
+    SQ_TRY(s.wave_cnt.reserve((size_t)n_waves * 8));
+    SQ_TRY(s.q_al.reserve((size_t)c.nq * ldq * 4));
+    // rows beyond the ring kernels: a second-level threshold between the pass and the re-rank (sq_dense_tighten.hpp).
+    // (The ring kernels do not store their entries' scores: the few instructions that would in dense_scan_kernel's
+    // emission path changed the answers of its hand-scheduled multi-tile builds -- one query of a hundred lost the
+    // survivors of its last row tiles -- and were taken out again; tools/tighten_debug.py.  In the compiler-scheduled
+    // one-tile builds alone they were correct but not worth it: 10 M x 128 without the int8 copy, 3.3 k -> 2.1 k rows
+    // re-ranked per query, 0.424 -> 0.451 ms per step: two more launches against 512-byte gathers.)
+    const bool wide_tighten = h->opt.dense_tighten != 0 && d_pad > RING_MAX_DPAD && e.group_q <= TG_MAX_GROUP && c.nq_pad <= TG_CAP_Q;
+    DenseTighten tg;
+    if (wide_tighten) SQ_TRY(dense_tighten_scratch(s, (size_t)n_waves * kWaveCap, st, tg));
+    // L2, one query tile per wave (the HBM-bound configuration a pipelined step runs): no prep launch -- the scan
+    // kernels build the planes of their query tile themselves and the threshold kernel's prologue does the rest
+    // (DenseScanArgs::raw_q, DenseThrPost).  The head of a call is then sample pass -> threshold: on a 1.25 M-row
+    // shard the three-launch head (prep 6-27 us beside the neighbours' kernels, sample, threshold) no longer
+    // fitted under the previous call's 59 us scan, and the scans did not run back to back.
+    const bool fused_prep = !e.cosine && e.qt == 1 && e.qp == 2 && h->opt.dense_fused_prep != 0 && d_pad <= RING_MAX_DPAD;
+    const float* centerp = h->center.p ? h->center.as<float>() : nullptr;
+    if (!fused_prep)
+        SQ_TRY(launch<dense_prep_queries_kernel>(dim3(c.nq_pad), dim3(256), 0, st, c.q, c.nq, d, d_pad, h->metric, qs, e.qn2, e.thr, e.cnt, e.oflag,
+                                                 s.q_al.as<float>(), ldq, centerp));
+    DenseScanArgs a{};
+    if (fused_prep) {
+        a.raw_q = c.q;
+        a.raw_nq = c.nq;
+        a.raw_d = d;
+        a.center = centerp;
+    }
+    a.scan = h->scan.as<uint4>();
+    a.norms = e.cosine ? nullptr : (e.qp == 1 ? h->norms1.as<float>() : h->norms.as<float>());  // n' of this plane count
+    a.norm_step = 1;
+    // non-temporal stream (32 queries, pipelined step): 10 M rows 0.456 -> 0.401 ms, 5 M 0.251 -> 0.227, 2.5 M 0.147 ->
+    // 0.139.  One-tile kernel: everything behind a cacheable head of 192 MB ("dense_nt_keep_mb"); multi-tile kernels
+    // with one query group: their non-temporal build when the copy is far beyond the MALL.
+    dense_nt_policy(h->opt, (size_t)h->n_pad * d_pad * 2, (long long)d_pad * 2, 192, true, a.nt, a.nt_from_row);
+    if (e.cosine && (e.qt > 1 || e.qp == 1)) {  // the AGPR configurations always stream a norm piece
+        a.norms = h->zeros.as<float>();
+        a.norm_step = 0;
+    }
+    a.n = n;
+    a.n_tiles = n_tiles;
+    a.qs = qs;
+    a.thr = e.thr;
+    a.wave_out = s.wave_out.as<uint2>();
+    a.wave_cnt = s.wave_cnt.as<u32>();
+    a.wave_cap = kWaveCap;
+    a.sample_out = s.sample.as<float>();
+    a.ns = ns;
+    a.nqt = e.nqt;
+    a.debug = h->opt.dense_debug;
+    // sample pass
+    a.tile_step = stride;
+    a.n_sel = ns_tiles;
+    a.nrb = nrb_sample;
+    {
+        const long long work = sample_runs ? (ns_tiles + 3) / 4 : ns_tiles;  // runs / tiles a wave takes at a time
+        if (work < (long long)nrb * wv) a.nrb = (int)(((work + wv - 1) / wv + 7) / 8 * 8);
+    }
+    SQ_TRY(scan_launch<true>(h->opt, a, d_pad, e.qt, e.qp, st));
+    DenseThrPost tp{e.qn2, e.cosine ? 1 : 0, filter_bound(e.cosine ? 1 : 0, eps_a, eps_b, h->xn2_max)};
+    tp.traw_out = tg.traw;
+    if (fused_prep) {
+        tp.raw_q = c.q;
+        tp.nq = c.nq;
+        tp.nq_pad = c.nq_pad;
+        tp.d = d;
+        tp.ldq = ldq;
+        tp.center = centerp;
+        tp.qn2_out = e.qn2;
+        tp.thr_out = e.thr;
+        tp.cnt = e.cnt;
+        tp.oflag = e.oflag;
+        tp.q_al = s.q_al.as<float>();
+    }
+    SQ_TRY(launch<kth_threshold_f32_kernel<DenseThrPost>>(dim3(c.nq), dim3(1024), 0, st, a.sample_out, ns, e.kk, e.thr, tp));
+    // full pass
+    a.tile_step = 1;
+    a.n_sel = n_tiles;
+    a.nrb = nrb;
+    if (c.prof) SQ_HIP(hipEventRecord(s.ev[1], st));
+    a.wave_score = wide_tighten ? s.wave_score.as<float>() : nullptr;
+    SQ_TRY(scan_launch<false>(h->opt, a, d_pad, e.qt, e.qp, st));
+    if (c.prof) SQ_HIP(hipEventRecord(s.ev[2], st));
+    if (wide_tighten) {
+        DenseThrPost tp2 = tp;   // (the same slack rule, nothing else)
+        tp2.traw_out = nullptr;
+        tp2.raw_q = nullptr;
+        SQ_TRY(launch<dense_tighten_hist_kernel>(dim3(e.nqt > 4 ? 16 : 64, e.nqt), dim3(256), 0, st, a.wave_out, a.wave_score, a.wave_cnt, kWaveCap, n_waves,
+                                                 (const float*)e.thr, (const float*)tg.traw, e.group_q, tg.hist));
+        SQ_TRY(launch<dense_tighten_thr_kernel<DenseThrPost>>(dim3((c.nq_pad + 63) / 64), dim3(64), 0, st, tg.hist, (const float*)e.thr, (const float*)tg.traw,
+                                                              c.nq, c.nq_pad, e.kk, tp2, tg.thr2, tg.thr2k));
+    }
+    c.stats.scan_launches = 2;
+    c.stats.bytes_scanned = h->n_pad * ((long long)d_pad * 2 + (e.cosine ? 0 : 4));
+    // (L2, four-wave scan workgroups, i.e. multi-tile batches: 4 segments per re-rank workgroup measured 2 % faster than 2;
+    // the cosine kernel's row stage is sized for 256 threads)
+    int wpb = (wv == 4 && !e.cosine) ? 4 : 2;
+    if (h->opt.dense_rerank_segments > 0 && wv % h->opt.dense_rerank_segments == 0) wpb = h->opt.dense_rerank_segments;
+    DenseSurvivors v = dense_slot_survivors(h, s, n_waves, wpb, ldq, tg);
+    return by_metric(e.cosine, [&](auto m) {
+        using M = decltype(m);
+        v.expect = M::cosine ? 0 : 4 * stride * e.kk;   // ~2.7 stride k candidates per query on N(0,1) data
+        return dense_survivor_tail<M>(h, e, v, c.k, e.filter_fin<M>(M::cosine ? eps_a + eps_b : 0.5 * eps_a + eps_b), st);
+    });
 }
 
 static int dense_bf16_materialize(DenseHandle* h);   // (option "dense_bf16": the scan copy built by the first call that streams it)
 
 // Enqueue one search (nq <= kDenseQueryChunk queries) on `st` with the workspace of slot `s`; nothing is
 // waited for.  dense_resolve() finishes the call: it waits for the kernels, reads the status words and
-// sends uncertified queries down the exact path.
+// sends uncertified queries down the exact path.  This function chooses the stage that takes the call and fills
+// DenseCall; the stages are dense_small_enqueue, dense8_wide_enqueue, dense8_enqueue and dense_bf16_enqueue.
 static int dense_enqueue(DenseHandle* h, DenseSlot& s, const float* q, int nq, int k, void* out_dist, long long* out_idx,
                          hipStream_t st, bool use_event) {
     const long long n = h->n;
@@ -541,19 +1102,20 @@ static int dense_enqueue(DenseHandle* h, DenseSlot& s, const float* q, int nq, i
     u32 cap = h->opt.candidate_cap > 0 ? (u32)h->opt.candidate_cap : 65536u;
     if (cap < (u32)(4 * kk)) cap = (u32)(4 * kk);
     const bool small = n <= (long long)cap;
+    DenseCtx e{};
+    e.key_stride = small ? n : (long long)cap;
     // k beyond the one-workgroup select (16384; cosine 7168): every query takes the exact path, whose select sorts
     // (the reference has no limit on n: lsh.py:513-518)
     // filter_ok: the shape allows a first-stage filter at all (rows wider than MAX_DPAD have no scan copy of any kind)
     const bool filter_ok = !small && kk <= (cosine ? kSelectLdsKeys128 : kSelectLdsKeys64) && d_pad <= MAX_DPAD;
-    const int qt = scan_query_tiles(h->opt, d_pad, (nq + TILE_ROWS - 1) / TILE_ROWS);  // query tiles per wave
+    const int qt = e.qt = scan_query_tiles(h->opt, d_pad, (nq + TILE_ROWS - 1) / TILE_ROWS);  // query tiles per wave
     // query planes: the multi-tile configuration is MFMA bound, so it drops q_lo (half the MFMAs, twice the
     // product bound: ~1.4x more rows pass the filter) unless asked otherwise
     // (rows beyond the ring kernels, sq_dense_wide.hpp: two planes unless option dense_qplanes = 1 -- half the query bytes read from L2 per row tile, twice the slack)
-    const int qp = d_pad > RING_MAX_DPAD ? (h->opt.dense_qplanes == 1 ? 1 : 2)
-                                        : ((qt > 1 && (h->opt.dense_qplanes != 2 || d_pad > KT)) ? 1 : 2);
-    const int group_q = qt * TILE_ROWS;                                           // queries per scan workgroup
-    const int nqt = (nq + group_q - 1) / group_q;                                 // groups of qt query tiles
-    const int nq_pad = nqt * group_q;
+    e.qp = d_pad > RING_MAX_DPAD ? (h->opt.dense_qplanes == 1 ? 1 : 2) : ((qt > 1 && (h->opt.dense_qplanes != 2 || d_pad > KT)) ? 1 : 2);
+    e.group_q = qt * TILE_ROWS;                                    // queries per scan workgroup
+    e.nqt = (nq + e.group_q - 1) / e.group_q;                      // groups of qt query tiles
+    const int nq_pad = e.nqt * e.group_q;
     // Which first stage takes the call.  The shortcut past a suspended filter and the two int8 stages need no bfloat16
     // copy; the bfloat16 chain does, and builds it here when option "dense_bf16" left it for the first call that wants it.
     const bool int8_on = filter_ok && h->use8 && h->opt.dense_int8 != 0 && !(h->suspended8 && h->opt.dense_int8 < 0);
@@ -581,8 +1143,8 @@ static int dense_enqueue(DenseHandle* h, DenseSlot& s, const float* q, int nq, i
     c.cap = cap;
     c.use_event = use_event;
     if (prof) {
-        for (auto& e : s.ev)
-            if (!e) SQ_HIP(hipEventCreate(&e));
+        for (auto& ev : s.ev)
+            if (!ev) SQ_HIP(hipEventCreate(&ev));
         if (!h->ev_ref && getenv("SQ_TRACE")) {
             SQ_HIP(hipEventCreate(&h->ev_ref));
             SQ_HIP(hipEventRecord(h->ev_ref, st));
@@ -599,545 +1161,22 @@ static int dense_enqueue(DenseHandle* h, DenseSlot& s, const float* q, int nq, i
         SQ_TRY(s.oflag.reserve(64));
         SQ_HIP(hipMemsetAsync(s.oflag.p, 0, 64, st));
     }
-    u32* cnt = s.cnt.as<u32>();
-    float* thr = s.thr.as<float>();
-    double* qn2 = s.qn2.as<double>();
-    uint4* qs = s.q_scaled.as<uint4>();
-    // per-query candidate counts and status words land in pinned host memory straight from the
-    // finalisation (no copy launch): [cnt (nq_pad) | status (nq)]
-    u32* hs_raw = reinterpret_cast<u32*>(s.status_host.p);
-    u32* hs_raw_dev = nullptr;
-    SQ_TRY(s.status_host.device_ptr(reinterpret_cast<void**>(&hs_raw_dev)));
-    u32* hs_dev = hs_raw_dev + nq_pad;
-    // error bound of the bf16 filter score (sq_dense_exact.hpp filter_eps, DESIGN.md 4.1):
-    //   products: |x q' - x_hi (q'_hi + q'_lo)| <= (2^-8 + 2^-15) |x||q'|, q' = -2q  ->  eps_a = 2^-7 + 2^-14 (times X|q|)
-    //             (cosine: unit vectors and q' = -q^ without the factor 2: half of that)
-    //   float32 accumulation of 2d+1 terms and the float32 norm                     ->  eps_b = (3d+8) 2^-23
-    //   one query plane: |x q' - x_hi q'_hi| <= (2^-8 + 2^-8 + 2^-16) |x||q'|                 ->  eps_a = 2^-6 + 2^-13
-    const double eps_a = (qp == 2 ? kEpsA2 : kEpsA1) * (cosine ? 0.5 : 1.0);
-    const double eps_b = dense_eps_b(d_pad);
-    const size_t l2_lds = (size_t)((d + 3) / 4 * 4) * 4;
     if (cosine) {
         SQ_TRY(s.cos_nq.reserve((size_t)nq * 8));
-        hipLaunchKernelGGL(dense_cos_qnorm_kernel, dim3((nq + 63) / 64), dim3(64), 0, st, q, nq, d, s.cos_nq.as<double>());
+        SQ_TRY(launch<dense_cos_qnorm_kernel>(dim3((nq + 63) / 64), dim3(64), 0, st, q, nq, d, s.cos_nq.as<double>()));
     }
-    const double* cnx = h->cos_nx.as<double>();
-    const double* cnq = s.cos_nq.as<double>();
-
-    const long long key_stride = small ? n : (long long)cap;
+    SQ_TRY(e.bind(h, s));
     if (small) {
-        // every row is a candidate: exact keys for all rows, no scan
-        SQ_TRY(s.keys.reserve((size_t)nq * key_stride * key_bytes));
-        hipLaunchKernelGGL(fill_u32_kernel, dim3((nq_pad + 255) / 256), dim3(256), 0, st, cnt, (long long)nq_pad, (u32)n);
-        const unsigned gx = (unsigned)((n + 255) / 256);
-        if (prof) SQ_HIP(hipEventRecord(s.ev[1], st));
-        if (cosine)
-            hipLaunchKernelGGL(dense_exact_cos_kernel, dim3(gx, nq), dim3(256), 0, st, h->db, h->ld, d, q, nullptr, cnt,
-                               (u32)n, n, 0ll, s.keys.as<K128>(), key_stride, cnx, cnq, nullptr, 0, h->deadp());
-        else
-            hipLaunchKernelGGL(dense_exact_l2_kernel, dim3(gx, nq), dim3(256), l2_lds, st, h->db, h->ld, d, q, nullptr,
-                               cnt, (u32)n, n, 0ll, s.keys.as<u64>(), key_stride, nullptr, 0, h->deadp());
-        if (prof) SQ_HIP(hipEventRecord(s.ev[2], st));
-        c.stats.scan_launches = 1;
-        c.stats.bytes_scanned = n * (long long)d * 4;
-        if (cosine) {
-            SQ_TRY(select_launch_t<K128>(s.keys.as<K128>(), cnt, (u32)n, key_stride, k, nq, s.out_keys.as<K128>(),
-                                         with_dead(DenseFinalizeCos{cnt, (u32)n, kk, h->id_base, thr, 0.0, 0, (double*)out_dist, out_idx,
-                                                                    hs_dev, hs_raw_dev, nullptr, 0}, h->deadp()),
-                                         st, s.sort_tmp));
-        } else {
-            SQ_TRY(select_launch_t<u64>(s.keys.as<u64>(), cnt, (u32)n, key_stride, k, nq, s.out_keys.as<u64>(),
-                                        with_dead(DenseFinalizeL2{cnt, (u32)n, kk, h->id_base, thr, qn2, 0.0, 0,
-                                                                  (float*)out_dist, out_idx, hs_dev, hs_raw_dev, nullptr, 0}, h->deadp()),
-                                        st, s.sort_tmp));
-        }
+        SQ_TRY(dense_small_enqueue(h, s, e));
     } else if (take_mid) {
         c.all_fallback = true;   // (nothing enqueued: dense_resolve starts every query at the middle tier)
         c.mid_direct = true;
     } else if (take_i8_wide) {
-        // ---- rows of 513 to 8192 dimensions, one query tile: the int8 first stage of sq_dense_i8_wide.hpp
-        // (filter_ok: kk is inside the one-workgroup select; larger batches take the bfloat16 chain below)
-        c.int8 = true;
-        if (h->suspended8) {   // dense_int8 = 1 on the handle: the filter is armed again (and judged again from the next calls)
-            h->suspended8 = false;
-            h->overflow8 = 0;
-        }
-        c.stats.scan_launches = 2;
-        c.stats.bytes_scanned = h->n_pad64 * ((long long)h->row8 + 4);
-        SQ_TRY(dense8_wide_enqueue(h, s, q, nq, k, kk, out_dist, out_idx, st, prof, cap, hs_dev, hs_raw_dev));
+        SQ_TRY(dense8_wide_enqueue(h, s, e));
     } else if (take_i8) {
-        // ---- the int8 first-stage filter (sq_dense_i8.hpp): half the bytes per row, measured error bound
-        c.int8 = true;
-        if (h->suspended8) {   // dense_int8 = 1 on the handle: the filter is armed again (and judged again from the next calls)
-            h->suspended8 = false;
-            h->overflow8 = 0;
-        }
-        // (128-byte rows stream in ring units of 64 rows on eight waves.  Two other geometries were built and measured --
-        // commit 5048766: 128-row units on four waves 0.197 against 0.204 ms per pass alone but 0.244-0.251 against 0.223-0.226 ms
-        // per pipelined step; 32-row units on sixteen waves 0.236 -- and removed again.)
-        const int row8 = h->row8, unit_rows = i8_unit_rows(row8), spu = 2 * (unit_rows / 32), waves8 = i8_waves(row8);   // samples per unit
-        const long long n_units = (n + unit_rows - 1) / unit_rows;
-        long long stride = h->opt.sample_stride;
-        if (stride <= 0) {
-            // units of 64 rows, four samples per unit: the bf16 path's cost model in units of two tiles
-            // (measured at 10 M x 128, k = 100: 0.293 / 0.269 / 0.262 / 0.258 / 0.257 / 0.257 / 0.263 ms per step at 6 / 8 / 10 / 12 / 16 / 20 / 24)
-            // 256- and 512-byte rows: flat from 8 to 14, best at 10 (0.471 / 0.988 ms per step at 10 M x 256 / 512); the float64 cosine
-            // re-rank costs ~3.6x the float32 one per candidate: sqrt of that off the stride, as in the bf16 path
-            stride = (long long)((row8 == 128 ? 14.0 : 10.0) * sqrt((double)n / 1e7 * 100.0 / (double)kk / (double)qt) / (cosine ? 1.9 : 1.0) + 0.5);
-            if (stride > 16) stride = 16;
-            // The fused call with the tightened threshold (sq_dense_i8.hpp): the sample only has to keep the first-level
-            // entries inside the wave segments -- what is re-ranked no longer depends on it -- so it is several times sparser
-            const bool will_tighten = h->opt.dense_fused != 0 && h->opt.dense_tighten != 0 && qt == 1 && nqt == 1;
-            if (will_tighten) {
-                stride = (long long)(40.0 * sqrt((double)n / 1e7 * 100.0 / (double)kk) + 0.5);
-                if (stride > 64) stride = 64;
-            }
-            if (stride < 1) stride = 1;
-            if (stride > (long long)cap / (16ll * kk)) stride = std::max<long long>(1, (long long)cap / (16ll * kk));
-        }
-        while (stride > 1 && (n_units / stride) * spu < 8ll * kk) stride >>= 1;
-        const long long ns_units = (n_units + stride - 1) / stride;
-        const long long ns = ns_units * spu;
-        SQ_TRY(s.keys.reserve((size_t)nq * key_stride * key_bytes));
-        SQ_TRY(s.q8.reserve((size_t)2 * nq_pad * row8));
-        SQ_TRY(s.par8.reserve((size_t)nq_pad * 8));
-        const int cus = cu_count(h->device);
-        int nrb = h->opt.dense_blocks > 0 ? h->opt.dense_blocks : (use_event && h->opt.dense_async_streams == 2 && nqt == 1 ? cus * 3 / 4 : cus);
-        nrb = (nrb + 7) / 8 * 8;
-        const long long n_waves = (long long)nrb * nqt * waves8;
-        const u32 wave_cap = 2048;
-        const int ldq = (d + 3) / 4 * 4;
-        SQ_TRY(s.wave_out.reserve((size_t)n_waves * wave_cap * 8));
-        SQ_TRY(s.wave_cnt.reserve((size_t)n_waves * 8));
-        SQ_TRY(s.q_al.reserve((size_t)nq * ldq * 4));
-        u32* oflag = s.oflag.as<u32>();
-        const float* centerp = (!cosine && h->center.p) ? h->center.as<float>() : nullptr;
-        Dense8ScanArgs a{};
-        a.scan8 = h->scan8.as<signed char>();
-        a.nrow = h->nrow8.as<float>();
-        a.n = n;
-        a.n_units = n_units;
-        a.qs8 = s.q8.as<signed char>();
-        a.par = s.par8.as<float2>();
-        a.thr = thr;
-        a.wave_out = s.wave_out.as<uint2>();
-        a.wave_cnt = s.wave_cnt.as<u32>();
-        a.wave_cap = wave_cap;
-        a.sample_out = s.sample.as<float>();
-        a.ns = ns;
-        a.nqt = nqt;
-        a.plane_rows = nq_pad;
-        a.debug = h->opt.dense_debug;
-        {
-            // (cacheable head: 32-64 MB measured best here -- 0.244 ms per step at 10 M rows against 0.250 at the bf16 copy's 192 MB)
-            const size_t copy_bytes = (size_t)h->n_pad64 * row8;
-            const long long keep_mb = h->opt.dense_nt_keep_mb > 0 ? h->opt.dense_nt_keep_mb : 64;
-            a.nt = h->opt.dense_nt >= 0 ? h->opt.dense_nt : (copy_bytes > ((size_t)512 << 20) && nqt == 1 ? 1 : 0);   // (several groups re-read the rows from L2)
-            a.nt_from_row = h->opt.dense_nt == 0 ? 0x7fffffffffffffffll : h->opt.dense_nt == 1 ? 0ll : (keep_mb << 20) / row8;
-        }
-        int nrb_sample = nrb;
-        if (use_event && h->opt.dense_async_streams == 2 && h->opt.dense_blocks <= 0 && nqt == 1) {
-            int sb = h->opt.dense_sample_blocks > 0 ? h->opt.dense_sample_blocks : (h->opt.dense_sample_blocks < 0 ? nrb : cus - nrb);
-            sb = (sb + 7) / 8 * 8;
-            if (sb >= 8 && sb < nrb_sample) nrb_sample = sb;
-        }
-        if (ns_units < (long long)nrb_sample * waves8) nrb_sample = (int)(((ns_units + waves8 - 1) / waves8 + 7) / 8 * 8);
-        // Three launches instead of six (sq_dense_i8.hpp, "a call in three launches"): one query tile, and a head grid whose
-        // M = workgroups x waves x 2 lane minima per query number at least 4 k (the threshold is then within a few per cent of
-        // the k-th smallest sample) and at most 2048 (what the last workgroup's waves hold in registers).
-        bool fused = h->opt.dense_fused != 0 && qt == 1 && nqt == 1 && ns_units >= 2ll * kk;
-        const bool tighten = fused && h->opt.dense_tighten != 0;
-        if (fused) {
-            const int lanes_per_wg = waves8 * 2;
-            const int wg_min = ((4 * kk + lanes_per_wg - 1) / lanes_per_wg + 7) / 8 * 8, wg_max = 2048 / lanes_per_wg;
-            if (wg_min > wg_max || wg_min > cus)
-                fused = false;
-            else
-                nrb_sample = std::min(std::max(nrb_sample, wg_min), std::min(wg_max, (cus + 7) / 8 * 8));
-        }
-        // minima a head workgroup hands over per query: the k best of a call fall on a workgroup k / workgroups at a time
-        int keep8 = waves8 * 2;
-        if (fused) {
-            const double per_wg = (double)kk / nrb_sample;
-            if (per_wg <= 1.7 && keep8 > 4) keep8 = 4;
-            else if (per_wg <= 4.5 && keep8 > 8) keep8 = 8;
-        }
-        const long long lane_m = (long long)nrb_sample * keep8;
-        SQ_TRY(s.sample.reserve(fused ? (size_t)TILE_ROWS * lane_m * 4 : (size_t)nq_pad * ns * 4));
-        a.sample_out = s.sample.as<float>();
-        if (fused) {
-            SQ_TRY(s.wave_score.reserve((size_t)n_waves * wave_cap * 4));
-            SQ_TRY(s.hist8.reserve((size_t)I8_HIST_WORDS * 4));
-            a.wave_score = s.wave_score.as<float>();
-            a.hist = s.hist8.as<u32>();
-        }
-        int wpb = 2;   // survivor segments per re-rank workgroup (128 threads each)
-        if (!cosine && h->opt.dense_rerank_segments > 0 && waves8 % h->opt.dense_rerank_segments == 0 && h->opt.dense_rerank_segments <= 4)
-            wpb = h->opt.dense_rerank_segments;
-        const size_t rr_lds = (qt == 1 && ldq <= 156) ? (size_t)32 * (ldq + 4) * 4 : 0;
-        // The chain of six launches, eagerly or as a captured graph.  A launch costs ~2.8 us of host time
-        // (tools/micro/launch_cost.hip: 19.3 us for a chain of seven, 5.6-6.3 us for one hipGraphLaunch of the same chain; in
-        // this call 20 against 9.5 us, tools/host_sections.py).  It does not shorten a 1.25 M-row shard's ~55 us step -- that
-        // is the latency of the chain itself, three deep -- but frees the host thread for the gather / merge work of a
-        // sharded search.  The slot's first call of a shape runs eagerly (it sizes the workspace and sets the kernels'
-        // attributes), the second captures, later ones launch the graph; the caller's pointers travel through a pinned
-        // block (DenseCallPtrs).
-        const DenseCallPtrs* ind = nullptr;
-        auto chain = [&](hipStream_t cs) -> int {
-            if (fused) {
-                // head: query prep + sample pass (lane minima) + thresholds by the last workgroup
-                Dense8HeadArgs ha{};
-                ha.s = a;
-                ha.s.unit_step = stride;
-                ha.s.n_sel = ns_units;
-                ha.s.nrb = nrb_sample;
-                ha.q = q;
-                ha.nq = nq;
-                ha.d = d;
-                ha.center = centerp;
-                ha.dx = h->dx8;
-                ha.r_max = h->rmax8;
-                ha.x_max = h->xmax8;
-                ha.cosine = cosine ? 1 : 0;
-                ha.qn2 = qn2;
-                ha.cnt = cnt;
-                ha.oflag = oflag;
-                ha.q_al = s.q_al.as<float>();
-                ha.ldq = ldq;
-                ha.ind = ind;
-                ha.lane_min = s.sample.as<float>();
-                ha.keep = keep8;
-                ha.kk = kk;
-                if (const int rc = dense8_head_launch(row8, ha, cs)) return rc;
-                // body: the full pass; its workgroups re-rank their own survivors when the stream has drained
-                Dense8ScanArgs b = a;
-                b.unit_step = 1;
-                b.n_sel = n_units;
-                b.nrb = nrb;
-                Dense8TailArgs ta{h->db, h->ld, d, s.q_al.as<float>(), ldq, nq, s.keys.p, cnt, cap, oflag, cnx, cnq, h->opt.dense_debug, qn2, kk, tighten ? 1 : 0, nullptr};
-                s.clk8_wgs = 0;
-                if ((h->opt.dense_debug & 8192) && !use_event) {   // (blocking calls only: printed by dense_resolve)
-                    if (const int rc = s.clk8.reserve((size_t)nrb * 64)) return rc;
-                    SQ_HIP(hipMemsetAsync(s.clk8.p, 0, (size_t)nrb * 64, cs));
-                    ta.clk = s.clk8.as<long long>();
-                    s.clk8_wgs = nrb;
-                }
-                if (prof) SQ_HIP(hipEventRecord(s.ev[1], cs));
-                if (const int rc = dense8_body_launch(row8, cosine, b, ta, cs)) return rc;
-                if (prof) {
-                    SQ_HIP(hipEventRecord(s.ev[2], cs));
-                    SQ_HIP(hipEventRecord(s.ev[4], cs));
-                }
-                if (cosine) {
-                    DenseFinalizeCos fin{cnt, cap, kk, h->id_base, thr, 0.0, 1, (double*)out_dist, out_idx, hs_dev, hs_raw_dev, oflag, 0};
-                    fin.lin = s.par8.as<float2>();
-                    fin.ind = ind;
-                    if (tighten) fin.thr2k = a.hist + TILE_ROWS * I8_HIST_BINS;
-                    fin.cnt_shift = I8_CNT_SHIFT;
-                    return select_launch_t<K128>(s.keys.as<K128>(), cnt, cap, key_stride, k, nq, s.out_keys.as<K128>(), fin, cs, s.sort_tmp, 8 * stride * kk, I8_CNT_SHIFT);
-                }
-                DenseFinalizeL2 fin{cnt, cap, kk, h->id_base, thr, qn2, 0.0, 1, (float*)out_dist, out_idx, hs_dev, hs_raw_dev, oflag, 0};
-                fin.lin = s.par8.as<float2>();
-                fin.ind = ind;
-                if (tighten) fin.thr2k = a.hist + TILE_ROWS * I8_HIST_BINS;
-                fin.cnt_shift = I8_CNT_SHIFT;
-                return select_launch_t<u64>(s.keys.as<u64>(), cnt, cap, key_stride, k, nq, s.out_keys.as<u64>(), fin, cs, s.sort_tmp, 8 * stride * kk, I8_CNT_SHIFT);
-            }
-            {
-                auto prep = row8 == 128 ? dense8_prep_queries_kernel<2> : (row8 == 256 ? dense8_prep_queries_kernel<4> : dense8_prep_queries_kernel<8>);
-                hipLaunchKernelGGL(prep, dim3(nq_pad / 4), dim3(64), 0, cs, q, nq, d, centerp, h->dx8, h->rmax8, h->xmax8,
-                                   s.q8.as<signed char>(), s.par8.as<float2>(), qn2, thr, cnt, oflag, s.q_al.as<float>(), ldq, ind, cosine ? 1 : 0, nq_pad);
-            }
-            Dense8ScanArgs b = a;
-            b.unit_step = stride;   // sample pass (on the CUs the pipelined full pass leaves free)
-            b.n_sel = ns_units;
-            b.nrb = nrb_sample;
-            if (const int rc = dense8_scan_any<true>(row8, qt, b, cs)) return rc;
-            hipLaunchKernelGGL((kth_threshold_f32_kernel<Dense8ThrPost>), dim3(nq), dim3(1024), 0, cs, a.sample_out, ns, kk, thr,
-                               Dense8ThrPost{s.par8.as<float2>(), qn2});
-            b.unit_step = 1;        // full pass
-            b.n_sel = n_units;
-            b.nrb = nrb;
-            if (prof) SQ_HIP(hipEventRecord(s.ev[1], cs));
-            if (const int rc = dense8_scan_any<false>(row8, qt, b, cs)) return rc;
-            if (prof) SQ_HIP(hipEventRecord(s.ev[2], cs));
-            if (cosine) {
-                hipLaunchKernelGGL(dense_rerank_cos_kernel, dim3((unsigned)((n_waves + wpb - 1) / wpb)), dim3(128 * wpb), rr_lds, cs, h->db, h->ld, d,
-                                   s.q_al.as<float>(), ldq, a.wave_out, a.wave_cnt, wave_cap, n_waves, wpb, nq, group_q, s.keys.as<K128>(), cnt,
-                                   cap, oflag, cnx, cnq, h->opt.dense_debug);
-                if (prof) SQ_HIP(hipEventRecord(s.ev[4], cs));
-                DenseFinalizeCos fin{cnt, cap, kk, h->id_base, thr, 0.0, 1, (double*)out_dist, out_idx, hs_dev, hs_raw_dev, oflag, 0};
-                fin.lin = s.par8.as<float2>();
-                fin.ind = ind;
-                return select_launch_t<K128>(s.keys.as<K128>(), cnt, cap, key_stride, k, nq, s.out_keys.as<K128>(), fin, cs, s.sort_tmp, 8 * stride * kk);
-            }
-            hipLaunchKernelGGL(dense_rerank_l2_kernel, dim3((unsigned)((n_waves + wpb - 1) / wpb)), dim3(128 * wpb), rr_lds, cs, h->db, h->ld, d,
-                               s.q_al.as<float>(), ldq, a.wave_out, a.wave_cnt, wave_cap, n_waves, wpb, nq, group_q, s.keys.as<u64>(), cnt,
-                               cap, oflag, h->opt.dense_debug);
-            if (prof) SQ_HIP(hipEventRecord(s.ev[4], cs));
-            DenseFinalizeL2 fin{cnt, cap, kk, h->id_base, thr, qn2, 0.0, 1, (float*)out_dist, out_idx, hs_dev, hs_raw_dev, oflag, 0};
-            fin.lin = s.par8.as<float2>();
-            fin.ind = ind;
-            return select_launch_t<u64>(s.keys.as<u64>(), cnt, cap, key_stride, k, nq, s.out_keys.as<u64>(), fin, cs, s.sort_tmp, 8 * stride * kk);
-        };
-        c.stats.scan_launches = 2;
-        c.stats.bytes_scanned = h->n_pad64 * ((long long)row8 + 4) * nqt;
-        bool launched = false;
-        if (use_event && !prof && h->opt.dense_graph != 0 && !h->graph_broken && st != nullptr && st == s.own) {   // (never a capture on the caller's stream)
-            // everything the captured launches were given by value: shapes, the slot's and the handle's buffers
-            u64 key = 0xcbf29ce484222325ull;
-            auto mix = [&key](u64 v) { key = (key ^ v) * 0x100000001b3ull; };
-            for (u64 v : {(u64)(fused ? 1 : 0), (u64)(tighten ? 1 : 0), (u64)(uintptr_t)s.wave_score.p, (u64)(uintptr_t)s.hist8.p, (u64)lane_m, (u64)nq, (u64)k, (u64)row8, (u64)qt, (u64)nqt, (u64)wpb, (u64)stride, (u64)nrb, (u64)nrb_sample, (u64)ns, (u64)a.nt, (u64)a.nt_from_row, (u64)n, (u64)h->n_live, (u64)cap,
-                          (u64)h->opt.dense_debug, (u64)h->id_base, (u64)(uintptr_t)st, (u64)(uintptr_t)h->db, (u64)(uintptr_t)centerp,
-                          (u64)(uintptr_t)h->scan8.p, (u64)(uintptr_t)h->nrow8.p, (u64)(uintptr_t)s.q8.p, (u64)(uintptr_t)s.par8.p,
-                          (u64)(uintptr_t)s.sample.p, (u64)(uintptr_t)s.keys.p, (u64)(uintptr_t)s.wave_out.p, (u64)(uintptr_t)s.wave_cnt.p,
-                          (u64)(uintptr_t)s.q_al.p, (u64)(uintptr_t)cnt, (u64)(uintptr_t)thr, (u64)(uintptr_t)qn2, (u64)(uintptr_t)oflag,
-                          (u64)(uintptr_t)s.out_keys.p, (u64)(uintptr_t)hs_raw_dev, (u64)(uintptr_t)cnx, (u64)(uintptr_t)cnq, (u64)(cosine ? 1 : 0)})
-                mix(v);
-            if (key == 0) key = 1;
-            if (s.gexec && s.gkey != key) {
-                (void)hipGraphExecDestroy(s.gexec);
-                s.gexec = nullptr;
-            }
-            if (!s.gexec && s.seen_key == key) {   // second call of this shape on this slot: capture
-                SQ_TRY(s.call_ptrs.reserve(sizeof(DenseCallPtrs)));
-                void* ind_dev = nullptr;
-                SQ_TRY(s.call_ptrs.device_ptr(&ind_dev));
-                ind = static_cast<const DenseCallPtrs*>(ind_dev);
-                // (a capture that fails is no reason to fail the search: the handle goes back to eager launches for good)
-                hipGraph_t g = nullptr;
-                bool ok = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess;
-                if (ok) {
-                    const int rc = chain(st);
-                    const hipError_t ec = hipStreamEndCapture(st, &g);
-                    ok = rc == SQ_OK && ec == hipSuccess && g != nullptr;
-                }
-                if (ok) ok = hipGraphInstantiate(&s.gexec, g, nullptr, nullptr, 0) == hipSuccess;
-                if (g) (void)hipGraphDestroy(g);
-                if (!ok) {
-                    (void)hipGetLastError();
-                    s.gexec = nullptr;
-                    h->graph_broken = true;
-                } else {
-                    s.gkey = key;
-                    if (getenv("SQ_INT8_REPORT")) fprintf(stderr, "[smqtk_hip] call graph captured (%d queries, k = %d)\n", nq, k);
-                }
-            }
-            s.seen_key = key;
-            if (s.gexec) {
-                *static_cast<DenseCallPtrs*>(s.call_ptrs.p) = DenseCallPtrs{q, out_dist, out_idx};
-                SQ_HIP(hipGraphLaunch(s.gexec, st));
-                launched = true;
-            }
-        }
-        if (!launched) {
-            ind = nullptr;
-            SQ_TRY(chain(st));
-        }
+        SQ_TRY(dense8_enqueue(h, s, e));
     } else if (take_bf16) {
-        const long long n_tiles = (n + TILE_ROWS - 1) / TILE_ROWS;
-        // Sample every stride-th tile.  The sample pass costs ~ n * groups / stride, the re-rank + select
-        // ~ nq * stride * k (candidates per query ~ stride * k * slack); with groups ~ nq / (32 qt) the
-        // balance is stride ~ sqrt(n / (qt k)), independent of the batch: 20 at 10 M rows, k = 100, one
-        // query tile per wave (measured optimum 16-24; 8-12 with four tiles; 4 on a 1.25 M-row shard).
-        long long stride = h->opt.sample_stride;
-        if (stride <= 0) {
-            // (the float64 cosine re-rank costs ~3.6x the float32 L2 one per candidate: sqrt of that off the stride)
-            stride = (long long)(20.0 * sqrt((double)n / 1e7 * 100.0 / (double)kk / (double)qt) / (cosine ? 1.9 : 1.0) + 0.5);
-            if (stride > 24) stride = 24;
-            if (stride < 2) stride = 2;
-            if (stride > (long long)cap / (8ll * kk)) stride = (long long)cap / (8ll * kk);  // room in the key lists
-        }
-        if (stride > 64) stride = 64;
-        if (stride < 1) stride = 1;
-        while (stride > 1 && (n_tiles / stride) * 2 < 8ll * kk) stride >>= 1;
-        const long long ns_tiles = (n_tiles + stride - 1) / stride;
-        // one sample (a 16-row group minimum) per lane half per tile; the four-tile sample pass writes runs of four
-        // tiles ([query][half][tiles rounded up to 4], +inf in the padding: dense_scan_kernel CHUNK)
-        const bool sample_runs = qt == 4 && qp == 1 && d_pad == KT;
-        const long long ns = (sample_runs ? (ns_tiles + 3) / 4 * 4 : ns_tiles) * 2;
-        SQ_TRY(s.sample.reserve((size_t)nq_pad * ns * 4));
-        SQ_TRY(s.keys.reserve((size_t)nq * key_stride * key_bytes));
-        const int cus = cu_count(h->device);
-        // One scan workgroup per CU fills the chip -- and leaves nothing for the other call slot's short kernels
-        // (re-rank, select of the previous call; query prep, sample pass, threshold of the next), whose workgroups
-        // need LDS of their own.  When the two slots run on their own streams the scan takes three quarters of
-        // the CUs: alone it is as fast (HBM bound: 0.433 ms on 160 workgroups against 0.439 on 256 at 10 M x 128),
-        // and the pipelined step drops from 0.50 to 0.46 ms (tools/step_sweep.py dense_blocks=...).
-        // (one query tile per wave only: the multi-tile configurations are MFMA bound and want every CU)
-        int nrb = h->opt.dense_blocks > 0 ? h->opt.dense_blocks : (use_event && h->opt.dense_async_streams == 2 && nqt == 1 ? cus * 3 / 4 : cus);
-        // (the wide kernel, 122 registers and 32 KB of LDS: two eight-wave workgroups per CU -- twice the row bytes in flight)
-        if (d_pad > RING_MAX_DPAD && h->opt.dense_blocks <= 0) nrb = qt == 1 ? 2 * cus : cus;   // (two tiles per wave: one workgroup per CU)
-        nrb = (nrb + 7) / 8 * 8;
-        const int wv = d_pad > RING_MAX_DPAD ? WIDE_WAVES : scan_geometry(h->opt, d_pad, qt, qp).waves;
-        // survivors leave the scan as per-wave segments; the re-rank kernel turns them into per-query key lists
-        const long long n_waves = (long long)nrb * nqt * wv;
-        const u32 wave_cap = 2048;
-        const int ldq = (d + 3) / 4 * 4;
-        SQ_TRY(s.wave_out.reserve((size_t)n_waves * wave_cap * 8));
-        SQ_TRY(s.wave_cnt.reserve((size_t)n_waves * 8));
-        SQ_TRY(s.q_al.reserve((size_t)nq * ldq * 4));
-        u32* oflag = s.oflag.as<u32>();
-        // rows beyond the ring kernels: a second-level threshold between the pass and the re-rank (sq_dense_tighten.hpp).
-        // (The ring kernels do not store their entries' scores: the few instructions that would in dense_scan_kernel's
-        // emission path changed the answers of its hand-scheduled multi-tile builds -- one query of a hundred lost the
-        // survivors of its last row tiles -- and were taken out again; tools/tighten_debug.py.  In the compiler-scheduled
-        // one-tile builds alone they were correct but not worth it: 10 M x 128 without the int8 copy, 3.3 k -> 2.1 k rows
-        // re-ranked per query, 0.424 -> 0.451 ms per step: two more launches against 512-byte gathers.)
-        const bool wide_tighten = h->opt.dense_tighten != 0 && d_pad > RING_MAX_DPAD && group_q <= TG_MAX_GROUP && nq_pad <= TG_CAP_Q;
-        u32 *tg_hist = nullptr, *tg_thr2k = nullptr;
-        float *tg_traw = nullptr, *tg_thr2 = nullptr;
-        if (wide_tighten) {
-            SQ_TRY(s.wave_score.reserve((size_t)n_waves * wave_cap * 4));
-            SQ_TRY(s.tg.reserve((size_t)TG_CAP_Q * (TG_BINS + 3) * 4));   // (fixed layout: the histogram region never meets old thresholds)
-            if (s.tg_zeroed != s.tg.p) {   // a new allocation: wiped once, dense_tighten_thr_kernel leaves the histogram clean
-                SQ_HIP(hipMemsetAsync(s.tg.p, 0, s.tg.cap, st));
-                s.tg_zeroed = s.tg.p;
-            }
-            tg_hist = s.tg.as<u32>();
-            tg_traw = reinterpret_cast<float*>(tg_hist + (size_t)TG_CAP_Q * TG_BINS);
-            tg_thr2 = tg_traw + TG_CAP_Q;
-            tg_thr2k = reinterpret_cast<u32*>(tg_thr2 + TG_CAP_Q);
-        }
-        // L2, one query tile per wave (the HBM-bound configuration a pipelined step runs): no prep launch -- the scan
-        // kernels build the planes of their query tile themselves and the threshold kernel's prologue does the rest
-        // (DenseScanArgs::raw_q, DenseThrPost).  The head of a call is then sample pass -> threshold: on a 1.25 M-row
-        // shard the three-launch head (prep 6-27 us beside the neighbours' kernels, sample, threshold) no longer
-        // fitted under the previous call's 59 us scan, and the scans did not run back to back.
-        const bool fused_prep = !cosine && qt == 1 && qp == 2 && h->opt.dense_fused_prep != 0 && d_pad <= RING_MAX_DPAD;
-        const float* centerp = h->center.p ? h->center.as<float>() : nullptr;
-        if (!fused_prep)
-            hipLaunchKernelGGL(dense_prep_queries_kernel, dim3(nq_pad), dim3(256), 0, st, q, nq, d, d_pad, h->metric, qs,
-                               qn2, thr, cnt, oflag, s.q_al.as<float>(), ldq, centerp);
-        DenseScanArgs a{};
-        if (fused_prep) {
-            a.raw_q = q;
-            a.raw_nq = nq;
-            a.raw_d = d;
-            a.center = centerp;
-        }
-        a.scan = h->scan.as<uint4>();
-        a.norms = cosine ? nullptr : (qp == 1 ? h->norms1.as<float>() : h->norms.as<float>());  // n' of this plane count
-        a.norm_step = 1;
-        // non-temporal stream (32 queries, pipelined step): 10 M rows 0.456 -> 0.401 ms, 5 M 0.251 -> 0.227, 2.5 M 0.147 ->
-        // 0.139.  One-tile kernel: everything behind a cacheable head of 192 MB ("dense_nt_keep_mb"); multi-tile kernels
-        // with one query group: their non-temporal build when the copy is far beyond the MALL.
-        {
-            const size_t copy_bytes = (size_t)h->n_pad * d_pad * 2;
-            const long long keep_mb = h->opt.dense_nt_keep_mb > 0 ? h->opt.dense_nt_keep_mb : 192;
-            a.nt = h->opt.dense_nt >= 0 ? h->opt.dense_nt : (copy_bytes > ((size_t)512 << 20) ? 1 : 0);
-            a.nt_from_row = h->opt.dense_nt == 0 ? 0x7fffffffffffffffll : h->opt.dense_nt == 1 ? 0ll : (keep_mb << 20) / ((long long)d_pad * 2);
-        }
-        if (cosine && (qt > 1 || qp == 1)) {  // the AGPR configurations always stream a norm piece
-            a.norms = h->zeros.as<float>();
-            a.norm_step = 0;
-        }
-        a.n = n;
-        a.n_tiles = n_tiles;
-        a.qs = qs;
-        a.thr = thr;
-        a.wave_out = s.wave_out.as<uint2>();
-        a.wave_cnt = s.wave_cnt.as<u32>();
-        a.wave_cap = wave_cap;
-        a.sample_out = s.sample.as<float>();
-        a.ns = ns;
-        a.nqt = nqt;
-        a.debug = h->opt.dense_debug;
-        // sample pass
-        a.tile_step = stride;
-        a.n_sel = ns_tiles;
-        a.nrb = nrb;
-        // Pipelined one-group calls: the sample pass is a scan kernel too (one workgroup wants most of a CU's LDS), so on
-        // as many workgroups as the full pass it cannot run BESIDE the neighbouring call's full pass (192 of the 256
-        // CUs) -- its tail queues behind that pass and the two scans of a step serialise (a 1.25 M-row shard: 16 + 63 us
-        // of an 83 us step).  On the spare quarter of the CUs it runs wholly under the neighbour's full pass.
-        if (use_event && h->opt.dense_async_streams == 2 && nqt == 1 && h->opt.dense_blocks <= 0) {
-            int sb = h->opt.dense_sample_blocks > 0 ? h->opt.dense_sample_blocks : (h->opt.dense_sample_blocks < 0 ? nrb : cus - nrb);
-            sb = (sb + 7) / 8 * 8;
-            if (sb >= 8 && sb < a.nrb) a.nrb = sb;
-        }
-        {
-            const long long work = sample_runs ? (ns_tiles + 3) / 4 : ns_tiles;  // runs / tiles a wave takes at a time
-            if (work < (long long)nrb * wv) a.nrb = (int)(((work + wv - 1) / wv + 7) / 8 * 8);
-        }
-        SQ_TRY(scan_launch<true>(h->opt, a, d_pad, qt, qp, st));
-        DenseThrPost tp{qn2, cosine ? 1 : 0, filter_bound(cosine ? 1 : 0, eps_a, eps_b, h->xn2_max)};
-        {
-            tp.traw_out = tg_traw;
-            if (fused_prep) {
-                tp.raw_q = q;
-                tp.nq = nq;
-                tp.nq_pad = nq_pad;
-                tp.d = d;
-                tp.ldq = ldq;
-                tp.center = centerp;
-                tp.qn2_out = qn2;
-                tp.thr_out = thr;
-                tp.cnt = cnt;
-                tp.oflag = oflag;
-                tp.q_al = s.q_al.as<float>();
-            }
-            hipLaunchKernelGGL((kth_threshold_f32_kernel<DenseThrPost>), dim3(nq), dim3(1024), 0, st, a.sample_out, ns, kk, thr, tp);
-        }
-        // full pass
-        a.tile_step = 1;
-        a.n_sel = n_tiles;
-        a.nrb = nrb;
-        if (prof) SQ_HIP(hipEventRecord(s.ev[1], st));
-        a.wave_score = wide_tighten ? s.wave_score.as<float>() : nullptr;
-        SQ_TRY(scan_launch<false>(h->opt, a, d_pad, qt, qp, st));
-        if (prof) SQ_HIP(hipEventRecord(s.ev[2], st));
-        if (wide_tighten) {
-            DenseThrPost tp2 = tp;   // (the same slack rule, nothing else)
-            tp2.traw_out = nullptr;
-            tp2.raw_q = nullptr;
-            hipLaunchKernelGGL(dense_tighten_hist_kernel, dim3(nqt > 4 ? 16 : 64, nqt), dim3(256), 0, st, a.wave_out, a.wave_score, a.wave_cnt,
-                               wave_cap, n_waves, (const float*)thr, (const float*)tg_traw, group_q, tg_hist);
-            hipLaunchKernelGGL((dense_tighten_thr_kernel<DenseThrPost>), dim3((nq_pad + 63) / 64), dim3(64), 0, st, tg_hist, (const float*)thr,
-                               (const float*)tg_traw, nq, nq_pad, kk, tp2, tg_thr2, tg_thr2k);
-        }
-        c.stats.scan_launches = 2;
-        c.stats.bytes_scanned = h->n_pad * ((long long)d_pad * 2 + (cosine ? 0 : 4));
-        // exact re-rank of the survivors (wave segments -> per-query keys), select, certify
-        // A re-rank workgroup takes `wpb` survivor segments of one scan workgroup (its waves share the query
-        // group), 128 threads per segment.  Many small workgroups win: the kernel is a chain of dependent
-        // memory round trips per workgroup, not the per-query atomics (2 vs 8 segments: 37 vs 50 us at 10 M rows).
-        // (L2, four-wave scan workgroups, i.e. multi-tile batches: 4 measured 2 % faster than 2; the cosine kernel's
-        // row stage is sized for 256 threads)
-        int wpb = (wv == 4 && !cosine) ? 4 : 2;
-        if (h->opt.dense_rerank_segments > 0 && wv % h->opt.dense_rerank_segments == 0) wpb = h->opt.dense_rerank_segments;
-        const unsigned rr_threads = (unsigned)std::min(512, 128 * wpb);
-        const size_t rr_lds = (qt == 1 && ldq <= 156) ? (size_t)32 * (ldq + 4) * 4 : 0;  // the query tile in LDS (rerank_block)
-        const unsigned gxr = (unsigned)((n_waves + wpb - 1) / wpb);
-        if (cosine) {
-            if (wide_tighten)
-                hipLaunchKernelGGL((dense_rerank_filtered_kernel<K128, true>), dim3(gxr), dim3(rr_threads), rr_lds, st, h->db, h->ld, d,
-                                   s.q_al.as<float>(), ldq, a.wave_out, a.wave_cnt, wave_cap, n_waves, wpb, nq, group_q, s.keys.as<K128>(), cnt,
-                                   cap, oflag, cnx, cnq, h->opt.dense_debug, (const float*)a.wave_score, (const float*)tg_thr2);
-            else
-                hipLaunchKernelGGL(dense_rerank_cos_kernel, dim3(gxr), dim3(rr_threads), rr_lds, st, h->db, h->ld, d, s.q_al.as<float>(),
-                                   ldq, a.wave_out, a.wave_cnt, wave_cap, n_waves, wpb, nq, group_q, s.keys.as<K128>(), cnt,
-                                   cap, oflag, cnx, cnq, h->opt.dense_debug);
-            if (prof) SQ_HIP(hipEventRecord(s.ev[4], st));
-            DenseFinalizeCos fin{cnt, cap, kk, h->id_base, thr, eps_a + eps_b, 1, (double*)out_dist, out_idx, hs_dev, hs_raw_dev, oflag, 0};
-            if (wide_tighten) fin.thr2k = tg_thr2k;
-            SQ_TRY(select_launch_t<K128>(s.keys.as<K128>(), cnt, cap, key_stride, k, nq, s.out_keys.as<K128>(), fin, st, s.sort_tmp));
-        } else {
-            if (wide_tighten)
-                hipLaunchKernelGGL((dense_rerank_filtered_kernel<u64, false>), dim3(gxr), dim3(rr_threads), rr_lds, st, h->db, h->ld, d,
-                                   s.q_al.as<float>(), ldq, a.wave_out, a.wave_cnt, wave_cap, n_waves, wpb, nq, group_q, s.keys.as<u64>(), cnt,
-                                   cap, oflag, (const double*)nullptr, (const double*)nullptr, h->opt.dense_debug, (const float*)a.wave_score,
-                                   (const float*)tg_thr2);
-            else
-                hipLaunchKernelGGL(dense_rerank_l2_kernel, dim3(gxr), dim3(rr_threads), rr_lds, st, h->db, h->ld, d, s.q_al.as<float>(),
-                                   ldq, a.wave_out, a.wave_cnt, wave_cap, n_waves, wpb, nq, group_q, s.keys.as<u64>(), cnt,
-                                   cap, oflag, h->opt.dense_debug);
-            if (prof) SQ_HIP(hipEventRecord(s.ev[4], st));
-            DenseFinalizeL2 fin{cnt, cap, kk, h->id_base, thr, qn2, 0.5 * eps_a + eps_b, 1, (float*)out_dist, out_idx, hs_dev, hs_raw_dev, oflag, 0};
-            if (wide_tighten) fin.thr2k = tg_thr2k;
-            SQ_TRY(select_launch_t<u64>(s.keys.as<u64>(), cnt, cap, key_stride, k, nq, s.out_keys.as<u64>(), fin, st, s.sort_tmp,
-                                        4 * stride * kk));   // ~2.7 stride k candidates per query on N(0,1) data
-        }
+        SQ_TRY(dense_bf16_enqueue(h, s, e));
     } else {
         c.all_fallback = true;  // rows wider than the MFMA scan covers: exact path for every query
         // no bfloat16 copy to stream ("dense_bf16" = 0, or no memory for it): the middle tier first where its shape rule allows
@@ -1152,299 +1191,273 @@ static int dense_enqueue(DenseHandle* h, DenseSlot& s, const float* q, int nq, i
     return SQ_OK;
 }
 
-// Finish the call enqueued on slot `s`: wait for its kernels, collect the statistics, and redo every query the
-// filter could not certify on the exact path (synchronously, on the call's stream).  h->stats = this call's.
-static int dense_resolve(DenseHandle* h, DenseSlot& s) {
-    DenseCall& c = s.call;
-    if (!c.pending) return SQ_OK;
-    c.pending = false;
+// Measurement ("dense_debug" & 8192): where the fused int8 body kernel's workgroups spent their time (100 MHz clock;
+// + 16384: printed).  Returns the kernel's own split for sq_stats_t in ms: the part after the last wave of any workgroup
+// has left the stream is the tail (thresholds + re-rank).
+static int dense_body_clocks(DenseHandle* h, DenseSlot& s, double& clk_tail_ms) {
+    std::vector<long long> ck((size_t)s.clk8_wgs * 8);
+    SQ_HIP(hipMemcpy(ck.data(), s.clk8.p, ck.size() * 8, hipMemcpyDeviceToHost));
+    long long t0 = ck[0], tend = 0;
+    for (int w = 0; w < s.clk8_wgs; ++w) t0 = std::min(t0, ck[(size_t)w * 8]), tend = std::max(tend, ck[(size_t)w * 8 + 4]);
+    double sum[5] = {0, 0, 0, 0, 0}, mx[5] = {0, 0, 0, 0, 0}, mn[5] = {1e30, 1e30, 1e30, 1e30, 1e30};
+    for (int w = 0; w < s.clk8_wgs; ++w) {
+        const long long* e = &ck[(size_t)w * 8];
+        const double v[5] = {(e[0] - t0) * 0.01, (e[1] - e[0]) * 0.01, (e[2] - e[1]) * 0.01, (e[3] - e[2]) * 0.01, (e[4] - e[3]) * 0.01};
+        for (int j = 0; j < 5; ++j) sum[j] += v[j], mx[j] = std::max(mx[j], v[j]), mn[j] = std::min(mn[j], v[j]);
+    }
+    const char* names[5] = {"start offset", "stream (first wave out)", "wave skew (all waves out)", "thresholds", "re-rank"};
+    if (h->opt.dense_debug & 16384) {
+        fprintf(stderr, "[body clocks] %d workgroups, kernel span %.1f us\n", s.clk8_wgs, (tend - t0) * 0.01);
+        for (int j = 0; j < 5; ++j) fprintf(stderr, "   %-28s min %8.1f  mean %8.1f  max %8.1f us\n", names[j], mn[j], sum[j] / s.clk8_wgs, mx[j]);
+    }
+    long long stream_end = 0;
+    for (int w = 0; w < s.clk8_wgs; ++w) stream_end = std::max(stream_end, ck[(size_t)w * 8 + 2]);
+    clk_tail_ms = (double)(tend - stream_end) * 1e-5;
+    s.clk8_wgs = 0;
+    return SQ_OK;
+}
+
+// dense_resolve, first phase: wait for the call's kernels, then timing, statistics and the bookkeeping that suspends a
+// first filter whose lists overflow call after call.
+static int dense_resolve_wait(DenseHandle* h, DenseSlot& s, const DenseCtx& e) {
+    const DenseCall& c = s.call;
+    const long long n = h->n;
+    const int nq = c.nq;
+    SQ_HIP(c.use_event ? event_wait(s.ev_done) : stream_wait(c.st));  // counts and status words are in e.hs_cnt / e.hs now
+    SQ_HIP(hipGetLastError());
+    double clk_tail_ms = -1.0;
+    if (s.clk8_wgs > 0 && (h->opt.dense_debug & 8192)) SQ_TRY(dense_body_clocks(h, s, clk_tail_ms));
+    if (c.prof) {
+        float t1 = 0, t2 = 0;
+        SQ_HIP(hipEventElapsedTime(&t1, s.ev[1], s.ev[2]));
+        SQ_HIP(hipEventElapsedTime(&t2, s.ev[0], s.ev[3]));
+        h->stats.scan_ms = t1;
+        h->stats.total_ms = t2;
+        if (h->ev_ref) {   // when the call's head / scan / re-rank / select ended, on the clock of the first traced call
+            float at[5] = {0, 0, 0, 0, 0};
+            const int order[5] = {0, 1, 2, 4, 3};
+            for (int j = 0; j < 5; ++j) (void)hipEventElapsedTime(&at[j], h->ev_ref, s.ev[order[j]]);
+            fprintf(stderr, "[smqtk_hip] trace slot %d: start %.1f | head-> %.1f | scan-> %.1f | rerank-> %.1f | select-> %.1f us\n",
+                    (int)(&s - h->slot), at[0] * 1e3f, at[1] * 1e3f, at[2] * 1e3f, at[3] * 1e3f, at[4] * 1e3f);
+        }
+        if (c.stats.scan_launches == 2) {  // (the filter path: a re-rank kernel followed the scan)
+            float t3 = 0;
+            SQ_HIP(hipEventElapsedTime(&t3, s.ev[2], s.ev[4]));
+            h->stats.rerank_ms = t3;
+            // the fused int8 call re-ranks inside the full-pass kernel: with its clocks recorded (dense_debug & 8192) the
+            // tail's share of scan_ms is reported as rerank_ms
+            if (clk_tail_ms >= 0.0) h->stats.rerank_ms = clk_tail_ms;
+        }
+    }
+    for (int qi = 0; qi < nq; ++qi) h->stats.candidates += e.hs_cnt[qi];
+    int over = 0;   // queries whose lists overflowed
+    for (int qi = 0; qi < nq; ++qi) over += (e.hs[qi] & 1u) ? 1 : 0;
+    if (c.int8) {
+        // data the measured bound does not suit (every row of a tight cluster inside the slack): the lists overflow call
+        // after call and each query pays a second tier -- after three such calls in a row the handle goes back to bf16
+        const long long cands = h->stats.candidates;   // (of this call: summed above)
+        // (... or pass so many rows that the re-rank outweighs the bytes saved: the bf16 filter passes ~50 k of 10 M)
+        const bool heavy = 2 * over > nq || cands > (long long)nq * std::max<long long>(24ll * 1024, n / 128);
+        h->overflow8 = heavy ? h->overflow8 + 1 : 0;
+        if (h->overflow8 >= 3 && h->opt.dense_int8 < 0) h->suspended8 = true;
+    }
+    if (!c.small && (!c.int8 || h->opt.dense_int8 > 0)) {   // (an int8 stage in automatic mode suspends itself first, above)
+        const bool heavy = 2 * over > nq;
+        if (h->first_suspended) {          // this call was a probe
+            if (heavy) {
+                h->probe_interval = std::min(1024u, 2u * h->probe_interval);
+                h->direct_calls = 0;   // (the next probe a whole interval from here)
+            } else {
+                h->first_suspended = false;
+                h->overflow16 = 0;
+                h->probe_interval = 16u;
+            }
+        } else {
+            h->overflow16 = heavy ? h->overflow16 + 1 : 0;
+            if (h->overflow16 >= 3) {
+                h->first_suspended = true;
+                h->direct_calls = 0;
+            }
+        }
+    }
+    return SQ_OK;
+}
+
+// Column means of the float32 rows into out[d_pad] (float64 sums over row blocks), finished on return: the L2 filter's
+// origin (rows appended later keep it) and the cosine middle tier's
+static int dense_column_means(const DenseHandle* h, DevBuf& out, hipStream_t st) {
+    const long long n = h->n, rpb = 512;
+    const int d = h->d, d_pad = h->d_pad;
+    SQ_TRY(out.reserve((size_t)d_pad * 4));
+    DevBuf colsum;
+    int rc = colsum.reserve((size_t)d * 8);
+    if (rc == SQ_OK && hipMemsetAsync(colsum.p, 0, (size_t)d * 8, st) != hipSuccess) rc = fail(SQ_ERR_HIP, "column means: memset failed");
+    if (rc == SQ_OK) rc = launch<dense_colsum_kernel>(dim3((unsigned)((n + rpb - 1) / rpb)), dim3(256), 0, st, h->db, n, h->ld, d, rpb, colsum.as<double>());
+    if (rc == SQ_OK) rc = launch<dense_center_kernel>(dim3((d_pad + 255) / 256), dim3(256), 0, st, colsum.as<double>(), n, d, d_pad, out.as<float>());
+    if (rc == SQ_OK && stream_wait(st) != hipSuccess) rc = fail(SQ_ERR_HIP, "column means failed: %s", hipGetErrorString(hipGetLastError()));
+    colsum.release();
+    return rc;
+}
+// the cosine tier's origin and per-row terms (sq_dense_mid.hpp), once per index and again after an append
+static int dense_mid_cos_terms(DenseHandle* h, hipStream_t st) {
     const long long n = h->n;
     const int d = h->d;
-    const int nq = c.nq, k = c.k;
-    const int kk = (int)(k < h->n_live ? k : h->n_live);
-    const bool cosine = h->metric == SQ_METRIC_COSINE;
-    const size_t key_bytes = cosine ? sizeof(K128) : sizeof(u64);
-    const u32 cap = c.cap;
+    if (!h->mid_cos_center.p) SQ_TRY(dense_column_means(h, h->mid_cos_center, st));
+    h->mid_cos_ld = (n + 63) / 64 * 64;
+    SQ_TRY(h->mid_cos_rows.reserve((size_t)h->mid_cos_ld * 2 * 4));
+    SQ_TRY(launch<dense_mid_cos_rows_kernel>(dim3((unsigned)((n + 31) / 32)), dim3(256), 0, st, h->db, n, h->ld, d,
+                                             (const float*)h->mid_cos_center.as<float>(), (const double*)h->cos_nx.as<double>(),
+                                             h->mid_cos_rows.as<float>(), h->mid_cos_ld));
+    h->mid_cos_n = n;
+    return dense_dead_reapply(h, 0, st);   // (the terms just built are those of every row: removed ones leave again)
+}
+
+// dense_resolve, second phase -- the middle tier (sq_dense_mid.hpp): the uncertified queries of a filtered call, 32 per
+// pass over the float32 rows, scored with 64 times less slack; whatever it certifies is final, the rest stays in `todo`
+// and goes on to the exact path.
+static int dense_mid_tier(DenseHandle* h, DenseSlot& s, const DenseCtx& e, std::vector<int>& todo) {
+    const DenseCall& c = s.call;
+    const long long n = h->n;
+    const int d = h->d, d_pad = h->d_pad;
     const u32* deadp = h->deadp();
-    const bool force_fb = h->opt.force_fallback != 0;
-    const bool small = c.small, all_fallback = c.all_fallback;
     hipStream_t st = c.st;
-    const float* q = c.q;
-    void* out_dist = c.out_dist;
-    long long* out_idx = c.out_idx;
-    u32* cnt = s.cnt.as<u32>();
-    float* thr = s.thr.as<float>();
-    double* qn2 = s.qn2.as<double>();
-    const double* cnx = h->cos_nx.as<double>();
-    const double* cnq = s.cos_nq.as<double>();
-    u32* hs_raw = reinterpret_cast<u32*>(s.status_host.p);
-    u32* hs = hs_raw + c.nq_pad;
-    u32* hs_raw_dev = nullptr;
-    SQ_TRY(s.status_host.device_ptr(reinterpret_cast<void**>(&hs_raw_dev)));
-    u32* hs_dev = hs_raw_dev + c.nq_pad;
-    const size_t l2_lds = (size_t)((d + 3) / 4 * 4) * 4;
-    h->stats = c.stats;
-    if (!all_fallback) {
-        SQ_HIP(c.use_event ? event_wait(s.ev_done) : stream_wait(st));  // counts and status words are in hs_raw / hs now
-        SQ_HIP(hipGetLastError());
-        double clk_tail_ms = -1.0;
-        if (s.clk8_wgs > 0 && (h->opt.dense_debug & 8192)) {   // measurement: where the body kernel's workgroups spent their time (100 MHz clock; + 16384: printed)
-            std::vector<long long> ck((size_t)s.clk8_wgs * 8);
-            SQ_HIP(hipMemcpy(ck.data(), s.clk8.p, ck.size() * 8, hipMemcpyDeviceToHost));
-            long long t0 = ck[0], tend = 0;
-            for (int w = 0; w < s.clk8_wgs; ++w) t0 = std::min(t0, ck[(size_t)w * 8]), tend = std::max(tend, ck[(size_t)w * 8 + 4]);
-            double sum[5] = {0, 0, 0, 0, 0}, mx[5] = {0, 0, 0, 0, 0}, mn[5] = {1e30, 1e30, 1e30, 1e30, 1e30};
-            for (int w = 0; w < s.clk8_wgs; ++w) {
-                const long long* e = &ck[(size_t)w * 8];
-                const double v[5] = {(e[0] - t0) * 0.01, (e[1] - e[0]) * 0.01, (e[2] - e[1]) * 0.01, (e[3] - e[2]) * 0.01, (e[4] - e[3]) * 0.01};
-                for (int j = 0; j < 5; ++j) sum[j] += v[j], mx[j] = std::max(mx[j], v[j]), mn[j] = std::min(mn[j], v[j]);
-            }
-            const char* names[5] = {"start offset", "stream (first wave out)", "wave skew (all waves out)", "thresholds", "re-rank"};
-            if (h->opt.dense_debug & 16384) {
-                fprintf(stderr, "[body clocks] %d workgroups, kernel span %.1f us\n", s.clk8_wgs, (tend - t0) * 0.01);
-                for (int j = 0; j < 5; ++j) fprintf(stderr, "   %-28s min %8.1f  mean %8.1f  max %8.1f us\n", names[j], mn[j], sum[j] / s.clk8_wgs, mx[j]);
-            }
-            // the kernel's own split for sq_stats_t (set below when the call was timed): the part after the last wave of any
-            // workgroup has left the stream is the tail (thresholds + re-rank)
-            long long stream_end = 0;
-            for (int w = 0; w < s.clk8_wgs; ++w) stream_end = std::max(stream_end, ck[(size_t)w * 8 + 2]);
-            clk_tail_ms = (double)(tend - stream_end) * 1e-5;
-            s.clk8_wgs = 0;
-        }
-        if (c.prof) {
-            float t1 = 0, t2 = 0;
-            SQ_HIP(hipEventElapsedTime(&t1, s.ev[1], s.ev[2]));
-            SQ_HIP(hipEventElapsedTime(&t2, s.ev[0], s.ev[3]));
-            h->stats.scan_ms = t1;
-            h->stats.total_ms = t2;
-            if (h->ev_ref) {   // when the call's head / scan / re-rank / select ended, on the clock of the first traced call
-                float e[5] = {0, 0, 0, 0, 0};
-                const int order[5] = {0, 1, 2, 4, 3};
-                for (int j = 0; j < 5; ++j) (void)hipEventElapsedTime(&e[j], h->ev_ref, s.ev[order[j]]);
-                fprintf(stderr, "[smqtk_hip] trace slot %d: start %.1f | head-> %.1f | scan-> %.1f | rerank-> %.1f | select-> %.1f us\n",
-                        (int)(&s - h->slot), e[0] * 1e3f, e[1] * 1e3f, e[2] * 1e3f, e[3] * 1e3f, e[4] * 1e3f);
-            }
-            if (c.stats.scan_launches == 2) {  // (the filter path: a re-rank kernel followed the scan)
-                float t3 = 0;
-                SQ_HIP(hipEventElapsedTime(&t3, s.ev[2], s.ev[4]));
-                h->stats.rerank_ms = t3;
-                // the fused int8 call re-ranks inside the full-pass kernel: with its clocks recorded (dense_debug & 8192) the
-                // tail's share of scan_ms is reported as rerank_ms
-                if (clk_tail_ms >= 0.0) h->stats.rerank_ms = clk_tail_ms;
-            }
-        }
-        for (int qi = 0; qi < nq; ++qi) h->stats.candidates += hs_raw[qi];
-        if (c.int8) {
-            // data the measured bound does not suit (every row of a tight cluster inside the slack): the lists overflow call
-            // after call and each query pays a second tier -- after three such calls in a row the handle goes back to bf16
-            int over = 0;
-            for (int qi = 0; qi < nq; ++qi) over += (hs[qi] & 1u) ? 1 : 0;
-            long long cands = 0;
-            for (int qi = 0; qi < nq; ++qi) cands += hs_raw[qi];
-            // (... or pass so many rows that the re-rank outweighs the bytes saved: the bf16 filter passes ~50 k of 10 M)
-            const bool heavy = 2 * over > nq || cands > (long long)nq * std::max<long long>(24ll * 1024, n / 128);
-            h->overflow8 = heavy ? h->overflow8 + 1 : 0;
-            if (h->overflow8 >= 3 && h->opt.dense_int8 < 0) h->suspended8 = true;
-        }
-        if (!small && (!c.int8 || h->opt.dense_int8 > 0)) {   // (an int8 stage in automatic mode suspends itself first, above)
-            int over = 0;
-            for (int qi = 0; qi < nq; ++qi) over += (hs[qi] & 1u) ? 1 : 0;
-            const bool heavy = 2 * over > nq;
-            if (h->first_suspended) {          // this call was a probe
-                if (heavy) {
-                    h->probe_interval = std::min(1024u, 2u * h->probe_interval);
-                    h->direct_calls = 0;   // (the next probe a whole interval from here)
-                } else {
-                    h->first_suspended = false;
-                    h->overflow16 = 0;
-                    h->probe_interval = 16u;
-                }
+    const int ldq = (d + 3) / 4 * 4;
+    const double eps_b_mid = (4.0 * d_pad + 8.0) * 1.1920928955078125e-07;
+    const FilterBound fb_mid = filter_bound(0, kEpsAMid, eps_b_mid, h->xn2_max);
+    const double alpha1 = filter_bound(0, kEpsA2, dense_eps_b(d_pad), 0.0).alpha;
+    float c1 = (float)((1.0 - fb_mid.alpha) / (1.0 - alpha1) * (1.0 - 4.8e-7));
+    const int waves = (size_t)TILE_ROWS * d_pad * 4 + (size_t)d_pad * 4 + (size_t)8 * MID_NSTAGE * MID_SLOT_BYTES <= 160 * 1024 - 64 ? 8 : 4;
+    const size_t mid_lds = (size_t)TILE_ROWS * d_pad * 4 + (size_t)d_pad * 4 + (size_t)waves * MID_NSTAGE * MID_SLOT_BYTES;
+    const int cus = cu_count(h->device);
+    const long long n_tiles = (n + 31) / 32;
+    int nrb = cus;
+    if ((long long)nrb * waves > n_tiles) nrb = (int)((n_tiles + waves - 1) / waves);
+    const long long n_waves = (long long)nrb * waves;
+    SQ_TRY(h->mid_q.reserve((size_t)MID_MAX_Q * d * 4));
+    SQ_TRY(h->mid_planes.reserve((size_t)MID_MAX_Q * d_pad * 4));
+    // [qn2 f64 x32][thr f32 x32][cnt u32 x32][oflag u32 x16][qmap i32 x32]
+    // cosine adds [cnq f64 x32][qw f32 x32][lin float2 x32]
+    SQ_TRY(h->mid_small.reserve(32 * 8 + 32 * 4 + 32 * 4 + 64 + 32 * 4 + 32 * 8 + 32 * 4 + 32 * 8));
+    SQ_TRY(h->mid_qal.reserve((size_t)MID_MAX_Q * ldq * 4));
+    SQ_TRY(h->mid_wave_out.reserve((size_t)n_waves * kWaveCap * 8));
+    SQ_TRY(h->mid_wave_cnt.reserve((size_t)n_waves * 8));
+    SQ_TRY(h->mid_keys.reserve((size_t)MID_MAX_Q * e.cap * e.key_bytes));
+    SQ_TRY(h->mid_out.reserve((size_t)MID_MAX_Q * c.k * e.key_bytes));
+    DenseCtx me = e;   // the tier's own counters, thresholds and norms; its launches take 32 queries; no counts are copied out
+    me.group_q = TILE_ROWS;
+    me.hs_cnt_dev = nullptr;
+    me.qn2 = h->mid_small.as<double>();
+    me.thr = reinterpret_cast<float*>(me.qn2 + 32);
+    me.cnt = reinterpret_cast<u32*>(me.thr + 32);
+    me.oflag = me.cnt + 32;
+    int* m_map = reinterpret_cast<int*>(me.oflag + 16);
+    double* m_cnq = reinterpret_cast<double*>(m_map + 32);
+    me.cnq = m_cnq;
+    float* m_qw = reinterpret_cast<float*>(m_cnq + 32);
+    float2* m_lin = reinterpret_cast<float2*>(m_qw + 32);
+    if (e.cosine && h->mid_cos_n != n) SQ_TRY(dense_mid_cos_terms(h, st));
+    // sample of true scores: every mid_stride-th row (about 64 k candidates per query pass the bound it gives)
+    long long mid_stride = std::min<long long>(64, std::min<long long>((long long)e.cap / (8ll * e.kk), n / (8ll * e.kk)));
+    if (mid_stride < 1) mid_stride = 1;
+    const long long mid_ns = (n + mid_stride - 1) / mid_stride;
+    const size_t mid_sample_lds = (size_t)d * 33 * 4;
+    const dim3 sample_grid((unsigned)((mid_ns + 7) / 8));
+    SQ_TRY(h->mid_sample.reserve((size_t)MID_MAX_Q * mid_ns * 4));
+    const float* mq = h->mid_q.as<float>();
+    const float* centerp = h->center.p ? h->center.as<float>() : nullptr;
+    std::vector<int> left;
+    for (size_t t0 = 0; t0 < todo.size(); t0 += MID_MAX_Q) {
+        MidSelection sel{};
+        sel.count = (int)std::min<size_t>(MID_MAX_Q, todo.size() - t0);
+        for (int j = 0; j < MID_MAX_Q; ++j) sel.idx[j] = todo[t0 + (size_t)(j < sel.count ? j : 0)];
+        SQ_TRY(launch<dense_mid_gather_kernel>(dim3(MID_MAX_Q), dim3(128), 0, st, c.q, d, sel, h->mid_q.as<float>(), m_map));
+        DenseMidArgs a{};
+        a.x = h->db;
+        a.n = n;
+        a.ld = h->ld;
+        a.d = d;
+        a.center = centerp;
+        a.norms = h->norms.as<float>();
+        a.norm_scale = c1;
+        a.qs = h->mid_planes.as<uint4>();
+        a.d_pad = d_pad;
+        a.thr = me.thr;
+        a.wave_out = h->mid_wave_out.as<uint2>();
+        a.wave_cnt = h->mid_wave_cnt.as<u32>();
+        a.wave_cap = kWaveCap;
+        a.n_tiles = n_tiles;
+        a.nrb = nrb;
+        a.rowstat = e.cosine ? h->mid_cos_rows.as<float>() : nullptr;
+        a.rowstat_ld = h->mid_cos_ld;
+        a.qw = m_qw;
+        const DenseSurvivors v = dense_survivors(h->mid_wave_out, h->mid_wave_cnt, h->mid_qal, h->mid_keys, h->mid_out, h->fb_sort, n_waves, 2, ldq,
+                                                 sel.count);
+        SQ_TRY(by_metric(e.cosine, [&](auto m) {
+            using M = decltype(m);
+            // query planes, a sample of true scores, the threshold from it
+            if constexpr (M::cosine) {
+                SQ_TRY(launch<dense_mid_cos_queries_kernel>(dim3(MID_MAX_Q), dim3(256), 0, st, h->mid_q.as<float>(), sel.count, d, d_pad,
+                                                            (const float*)h->mid_cos_center.as<float>(), eps_b_mid, h->mid_planes.as<uint4>(), me.qn2, me.thr,
+                                                            me.cnt, me.oflag, h->mid_qal.as<float>(), ldq, m_qw, m_lin));
+                SQ_TRY(launch<dense_cos_qnorm_kernel>(dim3(1), dim3(64), 0, st, mq, sel.count, d, m_cnq));
+                SQ_TRY(launch<dense_mid_cos_sample_kernel>(sample_grid, dim3(256), mid_sample_lds, st, h->db, h->ld, d, n, mid_stride, mid_ns, mq,
+                                                           (const double*)me.qn2, (const double*)h->cos_nx.as<double>(), h->mid_sample.as<float>(), deadp));
+                SQ_TRY(launch<kth_threshold_f32_kernel<DenseMidCosThrPost>>(
+                    dim3(sel.count), dim3(1024), 0, st, h->mid_sample.as<float>(), mid_ns, e.kk, me.thr,
+                    DenseMidCosThrPost{m_map, (const double*)c.out_dist, (const u32*)e.hs_dev, c.k, e.kk, (const float2*)m_lin}));
             } else {
-                h->overflow16 = heavy ? h->overflow16 + 1 : 0;
-                if (h->overflow16 >= 3) {
-                    h->first_suspended = true;
-                    h->direct_calls = 0;
-                }
+                SQ_TRY(launch<dense_prep_queries_kernel>(dim3(MID_MAX_Q), dim3(256), 0, st, h->mid_q.as<float>(), sel.count, d, d_pad, h->metric,
+                                                         h->mid_planes.as<uint4>(), me.qn2, me.thr, me.cnt, me.oflag, h->mid_qal.as<float>(), ldq, centerp));
+                SQ_TRY(launch_lds<dense_mid_sample_kernel>(512 * 33 * 4, sample_grid, dim3(256), mid_sample_lds, st, h->db, h->ld, d, n, mid_stride, mid_ns,
+                                                           mq, (const double*)me.qn2, h->mid_sample.as<float>(), deadp));
+                SQ_TRY(launch<kth_threshold_f32_kernel<DenseMidThrPost>>(
+                    dim3(sel.count), dim3(1024), 0, st, h->mid_sample.as<float>(), mid_ns, e.kk, me.thr,
+                    DenseMidThrPost{m_map, (const float*)c.out_dist, (const u32*)e.hs_dev, c.k, e.kk, me.qn2, fb_mid.beta}));
             }
-        }
+            SQ_TRY(waves == 8 ? launch_lds<dense_mid_scan_kernel<8, M::cosine>>(160 * 1024, dim3(nrb), dim3(512), mid_lds, st, a)
+                              : launch_lds<dense_mid_scan_kernel<4, M::cosine>>(160 * 1024, dim3(nrb), dim3(256), mid_lds, st, a));
+            auto fin = me.filter_fin<M>(M::cosine ? 0.0 : fb_mid.beta);
+            fin.qmap = m_map;
+            if constexpr (M::cosine) fin.lin = m_lin;
+            return dense_survivor_tail<M>(h, me, v, c.k, fin, st);
+        }));
+        h->stats.scan_launches++;
+        h->stats.bytes_scanned += n * (long long)d * 4;
+        h->stats.mid_tier_queries += sel.count;
+        SQ_HIP(stream_wait(st));  // the status words of these queries are in e.hs now
+        SQ_HIP(hipGetLastError());
+        for (int j = 0; j < sel.count; ++j)
+            if (e.hs[sel.idx[j]] != 0) left.push_back(sel.idx[j]);
     }
-    // Exact full-keys path, a group of up to 8 queries per pass over the matrix (dense_exact_group_kernel):
-    // exact keys for all n rows, then a two-level select -- the k-th smallest of every fb_stride-th exact
-    // distance bounds the k-th of all, the keys at or below it (~2 k fb_stride of them) are compacted by the
-    // whole device and the one-workgroup select runs on those.  (That select over all n keys directly: 13 ms
-    // per query at 10 M rows against 1.2 ms for the keys.)  Ties that overflow the compacted list, or too few
-    // finite distances, go on to the select over all keys.
-    long long fb_stride = std::min<long long>(64, std::min<long long>((long long)cap / (4ll * kk), n / (8ll * kk)));
+    todo.swap(left);
+    return SQ_OK;
+}
+
+// dense_resolve, third phase -- the exact full-keys path, a group of up to 8 queries per pass over the matrix
+// (dense_exact_group_kernel): exact keys for all n rows, then a two-level select -- the k-th smallest of every
+// fb_stride-th exact distance bounds the k-th of all, the keys at or below it (~2 k fb_stride of them) are compacted by
+// the whole device and the one-workgroup select runs on those.  (That select over all n keys directly: 13 ms
+// per query at 10 M rows against 1.2 ms for the keys.)  Ties that overflow the compacted list, or too few
+// finite distances, go on to the select over all keys.
+static int dense_exact_path(DenseHandle* h, DenseSlot& s, const DenseCtx& e, const std::vector<int>& todo) {
+    const DenseCall& c = s.call;
+    const long long n = h->n;
+    const int d = h->d;
+    const u32* deadp = h->deadp();
+    hipStream_t st = c.st;
+    const double* cnx = h->cos_nx.as<double>();
+    long long fb_stride = std::min<long long>(64, std::min<long long>((long long)e.cap / (4ll * e.kk), n / (8ll * e.kk)));
     if (n < 65536 || fb_stride < 2 || (h->opt.dense_debug & 128)) fb_stride = 0;  // debug 128: measurement, full select
     const long long fb_ns = fb_stride ? (n + fb_stride - 1) / fb_stride : 0;
-    std::vector<int> todo;
-    for (int qi = 0; qi < nq; ++qi)
-        if (all_fallback || (!small && (hs[qi] != 0 || force_fb))) todo.push_back(qi);
-    if (todo.empty()) return SQ_OK;
-    // ---- middle tier (sq_dense_mid.hpp): the uncertified queries of a filtered L2 call, 32 per pass over the float32
-    // rows, scored with 64 times less slack; whatever it certifies is final, the rest goes on to the exact path
-    if (c.mid_direct)
-        for (int qi = 0; qi < nq; ++qi) hs[qi] = 1u;   // (no first-filter result to take a bound from: DenseMid*ThrPost)
-    if ((!all_fallback || c.mid_direct) && !small && !force_fb && h->opt.dense_mid_tier != 0 && dense_mid_shape_ok(h)) {
-        const int d_pad = h->d_pad;
-        const int ldq = (d + 3) / 4 * 4;
-        const double eps_b_mid = (4.0 * d_pad + 8.0) * 1.1920928955078125e-07;
-        const FilterBound fb_mid = filter_bound(0, kEpsAMid, eps_b_mid, h->xn2_max);
-        const double alpha1 = filter_bound(0, kEpsA2, dense_eps_b(d_pad), 0.0).alpha;
-        float c1 = (float)((1.0 - fb_mid.alpha) / (1.0 - alpha1) * (1.0 - 4.8e-7));
-        const int waves = (size_t)TILE_ROWS * d_pad * 4 + (size_t)d_pad * 4 + (size_t)8 * MID_NSTAGE * MID_SLOT_BYTES <= 160 * 1024 - 64 ? 8 : 4;
-        const size_t mid_lds = (size_t)TILE_ROWS * d_pad * 4 + (size_t)d_pad * 4 + (size_t)waves * MID_NSTAGE * MID_SLOT_BYTES;
-        const int cus = cu_count(h->device);
-        const long long n_tiles = (n + 31) / 32;
-        int nrb = cus;
-        if ((long long)nrb * waves > n_tiles) nrb = (int)((n_tiles + waves - 1) / waves);
-        const long long n_waves = (long long)nrb * waves;
-        const u32 wave_cap = 2048;
-        SQ_TRY(h->mid_q.reserve((size_t)MID_MAX_Q * d * 4));
-        SQ_TRY(h->mid_planes.reserve((size_t)MID_MAX_Q * d_pad * 4));
-        // [qn2 f64 x32][thr f32 x32][cnt u32 x32][oflag u32 x16][qmap i32 x32]
-        // cosine adds [cnq f64 x32][qw f32 x32][lin float2 x32]
-        SQ_TRY(h->mid_small.reserve(32 * 8 + 32 * 4 + 32 * 4 + 64 + 32 * 4 + 32 * 8 + 32 * 4 + 32 * 8));
-        SQ_TRY(h->mid_qal.reserve((size_t)MID_MAX_Q * ldq * 4));
-        SQ_TRY(h->mid_wave_out.reserve((size_t)n_waves * wave_cap * 8));
-        SQ_TRY(h->mid_wave_cnt.reserve((size_t)n_waves * 8));
-        SQ_TRY(h->mid_keys.reserve((size_t)MID_MAX_Q * cap * key_bytes));
-        SQ_TRY(h->mid_out.reserve((size_t)MID_MAX_Q * k * key_bytes));
-        double* m_qn2 = h->mid_small.as<double>();
-        float* m_thr = reinterpret_cast<float*>(m_qn2 + 32);
-        u32* m_cnt = reinterpret_cast<u32*>(m_thr + 32);
-        u32* m_oflag = m_cnt + 32;
-        int* m_map = reinterpret_cast<int*>(m_oflag + 16);
-        double* m_cnq = reinterpret_cast<double*>(m_map + 32);
-        float* m_qw = reinterpret_cast<float*>(m_cnq + 32);
-        float2* m_lin = reinterpret_cast<float2*>(m_qw + 32);
-        if (cosine && h->mid_cos_n != n) {
-            // the cosine tier's origin and per-row terms (sq_dense_mid.hpp), once per index and again after an append
-            if (!h->mid_cos_center.p) {
-                SQ_TRY(h->mid_cos_center.reserve((size_t)d_pad * 4));
-                DevBuf colsum;
-                SQ_TRY(colsum.reserve((size_t)d * 8));
-                SQ_HIP(hipMemsetAsync(colsum.p, 0, (size_t)d * 8, st));
-                const long long rpb = 512;
-                hipLaunchKernelGGL(dense_colsum_kernel, dim3((unsigned)((n + rpb - 1) / rpb)), dim3(256), 0, st, h->db, n, h->ld, d, rpb,
-                                   colsum.as<double>());
-                hipLaunchKernelGGL(dense_center_kernel, dim3((d_pad + 255) / 256), dim3(256), 0, st, colsum.as<double>(), n, d, d_pad,
-                                   h->mid_cos_center.as<float>());
-                const hipError_t e = stream_wait(st);
-                colsum.release();
-                SQ_HIP(e);
-            }
-            h->mid_cos_ld = (n + 63) / 64 * 64;
-            SQ_TRY(h->mid_cos_rows.reserve((size_t)h->mid_cos_ld * 2 * 4));
-            hipLaunchKernelGGL(dense_mid_cos_rows_kernel, dim3((unsigned)((n + 31) / 32)), dim3(256), 0, st, h->db, n, h->ld, d,
-                               (const float*)h->mid_cos_center.as<float>(), (const double*)h->cos_nx.as<double>(),
-                               h->mid_cos_rows.as<float>(), h->mid_cos_ld);
-            SQ_HIP(hipGetLastError());
-            h->mid_cos_n = n;
-            SQ_TRY(dense_dead_reapply(h, 0, st));   // (the terms just built are those of every row: removed ones leave again)
-        }
-        // sample of true scores: every mid_stride-th row (about 64 k candidates per query pass the bound it gives)
-        long long mid_stride = std::min<long long>(64, std::min<long long>((long long)cap / (8ll * kk), n / (8ll * kk)));
-        if (mid_stride < 1) mid_stride = 1;
-        const long long mid_ns = (n + mid_stride - 1) / mid_stride;
-        const size_t mid_sample_lds = (size_t)d * 33 * 4;
-        SQ_TRY(h->mid_sample.reserve((size_t)MID_MAX_Q * mid_ns * 4));
-        std::vector<int> left;
-        for (size_t t0 = 0; t0 < todo.size(); t0 += MID_MAX_Q) {
-            MidSelection sel{};
-            sel.count = (int)std::min<size_t>(MID_MAX_Q, todo.size() - t0);
-            for (int j = 0; j < MID_MAX_Q; ++j) sel.idx[j] = todo[t0 + (size_t)(j < sel.count ? j : 0)];
-            hipLaunchKernelGGL(dense_mid_gather_kernel, dim3(MID_MAX_Q), dim3(128), 0, st, q, d, sel, h->mid_q.as<float>(), m_map);
-            if (cosine) {
-                hipLaunchKernelGGL(dense_mid_cos_queries_kernel, dim3(MID_MAX_Q), dim3(256), 0, st, h->mid_q.as<float>(), sel.count, d, d_pad,
-                                   (const float*)h->mid_cos_center.as<float>(), eps_b_mid, h->mid_planes.as<uint4>(), m_qn2, m_thr, m_cnt,
-                                   m_oflag, h->mid_qal.as<float>(), ldq, m_qw, m_lin);
-                hipLaunchKernelGGL(dense_cos_qnorm_kernel, dim3(1), dim3(64), 0, st, (const float*)h->mid_q.as<float>(), sel.count, d, m_cnq);
-                hipLaunchKernelGGL(dense_mid_cos_sample_kernel, dim3((unsigned)((mid_ns + 7) / 8)), dim3(256), mid_sample_lds, st, h->db, h->ld,
-                                   d, n, mid_stride, mid_ns, (const float*)h->mid_q.as<float>(), (const double*)m_qn2,
-                                   (const double*)h->cos_nx.as<double>(), h->mid_sample.as<float>(), deadp);
-                hipLaunchKernelGGL((kth_threshold_f32_kernel<DenseMidCosThrPost>), dim3(sel.count), dim3(1024), 0, st,
-                                   h->mid_sample.as<float>(), mid_ns, kk, m_thr,
-                                   DenseMidCosThrPost{m_map, (const double*)out_dist, (const u32*)hs_dev, k, kk, (const float2*)m_lin});
-            } else {
-                hipLaunchKernelGGL(dense_prep_queries_kernel, dim3(MID_MAX_Q), dim3(256), 0, st, h->mid_q.as<float>(), sel.count, d, d_pad,
-                                   h->metric, h->mid_planes.as<uint4>(), m_qn2, m_thr, m_cnt, m_oflag, h->mid_qal.as<float>(), ldq,
-                                   h->center.p ? h->center.as<float>() : nullptr);
-                SQ_TRY(launch_lds<dense_mid_sample_kernel>(512 * 33 * 4, dim3((unsigned)((mid_ns + 7) / 8)), dim3(256), mid_sample_lds, st, h->db, h->ld, d, n,
-                                                           mid_stride, mid_ns, (const float*)h->mid_q.as<float>(), (const double*)m_qn2, h->mid_sample.as<float>(), deadp));
-                hipLaunchKernelGGL((kth_threshold_f32_kernel<DenseMidThrPost>), dim3(sel.count), dim3(1024), 0, st, h->mid_sample.as<float>(),
-                                   mid_ns, kk, m_thr,
-                                   DenseMidThrPost{m_map, (const float*)out_dist, (const u32*)hs_dev, k, kk, m_qn2, fb_mid.beta});
-            }
-            DenseMidArgs a{};
-            a.x = h->db;
-            a.n = n;
-            a.ld = h->ld;
-            a.d = d;
-            a.center = h->center.p ? h->center.as<float>() : nullptr;
-            a.norms = h->norms.as<float>();
-            a.norm_scale = c1;
-            a.qs = h->mid_planes.as<uint4>();
-            a.d_pad = d_pad;
-            a.thr = m_thr;
-            a.wave_out = h->mid_wave_out.as<uint2>();
-            a.wave_cnt = h->mid_wave_cnt.as<u32>();
-            a.wave_cap = wave_cap;
-            a.n_tiles = n_tiles;
-            a.nrb = nrb;
-            a.rowstat = cosine ? h->mid_cos_rows.as<float>() : nullptr;
-            a.rowstat_ld = h->mid_cos_ld;
-            a.qw = m_qw;
-            if (cosine) {
-                if (waves == 8)
-                    SQ_TRY(launch_lds<dense_mid_scan_kernel<8, true>>(160 * 1024, dim3(nrb), dim3(512), mid_lds, st, a));
-                else
-                    SQ_TRY(launch_lds<dense_mid_scan_kernel<4, true>>(160 * 1024, dim3(nrb), dim3(256), mid_lds, st, a));
-            } else if (waves == 8) {
-                SQ_TRY(launch_lds<dense_mid_scan_kernel<8, false>>(160 * 1024, dim3(nrb), dim3(512), mid_lds, st, a));
-            } else {
-                SQ_TRY(launch_lds<dense_mid_scan_kernel<4, false>>(160 * 1024, dim3(nrb), dim3(256), mid_lds, st, a));
-            }
-            const int wpb = 2;
-            const size_t rr_lds = ldq <= 156 ? (size_t)32 * (ldq + 4) * 4 : 0;
-            if (cosine) {
-                hipLaunchKernelGGL(dense_rerank_cos_kernel, dim3((unsigned)((n_waves + wpb - 1) / wpb)), dim3(128 * wpb), rr_lds, st, h->db, h->ld,
-                                   d, h->mid_qal.as<float>(), ldq, a.wave_out, a.wave_cnt, wave_cap, n_waves, wpb, sel.count, TILE_ROWS,
-                                   h->mid_keys.as<K128>(), m_cnt, cap, m_oflag, cnx, (const double*)m_cnq, 0);
-                DenseFinalizeCos fin{m_cnt, cap, kk, h->id_base, m_thr, 0.0, 1, (double*)out_dist, out_idx, hs_dev, nullptr, m_oflag, 0};
-                fin.qmap = m_map;
-                fin.lin = m_lin;
-                SQ_TRY(select_launch_t<K128>(h->mid_keys.as<K128>(), m_cnt, cap, (long long)cap, k, sel.count, h->mid_out.as<K128>(), fin, st,
-                                             h->fb_sort));
-            } else {
-                hipLaunchKernelGGL(dense_rerank_l2_kernel, dim3((unsigned)((n_waves + wpb - 1) / wpb)), dim3(128 * wpb), rr_lds, st, h->db, h->ld, d,
-                                   h->mid_qal.as<float>(), ldq, a.wave_out, a.wave_cnt, wave_cap, n_waves, wpb, sel.count, TILE_ROWS,
-                                   h->mid_keys.as<u64>(), m_cnt, cap, m_oflag, 0);
-                DenseFinalizeL2 fin{m_cnt, cap, kk, h->id_base, m_thr, m_qn2, fb_mid.beta, 1, (float*)out_dist, out_idx, hs_dev, nullptr, m_oflag, 0};
-                fin.qmap = m_map;
-                SQ_TRY(select_launch_t<u64>(h->mid_keys.as<u64>(), m_cnt, cap, (long long)cap, k, sel.count, h->mid_out.as<u64>(), fin, st,
-                                            h->fb_sort));
-            }
-            h->stats.scan_launches++;
-            h->stats.bytes_scanned += n * (long long)d * 4;
-            h->stats.mid_tier_queries += sel.count;
-            SQ_HIP(stream_wait(st));  // the status words of these queries are in hs now
-            SQ_HIP(hipGetLastError());
-            for (int j = 0; j < sel.count; ++j)
-                if (hs[sel.idx[j]] != 0) left.push_back(sel.idx[j]);
-        }
-        todo.swap(left);
-        if (todo.empty()) return SQ_OK;
-    }
     // group size: the key arrays of a group stay under 4 GB; rows beyond the group kernel's depth go one by one
-    int gmax = (int)std::min<long long>(EXACT_GROUP, std::max<long long>(1, (4ll << 30) / (n * (long long)key_bytes)));
+    int gmax = (int)std::min<long long>(EXACT_GROUP, std::max<long long>(1, (4ll << 30) / (n * (long long)e.key_bytes)));
     if (d > (128 << EXACT_GROUP_DEPTH) || (h->opt.dense_debug & 256)) gmax = 1;    // debug 256: measurement, one query per pass
     const size_t grp_lds = (size_t)EXACT_GROUP * ((d + 3) / 4 * 4) * 4;
     constexpr int grp_lds_max = 160 * 1024 - 256;   // (the attribute is set once per device: the largest group any index asks for)
     const bool grp_ok = grp_lds <= (size_t)grp_lds_max && d <= (128 << EXACT_GROUP_DEPTH);
     // the exact path keeps its own per-query counters: the slot's belong to a call that may still be in flight
     // when another asynchronous call's queries are redone
-    SQ_TRY(h->fb_cnt.reserve((size_t)(nq + 64) * 4));
+    SQ_TRY(h->fb_cnt.reserve((size_t)(c.nq + 64) * 4));
     u32* full_cnt = h->fb_cnt.as<u32>();
     for (size_t t0 = 0; t0 < todo.size(); t0 += (size_t)gmax) {
         const int gn = (int)std::min<size_t>((size_t)gmax, todo.size() - t0);
@@ -1452,89 +1465,93 @@ static int dense_resolve(DenseHandle* h, DenseSlot& s) {
         for (int g = 0; g < EXACT_GROUP; ++g) grp.idx[g] = todo[t0 + (size_t)(g < gn ? g : 0)];
         grp.count = gn;
         h->stats.fallback_queries += gn;
-        SQ_TRY(h->big_keys.reserve((size_t)gn * n * key_bytes));
+        SQ_TRY(h->big_keys.reserve((size_t)gn * n * e.key_bytes));
         float* fb_sample = nullptr;
         float* fb_thr = nullptr;
         u32* fb_cnt = nullptr;
         if (fb_stride) {
             SQ_TRY(h->fb_sample.reserve((size_t)gn * fb_ns * 4 + 256));
-            SQ_TRY(h->fb_keys.reserve((size_t)gn * cap * key_bytes));
+            SQ_TRY(h->fb_keys.reserve((size_t)gn * e.cap * e.key_bytes));
             fb_thr = h->fb_sample.as<float>();               // [8] thresholds | [8] counts | samples
             fb_cnt = reinterpret_cast<u32*>(fb_thr + 8);
             fb_sample = fb_thr + 64;
         }
         unsigned gx = (unsigned)((n + 255) / 256);
         if (gx > 8192) gx = 8192;
-        if (grp_ok) {
-            if (cosine)
-                SQ_TRY(launch_lds<dense_exact_group_kernel<true, K128>>(grp_lds_max, dim3(gx), dim3(256), grp_lds, st, h->db, h->ld, d, q,
-                                                                        grp, n, h->big_keys.as<K128>(), fb_sample, fb_ns, (int)fb_stride, cnx, cnq, deadp));
-            else
-                SQ_TRY(launch_lds<dense_exact_group_kernel<false, u64>>(grp_lds_max, dim3(gx), dim3(256), grp_lds, st, h->db, h->ld, d, q,
-                                                                        grp, n, h->big_keys.as<u64>(), fb_sample, fb_ns, (int)fb_stride, nullptr, nullptr, deadp));
-        } else {  // one query per pass (gmax == 1 here)
-            const int qi = grp.idx[0];
-            if (cosine)
-                hipLaunchKernelGGL(dense_exact_cos_kernel, dim3(gx, 1), dim3(256), 0, st, h->db, h->ld, d,
-                                   q + (long long)qi * d, nullptr, full_cnt + qi, (u32)n, n, 0ll, h->big_keys.as<K128>(), n, cnx,
-                                   cnq + qi, fb_sample, (int)fb_stride, deadp);
-            else
-                hipLaunchKernelGGL(dense_exact_l2_kernel, dim3(gx, 1), dim3(256), l2_lds, st, h->db, h->ld, d,
-                                   q + (long long)qi * d, nullptr, full_cnt + qi, (u32)n, n, 0ll, h->big_keys.as<u64>(), n,
-                                   fb_sample, (int)fb_stride, deadp);
-        }
         h->stats.scan_launches++;
         h->stats.bytes_scanned += n * (long long)d * 4;
         bool done[EXACT_GROUP] = {false, false, false, false, false, false, false, false};
-        if (fb_stride) {
-            hipLaunchKernelGGL((kth_threshold_f32_kernel<KthIdentity>), dim3(gn), dim3(1024), 0, st, fb_sample, fb_ns, kk, fb_thr,
-                               KthIdentity{});
-            hipLaunchKernelGGL(fill_u32_kernel, dim3(1), dim3(64), 0, st, fb_cnt, (long long)gn, 0u);
-            const unsigned gc = (unsigned)std::min<long long>((n + 1023) / 1024, 512);
-            if (cosine) {
-                hipLaunchKernelGGL((dense_compact_keys_kernel<K128>), dim3(gc, gn), dim3(256), 0, st, h->big_keys.as<K128>(), n,
-                                   fb_thr, h->fb_keys.as<K128>(), cap, fb_cnt);
-                SQ_TRY(h->fb_out.reserve((size_t)gn * k * key_bytes));
-                SQ_TRY(select_launch_t<K128>(h->fb_keys.as<K128>(), fb_cnt, cap, (long long)cap, k, gn, h->fb_out.as<K128>(),
-                                             with_dead(DenseFinalizeCos{fb_cnt, cap, kk, h->id_base, thr, 0.0, 2, (double*)out_dist, out_idx,
-                                                                        hs_dev, nullptr, nullptr, 0, grp}, deadp),
-                                             st, h->fb_sort));
-            } else {
-                hipLaunchKernelGGL((dense_compact_keys_kernel<u64>), dim3(gc, gn), dim3(256), 0, st, h->big_keys.as<u64>(), n,
-                                   fb_thr, h->fb_keys.as<u64>(), cap, fb_cnt);
-                SQ_TRY(h->fb_out.reserve((size_t)gn * k * key_bytes));
-                SQ_TRY(select_launch_t<u64>(h->fb_keys.as<u64>(), fb_cnt, cap, (long long)cap, k, gn, h->fb_out.as<u64>(),
-                                            with_dead(DenseFinalizeL2{fb_cnt, cap, kk, h->id_base, thr, qn2, 0.0, 2,
-                                                                      (float*)out_dist, out_idx, hs_dev, nullptr, nullptr, 0, grp}, deadp),
-                                            st, h->fb_sort));
+        SQ_TRY(by_metric(e.cosine, [&](auto m) {
+            using M = decltype(m);
+            using K = typename M::Key;
+            K* big = h->big_keys.as<K>();
+            if (grp_ok) {
+                SQ_TRY(launch_lds<dense_exact_group_kernel<M::cosine, K>>(grp_lds_max, dim3(gx), dim3(256), grp_lds, st, h->db, h->ld, d, c.q, grp, n, big,
+                                                                          fb_sample, fb_ns, (int)fb_stride, M::cosine ? cnx : nullptr,
+                                                                          M::cosine ? e.cnq : nullptr, deadp));
+            } else {  // one query per pass (gmax == 1 here)
+                const int qi = grp.idx[0];
+                if constexpr (M::cosine)
+                    SQ_TRY(launch<dense_exact_cos_kernel>(dim3(gx, 1), dim3(256), 0, st, h->db, h->ld, d, c.q + (long long)qi * d, nullptr, full_cnt + qi,
+                                                          (u32)n, n, 0ll, big, n, cnx, e.cnq + qi, fb_sample, (int)fb_stride, deadp));
+                else
+                    SQ_TRY(launch<dense_exact_l2_kernel>(dim3(gx, 1), dim3(256), (size_t)((d + 3) / 4 * 4) * 4, st, h->db, h->ld, d, c.q + (long long)qi * d,
+                                                         nullptr, full_cnt + qi, (u32)n, n, 0ll, big, n, fb_sample, (int)fb_stride, deadp));
             }
-            SQ_HIP(stream_wait(st));  // the status words of the group are in hs now
-            SQ_HIP(hipGetLastError());
-            for (int g = 0; g < gn; ++g) done[g] = hs[grp.idx[g]] == 0;
-        }
-        for (int g = 0; g < gn; ++g) {
-            if (done[g]) continue;
-            const int qi = grp.idx[g];
-            hipLaunchKernelGGL(fill_u32_kernel, dim3(1), dim3(64), 0, st, full_cnt + qi, 1ll, (u32)n);
-            SQ_TRY(h->fb_out.reserve((size_t)k * key_bytes));
-            if (cosine) {
-                SQ_TRY(select_launch_t<K128>(h->big_keys.as<K128>() + (long long)g * n, full_cnt + qi, (u32)n, n, k, 1,
-                                             h->fb_out.as<K128>(),
-                                             with_dead(DenseFinalizeCos{full_cnt, (u32)n, kk, h->id_base, thr, 0.0, 0, (double*)out_dist, out_idx,
-                                                                        hs_dev, nullptr, nullptr, qi}, deadp),
-                                             st, h->fb_sort));
-            } else {
-                SQ_TRY(select_launch_t<u64>(h->big_keys.as<u64>() + (long long)g * n, full_cnt + qi, (u32)n, n, k, 1,
-                                            h->fb_out.as<u64>(),
-                                            with_dead(DenseFinalizeL2{full_cnt, (u32)n, kk, h->id_base, thr, qn2, 0.0, 0,
-                                                                      (float*)out_dist, out_idx, hs_dev, nullptr, nullptr, qi}, deadp),
-                                            st, h->fb_sort));
+            if (fb_stride) {
+                SQ_TRY(launch<kth_threshold_f32_kernel<KthIdentity>>(dim3(gn), dim3(1024), 0, st, fb_sample, fb_ns, e.kk, fb_thr, KthIdentity{}));
+                SQ_TRY(launch<fill_u32_kernel>(dim3(1), dim3(64), 0, st, fb_cnt, (long long)gn, 0u));
+                const unsigned gc = (unsigned)std::min<long long>((n + 1023) / 1024, 512);
+                SQ_TRY(launch<dense_compact_keys_kernel<K>>(dim3(gc, gn), dim3(256), 0, st, big, n, fb_thr, h->fb_keys.as<K>(), e.cap, fb_cnt));
+                SQ_TRY(h->fb_out.reserve((size_t)gn * c.k * e.key_bytes));
+                auto fin = M::finalize(e, fb_cnt, e.cap, 2);
+                fin.sel = grp;
+                fin.dead = deadp;   // (the keys hold removed rows)
+                SQ_TRY(select_launch_t<K>(h->fb_keys.as<K>(), fb_cnt, e.cap, (long long)e.cap, c.k, gn, h->fb_out.as<K>(), fin, st, h->fb_sort));
+                SQ_HIP(stream_wait(st));  // the status words of the group are in e.hs now
+                SQ_HIP(hipGetLastError());
+                for (int g = 0; g < gn; ++g) done[g] = e.hs[grp.idx[g]] == 0;
             }
-        }
+            for (int g = 0; g < gn; ++g) {
+                if (done[g]) continue;
+                const int qi = grp.idx[g];
+                SQ_TRY(launch<fill_u32_kernel>(dim3(1), dim3(64), 0, st, full_cnt + qi, 1ll, (u32)n));
+                SQ_TRY(h->fb_out.reserve((size_t)c.k * e.key_bytes));
+                auto fin = M::finalize(e, full_cnt, (u32)n, 0);
+                fin.q0 = qi;
+                fin.dead = deadp;
+                SQ_TRY(select_launch_t<K>(big + (long long)g * n, full_cnt + qi, (u32)n, n, c.k, 1, h->fb_out.as<K>(), fin, st, h->fb_sort));
+            }
+            return SQ_OK;
+        }));
     }
     SQ_HIP(hipStreamSynchronize(st));
     SQ_HIP(hipGetLastError());
     return SQ_OK;
+}
+
+// Finish the call enqueued on slot `s`: wait for its kernels, collect the statistics, and redo every query the
+// filter could not certify -- middle tier, then exact path (synchronously, on the call's stream).  h->stats = this call's.
+static int dense_resolve(DenseHandle* h, DenseSlot& s) {
+    DenseCall& c = s.call;
+    if (!c.pending) return SQ_OK;
+    c.pending = false;
+    DenseCtx e{};
+    SQ_TRY(e.bind(h, s));
+    h->stats = c.stats;
+    if (!c.all_fallback) SQ_TRY(dense_resolve_wait(h, s, e));
+    const bool force_fb = h->opt.force_fallback != 0;
+    std::vector<int> todo;
+    for (int qi = 0; qi < c.nq; ++qi)
+        if (c.all_fallback || (!c.small && (e.hs[qi] != 0 || force_fb))) todo.push_back(qi);
+    if (todo.empty()) return SQ_OK;
+    if (c.mid_direct)
+        for (int qi = 0; qi < c.nq; ++qi) e.hs[qi] = 1u;   // (no first-filter result to take a bound from: DenseMid*ThrPost)
+    if ((!c.all_fallback || c.mid_direct) && !c.small && !force_fb && h->opt.dense_mid_tier != 0 && dense_mid_shape_ok(h)) {
+        SQ_TRY(dense_mid_tier(h, s, e, todo));
+        if (todo.empty()) return SQ_OK;
+    }
+    return dense_exact_path(h, s, e, todo);
 }
 
 // Finish every asynchronous call still in flight, oldest first.
@@ -1597,10 +1614,11 @@ static int dense_build_rows(DenseHandle* h, long long row_base, int parts = ROWS
     if (cosine) {
         SQ_TRY(inv.reserve((size_t)(n_pad - row_base) * 4));
         invp = inv.as<float>() - row_base;
-        if (stats)
-            hipLaunchKernelGGL(dense_cos_norm_kernel, dim3((unsigned)((n - row_base + 255) / 256)), dim3(256), 0, 0, h->db, n,
-                               h->ld, d, h->cos_nx.as<double>(), row_base);
     }
+    int rc = SQ_OK;
+    if (cosine && stats)
+        rc = launch<dense_cos_norm_kernel>(dim3((unsigned)((n - row_base + 255) / 256)), dim3(256), 0, nullptr, h->db, n, h->ld, d,
+                                           h->cos_nx.as<double>(), row_base);
     float* centerp = h->center.p ? h->center.as<float>() : nullptr;
     float* norms1p = nullptr;
     double shrink2 = 1.0, shrink1 = 1.0;
@@ -1610,19 +1628,18 @@ static int dense_build_rows(DenseHandle* h, long long row_base, int parts = ROWS
         shrink2 = 1.0 - filter_bound(0, kEpsA2, dense_eps_b(d_pad), 0.0).alpha;
         shrink1 = 1.0 - filter_bound(0, kEpsA1, dense_eps_b(d_pad), 0.0).alpha;
     }
-    if (stats || (copy && cosine))
-        hipLaunchKernelGGL(dense_rowstats_kernel, dim3((unsigned)((n_pad - row_base) / 32)), dim3(256), 0, 0, h->db, n, h->ld,
-                           d, n_pad, h->scratch.as<u32>(), h->norms.as<float>(), invp, centerp, norms1p, shrink2, shrink1,
-                           row_base);
-    if (copy) {
-        const long long chunks = (n_pad - row_base) * (long long)(d_pad / 8);
-        hipLaunchKernelGGL(dense_build_scan_kernel, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, 0, h->db, n,
-                           h->ld, d, d_pad, n_pad, invp, centerp, h->scan.as<uint4>(), row_base);
-    }
+    if (rc == SQ_OK && (stats || (copy && cosine)))
+        rc = launch<dense_rowstats_kernel>(dim3((unsigned)((n_pad - row_base) / 32)), dim3(256), 0, nullptr, h->db, n, h->ld, d, n_pad,
+                                           h->scratch.as<u32>(), h->norms.as<float>(), invp, centerp, norms1p, shrink2, shrink1, row_base);
+    const long long chunks = (n_pad - row_base) * (long long)(d_pad / 8);
+    if (rc == SQ_OK && copy)
+        rc = launch<dense_build_scan_kernel>(dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, nullptr, h->db, n, h->ld, d, d_pad, n_pad, invp,
+                                             centerp, h->scan.as<uint4>(), row_base);
     u32 bits = 0;
     hipError_t e = hipMemcpy(&bits, h->scratch.p, 4, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     inv.release();
+    if (rc != SQ_OK) return rc;
     if (e != hipSuccess) return fail(SQ_ERR_HIP, "dense index build failed: %s", hipGetErrorString(e));
     float f;
     memcpy(&f, &bits, 4);
@@ -1659,28 +1676,16 @@ static bool dense8_is_wide(const DenseHandle* h) { return h->d > I8_MAX_ROW_BYTE
 static bool dense8_wide_wanted(const DenseHandle* h) { return h->opt.dense_int8_wide != 0 && h->d_pad <= MAX_DPAD; }
 // the build kernels for a row width: EPL = row bytes / 64, wide rows in chunks of 512 bytes (EPL = 8)
 template <class... A>
-static void dense8_energy_launch(int row8, dim3 grid, A... a) {
-    switch (row8) {
-        case 128: hipLaunchKernelGGL(dense8_energy_kernel<2>, grid, dim3(256), 0, 0, a...); break;
-        case 256: hipLaunchKernelGGL(dense8_energy_kernel<4>, grid, dim3(256), 0, 0, a...); break;
-        default: hipLaunchKernelGGL(dense8_energy_kernel<8>, grid, dim3(256), 0, 0, a...); break;
-    }
+static int dense8_energy_launch(int row8, dim3 grid, A... a) {
+    return with_row8(row8, [&](auto ks) { return launch<dense8_energy_kernel<decltype(ks)::value / 2>>(grid, dim3(256), 0, nullptr, a...); }, true);
 }
 template <class... A>
-static void dense8_clip_stats_launch(int row8, dim3 grid, A... a) {
-    switch (row8) {
-        case 128: hipLaunchKernelGGL(dense8_clip_stats_kernel<2>, grid, dim3(256), 0, 0, a...); break;
-        case 256: hipLaunchKernelGGL(dense8_clip_stats_kernel<4>, grid, dim3(256), 0, 0, a...); break;
-        default: hipLaunchKernelGGL(dense8_clip_stats_kernel<8>, grid, dim3(256), 0, 0, a...); break;
-    }
+static int dense8_clip_stats_launch(int row8, dim3 grid, A... a) {
+    return with_row8(row8, [&](auto ks) { return launch<dense8_clip_stats_kernel<decltype(ks)::value / 2>>(grid, dim3(256), 0, nullptr, a...); }, true);
 }
 template <class... A>
-static void dense8_build_launch(int row8, dim3 grid, A... a) {
-    switch (row8) {
-        case 128: hipLaunchKernelGGL(dense8_build_kernel<2>, grid, dim3(256), 0, 0, a..., row8); break;
-        case 256: hipLaunchKernelGGL(dense8_build_kernel<4>, grid, dim3(256), 0, 0, a..., row8); break;
-        default: hipLaunchKernelGGL(dense8_build_kernel<8>, grid, dim3(256), 0, 0, a..., row8); break;
-    }
+static int dense8_build_launch(int row8, dim3 grid, A... a) {
+    return with_row8(row8, [&](auto ks) { return launch<dense8_build_kernel<decltype(ks)::value / 2>>(grid, dim3(256), 0, nullptr, a..., row8); }, true);
 }
 // rows a pass over the copy covers: whole ring units of 64 rows, wide rows whole 32-row tiles
 static long long dense8_pass_rows(const DenseHandle* h, long long n) { return dense8_is_wide(h) ? (n + 31) / 32 * 32 : (n + 63) / 64 * 64; }
@@ -1721,7 +1726,7 @@ static int dense8_build(DenseHandle* h) {
     for (int pass = 0; pass < 3; ++pass) {
         double er[2] = {0.0, 0.0};
         SQ_HIP(hipMemset(tmp.p, 0, 64));
-        dense8_energy_launch(row8, dim3(stat_blocks), h->db, n, h->ld, d, centerp, nx64, cap_e, tmp.as<double>());
+        if (const int rc = dense8_energy_launch(row8, dim3(stat_blocks), h->db, n, h->ld, d, centerp, nx64, cap_e, tmp.as<double>())) return quit(rc);
         SQ_HIP(hipMemcpy(er, tmp.p, 16, hipMemcpyDeviceToHost));
         if (!(er[1] >= 0.5 * (double)n)) return quit(SQ_OK);   // (half the rows non-finite or beyond 16 x the mean: not this filter's data)
         rms = sqrt(er[0] / (er[1] * d));
@@ -1751,7 +1756,10 @@ static int dense8_build(DenseHandle* h) {
     // large matrices choose from every 8th row (the kernel evaluates twelve clamps per element: 16 ms of a 40 ms build at
     // 10 M x 128 when it reads every row; the choice needs the shape of the residuals' tail, not every row)
     const int clip_step = n >= 2000000 ? 8 : 1;
-    dense8_clip_stats_launch(row8, dim3(stat_blocks), h->db, n, h->ld, d, centerp, nx64, ca, clipbuf.as<u32>(), clip_step);
+    if (const int rc = dense8_clip_stats_launch(row8, dim3(stat_blocks), h->db, n, h->ld, d, centerp, nx64, ca, clipbuf.as<u32>(), clip_step)) {
+        clipbuf.release();
+        return quit(rc);
+    }
     u32 counts[I8_NCLIP][I8_NCUT];
     SQ_HIP(hipMemcpy(counts, clipbuf.p, clip_bytes, hipMemcpyDeviceToHost));
     clipbuf.release();
@@ -1775,7 +1783,8 @@ static int dense8_build(DenseHandle* h) {
         signed char* o8 = h->scan8.as<signed char>();
         float* nr8 = h->nrow8.as<float>();
         float* r2p = r2row.as<float>();
-        dense8_build_launch(row8, grid, h->db, n, h->ld, d, n_alloc, centerp, nx64, ca.inv_dx[best_c], ca.dx[best_c], o8, nr8, r2p, 0ll);
+        if (const int rc = dense8_build_launch(row8, grid, h->db, n, h->ld, d, n_alloc, centerp, nx64, ca.inv_dx[best_c], ca.dx[best_c], o8, nr8, r2p, 0ll))
+            return quit(rc);
         SQ_HIP(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(nr8 + n_alloc), 0x7f800000, 64));   // (+inf behind the last unit)
         if (spare8) SQ_HIP(hipMemset(o8 + (size_t)n_alloc * row8, 0, spare8));
     }
@@ -1785,9 +1794,11 @@ static int dense8_build(DenseHandle* h) {
     // rows beyond the chosen bound become always-candidates first; R and X are then the largest residual and the largest
     // |x'| of the rows that REMAIN under the bound (a row 100x the rest would otherwise set X for every query)
     double cut = best_r * best_r * (1.0 + 1e-4);   // (the choice was made in float32)
-    hipLaunchKernelGGL(dense8_flag_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, r2row.as<float>(), h->nrow8.as<float>(), n,
-                       (float)cut, flagged, 0ll);
-    hipLaunchKernelGGL(dense8_resid_stats_kernel, dim3(1024), dim3(256), 0, 0, r2row.as<float>(), h->nrow8.as<float>(), n, sum_r2, maxb);
+    if (const int rc = launch<dense8_flag_kernel>(dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, r2row.as<float>(), h->nrow8.as<float>(), n,
+                                                  (float)cut, flagged, 0ll))
+        return quit(rc);
+    if (const int rc = launch<dense8_resid_stats_kernel>(dim3(1024), dim3(256), 0, nullptr, r2row.as<float>(), h->nrow8.as<float>(), n, sum_r2, maxb))
+        return quit(rc);
     struct {
         double energy, sum_r2;
         u32 max_r2, max_n, flagged, pad;
@@ -1828,26 +1839,8 @@ static int dense8_build(DenseHandle* h) {
 static int dense_build_all(DenseHandle* h) {
     const long long n = h->n;
     const int d = h->d, d_pad = h->d_pad, metric = h->metric;
-    // the filter's origin (L2): the column means (float64 sums over row blocks); rows appended later keep it
-    if (metric == SQ_METRIC_L2 && d_pad <= MAX_DPAD && !h->opt.dense_no_center) {
-        SQ_TRY(h->center.reserve((size_t)d_pad * 4));
-        DevBuf colsum;
-        SQ_TRY(colsum.reserve((size_t)d * 8));
-        if (hipMemset(colsum.p, 0, (size_t)d * 8) != hipSuccess) {
-            colsum.release();
-            return fail(SQ_ERR_HIP, "memset failed");
-        }
-        const long long rpb = 512;
-        hipLaunchKernelGGL(dense_colsum_kernel, dim3((unsigned)((n + rpb - 1) / rpb)), dim3(256), 0, 0, h->db,
-                           (long long)n, h->ld, d, rpb, colsum.as<double>());
-        hipLaunchKernelGGL(dense_center_kernel, dim3((d_pad + 255) / 256), dim3(256), 0, 0, colsum.as<double>(),
-                           (long long)n, d, d_pad, h->center.as<float>());
-        if (hipDeviceSynchronize() != hipSuccess) {
-            colsum.release();
-            return fail(SQ_ERR_HIP, "dense index build: column means failed");
-        }
-        colsum.release();
-    }
+    // the filter's origin (L2): the column means
+    if (metric == SQ_METRIC_L2 && d_pad <= MAX_DPAD && !h->opt.dense_no_center) SQ_TRY(dense_column_means(h, h->center, nullptr));
     // row statistics, then the bfloat16 scan copy (skipped for rows wider than the scan kernel covers)
     int rc = h->norms.reserve((size_t)h->n_pad * 4);
     if (rc == SQ_OK && metric == SQ_METRIC_L2) rc = h->norms1.reserve((size_t)h->n_pad * 4);
@@ -1935,7 +1928,7 @@ static int dense8_append(DenseHandle* h, long long n_old) {
         signed char* o8 = h->scan8.as<signed char>();
         float* nr8 = h->nrow8.as<float>();
         float* r2p = r2row.as<float>();
-        dense8_build_launch(row8, grid, h->db, n, h->ld, d, n_alloc, centerp, nx64, h->inv_dxf8, h->dxf8, o8, nr8, r2p, row_base);
+        if (const int rc = dense8_build_launch(row8, grid, h->db, n, h->ld, d, n_alloc, centerp, nx64, h->inv_dxf8, h->dxf8, o8, nr8, r2p, row_base)) return done(rc);
         SQ_HIP(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(nr8 + n_alloc), 0x7f800000, 64));
         if (spare8) SQ_HIP(hipMemset(o8 + (size_t)n_alloc * row8, 0, spare8));
     }
@@ -1944,10 +1937,12 @@ static int dense8_append(DenseHandle* h, long long n_old) {
     u32* maxb = reinterpret_cast<u32*>(tmp.as<double>() + 2);
     u32* flagged = maxb + 2;
     // the largest |x'|^2 of the new rows BEFORE their always-candidates are marked (a flagged row needs no X)
-    hipLaunchKernelGGL(dense8_flag_kernel, dim3((unsigned)((n - row_base + 255) / 256)), dim3(256), 0, 0, r2row.as<float>(), h->nrow8.as<float>(), n,
-                       h->cut8, flagged, row_base);
-    hipLaunchKernelGGL(dense8_resid_stats_kernel, dim3(256), dim3(256), 0, 0, r2row.as<float>() + row_base, h->nrow8.as<float>() + row_base,
-                       n - row_base, sum_r2, maxb);
+    if (const int rc = launch<dense8_flag_kernel>(dim3((unsigned)((n - row_base + 255) / 256)), dim3(256), 0, nullptr, r2row.as<float>(), h->nrow8.as<float>(),
+                                                  n, h->cut8, flagged, row_base))
+        return done(rc);
+    if (const int rc = launch<dense8_resid_stats_kernel>(dim3(256), dim3(256), 0, nullptr, r2row.as<float>() + row_base, h->nrow8.as<float>() + row_base,
+                                                         n - row_base, sum_r2, maxb))
+        return done(rc);
     struct {
         double energy, sum_r2;
         u32 max_r2, max_n, flagged, pad;
@@ -2179,21 +2174,24 @@ extern "C" int sq_dense_remove(sq_handle_t hid, const int64_t* ids, int64_t m) {
         return done(fail(SQ_ERR_HIP, "sq_dense_remove: copy of the ids failed"));
     const dim3 grid((unsigned)((m + 255) / 256)), blk(256);
     // pass 1: validate and mark
-    hipLaunchKernelGGL(dense_remove_kernel, grid, blk, 0, 0, ids_dev.as<long long>(), (long long)m, h->id_base, h->n, h->dead.as<u32>(),
-                       won.as<u32>(), status.as<u32>());
+    if (const int rc = launch<dense_remove_kernel>(grid, blk, 0, nullptr, ids_dev.as<long long>(), (long long)m, h->id_base, h->n, h->dead.as<u32>(),
+                                                   won.as<u32>(), status.as<u32>()))
+        return done(rc);
     u32 st = 0;
     if (hipMemcpy(&st, status.p, 4, hipMemcpyDeviceToHost) != hipSuccess)
         return done(fail(SQ_ERR_HIP, "sq_dense_remove: %s", hipGetErrorString(hipGetLastError())));
     if (st != 0) {
         // pass 2, refused: the bits this call set are cleared again; nothing else was written
-        hipLaunchKernelGGL(dense_remove_undo_kernel, grid, blk, 0, 0, ids_dev.as<long long>(), (long long)m, h->id_base, h->dead.as<u32>(),
-                           won.as<u32>());
+        if (const int rc = launch<dense_remove_undo_kernel>(grid, blk, 0, nullptr, ids_dev.as<long long>(), (long long)m, h->id_base, h->dead.as<u32>(),
+                                                            won.as<u32>()))
+            return done(rc);
         if (hipDeviceSynchronize() != hipSuccess) return done(fail(SQ_ERR_HIP, "sq_dense_remove: undo failed"));
         return done(fail(SQ_ERR_INVALID, "sq_dense_remove: %s%s%s; nothing was removed", (st & DENSE_REMOVE_RANGE) ? "an id is out of range" : "",
                          st == 3u ? ", " : "", (st & DENSE_REMOVE_DEAD) ? "an id is already removed or listed twice" : ""));
     }
     // pass 2: the per-row terms of every copy the handle keeps
-    hipLaunchKernelGGL(dense_remove_apply_kernel, grid, blk, 0, 0, ids_dev.as<long long>(), (long long)m, h->id_base, dense_dead_terms(h));
+    if (const int rc = launch<dense_remove_apply_kernel>(grid, blk, 0, nullptr, ids_dev.as<long long>(), (long long)m, h->id_base, dense_dead_terms(h)))
+        return done(rc);
     if (hipDeviceSynchronize() != hipSuccess) return done(fail(SQ_ERR_HIP, "sq_dense_remove: %s", hipGetErrorString(hipGetLastError())));
     h->n_live -= m;
     return done(SQ_OK);
@@ -2222,8 +2220,9 @@ extern "C" int sq_dense_compact(sq_handle_t hid, int64_t* old_to_new) {
     };
     if (const int rc = prefix.reserve((size_t)words * 8)) return done(rc);
     if (const int rc = total.reserve(8)) return done(rc);
-    hipLaunchKernelGGL(dense_compact_scan_kernel, dim3(1), dim3(1024), 0, 0, h->deadp(), n_old, words, prefix.as<unsigned long long>(),
-                       total.as<unsigned long long>());
+    if (const int rc = launch<dense_compact_scan_kernel>(dim3(1), dim3(1024), 0, nullptr, h->deadp(), n_old, words, prefix.as<unsigned long long>(),
+                                                         total.as<unsigned long long>()))
+        return done(rc);
     unsigned long long live_dev = 0;
     if (hipMemcpy(&live_dev, total.p, 8, hipMemcpyDeviceToHost) != hipSuccess)
         return done(fail(SQ_ERR_HIP, "sq_dense_compact: %s", hipGetErrorString(hipGetLastError())));
@@ -2231,8 +2230,9 @@ extern "C" int sq_dense_compact(sq_handle_t hid, int64_t* old_to_new) {
     if (live != h->n_live) return done(fail(SQ_ERR_INTERNAL, "sq_dense_compact: the bitmap holds %lld live rows, the handle counts %lld", live, h->n_live));
     if (old_to_new) {   // before anything changes: a failure here leaves the index as it was
         if (const int rc = map.reserve((size_t)n_old * 8)) return done(rc);
-        hipLaunchKernelGGL(dense_compact_map_kernel, dim3((unsigned)((n_old + 255) / 256)), dim3(256), 0, 0, h->deadp(),
-                           prefix.as<unsigned long long>(), n_old, h->id_base, map.as<long long>());
+        if (const int rc = launch<dense_compact_map_kernel>(dim3((unsigned)((n_old + 255) / 256)), dim3(256), 0, nullptr, h->deadp(),
+                                                            prefix.as<unsigned long long>(), n_old, h->id_base, map.as<long long>()))
+            return done(rc);
         if (hipMemcpy(old_to_new, map.p, (size_t)n_old * 8, hipMemcpyDeviceToHost) != hipSuccess)
             return done(fail(SQ_ERR_HIP, "sq_dense_compact: %s", hipGetErrorString(hipGetLastError())));
         map.release();
@@ -2245,12 +2245,13 @@ extern "C" int sq_dense_compact(sq_handle_t hid, int64_t* old_to_new) {
     // rows of one gather launch: its grid stays below 2^30 workgroups
     const long long launch_rows = std::max<long long>(32, ((1ll << 30) * 256 / cpr) / 32 * 32);
     auto gather = [&](uint4* dst, long long r0, long long r1, long long dst_row0) {
-        hipLaunchKernelGGL(dense_compact_gather_kernel, dim3((unsigned)(((r1 - r0) * cpr + 255) / 256)), dim3(256), 0, 0, h->owned.as<uint4>(), dst,
-                           cpr, r0, r1, dst_row0, h->deadp(), prefix.as<unsigned long long>());
+        return launch<dense_compact_gather_kernel>(dim3((unsigned)(((r1 - r0) * cpr + 255) / 256)), dim3(256), 0, nullptr, h->owned.as<uint4>(), dst, cpr, r0,
+                                                   r1, dst_row0, h->deadp(), prefix.as<unsigned long long>());
     };
     if (fresh_rows.reserve((size_t)live * row_bytes) == SQ_OK) {
         // a second buffer: one pass, and the matrix shrinks to the rows that are left
-        for (long long r0 = 0; r0 < n_old; r0 += launch_rows) gather(fresh_rows.as<uint4>(), r0, std::min(n_old, r0 + launch_rows), 0);
+        for (long long r0 = 0; r0 < n_old; r0 += launch_rows)
+            if (const int rc = gather(fresh_rows.as<uint4>(), r0, std::min(n_old, r0 + launch_rows), 0)) return done(rc);
         if (hipDeviceSynchronize() != hipSuccess) return done(fail(SQ_ERR_HIP, "sq_dense_compact: gather failed: %s", hipGetErrorString(hipGetLastError())));
         h->owned.release();
         h->owned = fresh_rows;
@@ -2269,7 +2270,7 @@ extern "C" int sq_dense_compact(sq_handle_t hid, int64_t* old_to_new) {
             const long long r1 = std::min(n_old, r0 + piece);
             const long long d0 = (long long)pre[(size_t)(r0 >> 5)], d1 = r1 < n_old ? (long long)pre[(size_t)(r1 >> 5)] : live;
             if (d1 == d0) continue;
-            gather(bounce.as<uint4>(), r0, r1, d0);
+            if (const int rc = gather(bounce.as<uint4>(), r0, r1, d0)) return done(rc);
             if (hipMemcpyAsync(h->owned.as<char>() + (size_t)d0 * row_bytes, bounce.p, (size_t)(d1 - d0) * row_bytes, hipMemcpyDeviceToDevice, 0) != hipSuccess)
                 return done(fail(SQ_ERR_HIP, "sq_dense_compact: copy failed: %s", hipGetErrorString(hipGetLastError())));
         }
@@ -2404,11 +2405,9 @@ extern "C" int sq_dense_destroy(sq_handle_t hid) {
 }
 
 template <class T>
-static void distances_launch(const void* rows, long long n, int d, const void* q, int metric, void* out,
-                             hipStream_t st) {
-    const unsigned gx = (unsigned)((n + 31) / 32);
-    hipLaunchKernelGGL((dense_distances_kernel<T>), dim3(gx), dim3(256), 0, st, (const T*)rows, n, d, (const T*)q,
-                       metric, (T*)out, (double*)out);
+static int distances_launch(const void* rows, long long n, int d, const void* q, int metric, void* out, hipStream_t st) {
+    return launch<dense_distances_kernel<T>>(dim3((unsigned)((n + 31) / 32)), dim3(256), 0, st, (const T*)rows, n, d, (const T*)q, metric, (T*)out,
+                                             (double*)out);
 }
 
 extern "C" int sq_dense_distances(const void* query, const void* rows, int dtype, int64_t n, int d, int metric,
@@ -2420,12 +2419,8 @@ extern "C" int sq_dense_distances(const void* query, const void* rows, int dtype
     const size_t esz = dtype == SQ_DTYPE_F32 ? 4 : 8;
     const size_t osz = (metric == SQ_METRIC_COSINE || dtype == SQ_DTYPE_F64) ? 8 : 4;
     if (mem == SQ_MEM_DEVICE) {
-        if (dtype == SQ_DTYPE_F32)
-            distances_launch<float>(rows, n, d, query, metric, out, st);
-        else
-            distances_launch<double>(rows, n, d, query, metric, out, st);
-        SQ_HIP(hipGetLastError());
-        return SQ_OK;
+        return dtype == SQ_DTYPE_F32 ? distances_launch<float>(rows, n, d, query, metric, out, st)
+                                     : distances_launch<double>(rows, n, d, query, metric, out, st);
     }
     DevBuf dq, dr, dout;
     int rc = SQ_OK;
@@ -2441,10 +2436,9 @@ extern "C" int sq_dense_distances(const void* query, const void* rows, int dtype
     if (hipMemcpyAsync(dq.p, query, (size_t)d * esz, hipMemcpyHostToDevice, st) != hipSuccess ||
         hipMemcpyAsync(dr.p, rows, (size_t)n * d * esz, hipMemcpyHostToDevice, st) != hipSuccess)
         return done(fail(SQ_ERR_HIP, "sq_dense_distances: H2D copy failed"));
-    if (dtype == SQ_DTYPE_F32)
-        distances_launch<float>(dr.p, n, d, dq.p, metric, dout.p, st);
-    else
-        distances_launch<double>(dr.p, n, d, dq.p, metric, dout.p, st);
+    if ((rc = dtype == SQ_DTYPE_F32 ? distances_launch<float>(dr.p, n, d, dq.p, metric, dout.p, st)
+                                    : distances_launch<double>(dr.p, n, d, dq.p, metric, dout.p, st)) != SQ_OK)
+        return done(rc);
     if (hipMemcpyAsync(out, dout.p, (size_t)n * osz, hipMemcpyDeviceToHost, st) != hipSuccess ||
         hipStreamSynchronize(st) != hipSuccess)
         return done(fail(SQ_ERR_HIP, "sq_dense_distances: kernel or D2H copy failed: %s",

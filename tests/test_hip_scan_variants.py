@@ -157,9 +157,10 @@ def _plant(rng, n, d, nq, nwaves):
     return db, qs
 
 
-def _check_every_query(db, qs, dist, ids, k, metric):
+def _check_every_query(db, qs, dist, ids, k, metric, refs=None):
+    """`refs`: the oracle's (distances, ids) per query where several cases share them."""
     for qi, q in enumerate(qs):
-        rd, ri = O.dense_topk(db, q, k, metric)
+        rd, ri = refs[qi] if refs is not None else O.dense_topk(db, q, k, metric)
         kk = len(rd)
         if metric == "euclidean":
             assert dist.dtype == np.float32
@@ -192,5 +193,49 @@ def test_scan_variant_against_oracle(name, c, metric):
         assert st["fallback_queries"] == 0, st     # the answer checked is the scan's, not the exact path's
         assert st["scan_launches"] >= 1, st
         _check_every_query(db, qs, dist, ids, K, metric)
+    finally:
+        idx.close()
+
+
+# ---- option "dense_rerank_segments": survivor segments per re-rank workgroup of the chains' shared tail
+# (bf16 chain: any divisor of the scan workgroup's waves, 8 segments run on the kernel's 512-thread limit; int8 six-launch
+# chain: L2 only, four at the most -- its cosine cases run the same launch three times and are kept as the fixed point:
+# the option must not change a cosine answer).  n as _shape builds it (c row tiles per wave + a partial last tile).
+TAIL_GROUPS = {
+    # name: (options, scan waves, n, d, nq, segments)
+    "bf16-8w": (dict(dense_int8=0, dense_blocks=8, candidate_cap=2048, dense_qt=1), 8, (9 * 64 + 33) * 32 - 7, 100, 33, (1, 2, 4, 8)),
+    "bf16-4w": (dict(dense_int8=0, dense_blocks=8, candidate_cap=2048), 4, (18 * 32 + 17) * 32 - 7, 128, 130, (1, 2, 4)),
+    "int8-six": (dict(dense_int8=1, dense_fused=0), 8, 65536 + 17, 100, 17, (1, 2, 4)),
+}
+_tail_data = {}
+
+
+def _tail_case(group, metric):
+    """(db, qs, oracle answers) of a group, computed once for all its segment counts."""
+    if (group, metric) not in _tail_data:
+        _, waves, n, d, nq, _ = TAIL_GROUPS[group]
+        rng = np.random.default_rng(zlib.crc32(("tail %s %s" % (group, metric)).encode()))
+        db, qs = _plant(rng, n, d, nq, 8 * waves)
+        _tail_data[(group, metric)] = (db, qs, [O.dense_topk(db, q, K, metric) for q in qs])
+    return _tail_data[(group, metric)]
+
+
+@pytest.mark.parametrize("metric", ["euclidean", "cosine"])
+@pytest.mark.parametrize("group,segments", [(g, s) for g, v in TAIL_GROUPS.items() for s in v[5]])
+def test_rerank_segments_against_oracle(group, segments, metric):
+    db, qs, refs = _tail_case(group, metric)
+    opts = dict(TAIL_GROUPS[group][0], dense_rerank_segments=segments)
+    m = _lib.SQ_METRIC_L2 if metric == "euclidean" else _lib.SQ_METRIC_COSINE
+    idx = _lib.DenseIndex(db, metric=m, options=opts)
+    try:
+        if opts.get("dense_int8") == 1:
+            assert idx.info()["int8_in_use"], "no int8 copy: the six-launch int8 chain is not reached"
+        dist, ids = idx.search(qs, K)
+        st = idx.stats()
+        print(group, segments, metric, st)
+        # the answers checked are the chain's own: sample pass + full pass, every query certified by the tail's select
+        # (a later tier would add a pass per group of queries and count them here)
+        assert st["scan_launches"] == 2 and st["fallback_queries"] == 0 and st["mid_tier_queries"] == 0, st
+        _check_every_query(db, qs, dist, ids, K, metric, refs)
     finally:
         idx.close()
