@@ -9,6 +9,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <unordered_map>
@@ -16,37 +17,12 @@
 #include <vector>
 
 #include "../../include/smqtk_hip.h"
+#include "sq_buffers.hpp"   // errors (fail, SQ_HIP, SQ_TRY) and the owning buffers (DevBuf, HostPinned, PinnedStage, grow_keep)
 
 typedef unsigned long long u64;
 typedef unsigned int u32;
 
 namespace sq {
-
-// ------------------------------------------------------------------ errors
-extern thread_local char g_err[512];
-inline int fail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-#define SQ_HIP(expr)                                                                  \
-    do {                                                                              \
-        hipError_t e_ = (expr);                                                       \
-        if (e_ != hipSuccess)                                                         \
-            return sq::fail(e_ == hipErrorOutOfMemory ? SQ_ERR_NOMEM : SQ_ERR_HIP,    \
-                            "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_),   \
-                            __FILE__, __LINE__);                                      \
-    } while (0)
-
-// (variadic: an expression such as launch<kernel<A, B>>(...) has commas of its own)
-#define SQ_TRY(...)                   \
-    do {                              \
-        int rc_ = (__VA_ARGS__);      \
-        if (rc_ != SQ_OK) return rc_; \
-    } while (0)
 
 // ----------------------------------------------------------------- options
 struct Options {
@@ -118,116 +94,6 @@ inline hipError_t stream_wait(hipStream_t st) {
 inline hipError_t event_wait(hipEvent_t ev) {
     return poll_then_block([ev] { return hipEventQuery(ev); }, [ev] { return hipEventSynchronize(ev); });
 }
-
-// ------------------------------------------------------- device buffer (RAII)
-struct DevBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    int reserve(size_t bytes) {
-        if (bytes <= cap) return SQ_OK;
-        if (p) {
-            (void)hipFree(p);
-            p = nullptr;
-            cap = 0;
-        }
-        size_t want = bytes + (bytes >> 3) + 256;
-        hipError_t e = hipMalloc(&p, want);
-        if (e != hipSuccess) {
-            p = nullptr;
-            return fail(SQ_ERR_NOMEM, "hipMalloc(%zu) failed: %s", want, hipGetErrorString(e));
-        }
-        cap = want;
-        return SQ_OK;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-    template <class T>
-    T* as() const { return reinterpret_cast<T*>(p); }
-};
-
-struct HostPinned {
-    void* p = nullptr;
-    size_t cap = 0;
-    void* dev = nullptr;   // the block's device address (looked up once per allocation: device_ptr)
-    int reserve(size_t bytes) {
-        if (bytes <= cap) return SQ_OK;
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        dev = nullptr;
-        cap = 0;
-        hipError_t e = hipHostMalloc(&p, bytes + 256, hipHostMallocDefault);
-        if (e != hipSuccess) {
-            p = nullptr;
-            return fail(SQ_ERR_NOMEM, "hipHostMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
-        }
-        cap = bytes + 256;
-        return SQ_OK;
-    }
-    // device address of the block (a runtime call of a few microseconds: cached per allocation)
-    int device_ptr(void** out) {
-        if (!dev) {
-            hipError_t e = hipHostGetDevicePointer(&dev, p, 0);
-            if (e != hipSuccess) {
-                dev = nullptr;
-                return fail(SQ_ERR_HIP, "hipHostGetDevicePointer failed: %s", hipGetErrorString(e));
-            }
-        }
-        *out = dev;
-        return SQ_OK;
-    }
-    void release() {
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        dev = nullptr;
-        cap = 0;
-    }
-};
-
-// Small host buffers travel through pinned staging: an "asynchronous" copy from or to pageable memory is a
-// blocking staged copy inside the runtime (~10-15 us each; a one-query search makes three to five of them).
-// in(): memcpy into the pinned block, asynchronous H2D from there.  out(): asynchronous D2H into the block;
-// finish() -- after the stream has drained -- copies the pieces to the caller's buffers.  Calls above
-// kStageMax bytes in total copy directly.
-struct PinnedStage {
-    static constexpr size_t kStageMax = 1u << 20;
-    HostPinned pin;
-    size_t used = 0;
-    bool on = false;
-    struct Out {
-        void* dst;
-        size_t off, bytes;
-    };
-    Out outs[4];
-    int n_out = 0;
-    int begin(size_t total_bytes) {
-        used = 0;
-        n_out = 0;
-        on = total_bytes <= kStageMax;
-        return on ? pin.reserve(total_bytes + 64 * 8) : SQ_OK;
-    }
-    hipError_t in(void* dev, const void* host, size_t bytes, hipStream_t st) {
-        if (!on) return hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, st);
-        char* at = static_cast<char*>(pin.p) + used;
-        memcpy(at, host, bytes);
-        used += (bytes + 63) / 64 * 64;
-        return hipMemcpyAsync(dev, at, bytes, hipMemcpyHostToDevice, st);
-    }
-    hipError_t out(void* host, const void* dev, size_t bytes, hipStream_t st) {
-        if (!on || n_out >= 4) return hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, st);
-        outs[n_out++] = Out{host, used, bytes};
-        char* at = static_cast<char*>(pin.p) + used;
-        used += (bytes + 63) / 64 * 64;
-        return hipMemcpyAsync(at, dev, bytes, hipMemcpyDeviceToHost, st);
-    }
-    void finish() {  // the stream has been waited for
-        for (int i = 0; i < n_out; ++i) memcpy(outs[i].dst, static_cast<char*>(pin.p) + outs[i].off, outs[i].bytes);
-        n_out = 0;
-    }
-    void release() { pin.release(); }
-};
 
 // ------------------------------------------------------------------ handles
 enum HandleKind { H_HAMMING = 1, H_DENSE = 2, H_ROWS = 3, H_FIT = 4, H_ITQ = 5 };

@@ -77,18 +77,13 @@ struct DenseSlot {
     hipEvent_t ev_in = nullptr, ev_done = nullptr;
     hipStream_t own = nullptr;    // internal stream of the slot (asynchronous calls with "dense_async_streams" = 2)
     DenseCall call;
-    void release() {
-        for (DevBuf* b : {&q_scaled, &q_al, &qn2, &thr, &wave_out, &wave_cnt, &cnt, &keys, &sample, &out_keys, &cos_nq, &oflag, &sort_tmp, &q8, &par8, &wave_score, &hist8, &clk8, &tg})
-            b->release();
-        status_host.release();
-        call_ptrs.release();
-        if (gexec) (void)hipGraphExecDestroy(gexec), gexec = nullptr;
-        gkey = seen_key = 0;
+    ~DenseSlot() {   // (the buffers free themselves, after this body)
+        if (gexec) (void)hipGraphExecDestroy(gexec);
         for (auto& e : ev)
-            if (e) (void)hipEventDestroy(e), e = nullptr;
-        if (ev_in) (void)hipEventDestroy(ev_in), ev_in = nullptr;
-        if (ev_done) (void)hipEventDestroy(ev_done), ev_done = nullptr;
-        if (own) (void)hipStreamDestroy(own), own = nullptr;
+            if (e) (void)hipEventDestroy(e);
+        if (ev_in) (void)hipEventDestroy(ev_in);
+        if (ev_done) (void)hipEventDestroy(ev_done);
+        if (own) (void)hipStreamDestroy(own);
     }
 };
 
@@ -150,12 +145,6 @@ struct DenseHandle : HandleBase {
     hipEvent_t ev_ref = nullptr;   // SQ_TRACE (measurement aid): the origin of the printed call timelines
     ~DenseHandle() override {
         if (ev_ref) (void)hipEventDestroy(ev_ref);
-        for (DevBuf* b : {&dead, &owned, &scan, &scan8, &nrow8, &norms, &norms1, &zeros, &center, &cos_nx, &q_dev, &out_dist_dev, &out_idx_dev, &big_keys,
-                          &fb_sample, &fb_keys, &fb_out, &scratch, &fb_cnt, &fb_sort, &mid_q, &mid_planes, &mid_small, &mid_qal,
-                          &mid_wave_out, &mid_wave_cnt, &mid_keys, &mid_out, &mid_sample, &mid_cos_center, &mid_cos_rows})
-            b->release();
-        for (auto& sl : slot) sl.release();
-        stage.release();
     }
 };
 
@@ -1295,7 +1284,6 @@ static int dense_column_means(const DenseHandle* h, DevBuf& out, hipStream_t st)
     if (rc == SQ_OK) rc = launch<dense_colsum_kernel>(dim3((unsigned)((n + rpb - 1) / rpb)), dim3(256), 0, st, h->db, n, h->ld, d, rpb, colsum.as<double>());
     if (rc == SQ_OK) rc = launch<dense_center_kernel>(dim3((d_pad + 255) / 256), dim3(256), 0, st, colsum.as<double>(), n, d, d_pad, out.as<float>());
     if (rc == SQ_OK && stream_wait(st) != hipSuccess) rc = fail(SQ_ERR_HIP, "column means failed: %s", hipGetErrorString(hipGetLastError()));
-    colsum.release();
     return rc;
 }
 // the cosine tier's origin and per-row terms (sq_dense_mid.hpp), once per index and again after an append
@@ -1638,7 +1626,6 @@ static int dense_build_rows(DenseHandle* h, long long row_base, int parts = ROWS
     u32 bits = 0;
     hipError_t e = hipMemcpy(&bits, h->scratch.p, 4, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    inv.release();
     if (rc != SQ_OK) return rc;
     if (e != hipSuccess) return fail(SQ_ERR_HIP, "dense index build failed: %s", hipGetErrorString(e));
     float f;
@@ -1707,32 +1694,32 @@ static int dense8_build(DenseHandle* h) {
     const float* centerp = (!cosine && h->center.p) ? h->center.as<float>() : nullptr;
     DevBuf tmp;   // [sum f64 x2 | max bits u32 x2 | flagged u32]
     DevBuf r2row;
-    auto quit = [&](int rc) {
-        tmp.release();
-        r2row.release();
-        if (!h->use8) {
-            h->scan8.release();
-            h->nrow8.release();
+    struct DropUnused {   // on every way out from here: a handle that does not use the copy keeps no memory for one
+        DenseHandle* h;
+        ~DropUnused() {
+            if (!h->use8) {
+                h->scan8.release();
+                h->nrow8.release();
+            }
         }
-        return rc;
-    };
+    } drop_unused{h};
     if (tmp.reserve(64) != SQ_OK || r2row.reserve((size_t)n_alloc * 4) != SQ_OK || h->scan8.reserve((size_t)n_alloc * row8 + spare8) != SQ_OK ||
         h->nrow8.reserve((size_t)(n_alloc + 64) * 4) != SQ_OK) {   // (+ 64: a 32-row unit's DMA fetches 64 row terms)
         (void)hipGetLastError();
-        return quit(SQ_OK);
+        return SQ_OK;
     }
     const int stat_blocks = cu_count(h->device) * 8;
     double rms = 0.0, cap_e = (double)__builtin_inff();
     for (int pass = 0; pass < 3; ++pass) {
         double er[2] = {0.0, 0.0};
         SQ_HIP(hipMemset(tmp.p, 0, 64));
-        if (const int rc = dense8_energy_launch(row8, dim3(stat_blocks), h->db, n, h->ld, d, centerp, nx64, cap_e, tmp.as<double>())) return quit(rc);
+        if (const int rc = dense8_energy_launch(row8, dim3(stat_blocks), h->db, n, h->ld, d, centerp, nx64, cap_e, tmp.as<double>())) return rc;
         SQ_HIP(hipMemcpy(er, tmp.p, 16, hipMemcpyDeviceToHost));
-        if (!(er[1] >= 0.5 * (double)n)) return quit(SQ_OK);   // (half the rows non-finite or beyond 16 x the mean: not this filter's data)
+        if (!(er[1] >= 0.5 * (double)n)) return SQ_OK;   // (half the rows non-finite or beyond 16 x the mean: not this filter's data)
         rms = sqrt(er[0] / (er[1] * d));
         cap_e = 16.0 * er[0] / er[1];
     }
-    if (!(rms > 0.0) || !(rms < 1e30)) return quit(SQ_OK);
+    if (!(rms > 0.0) || !(rms < 1e30)) return SQ_OK;
     SQ_HIP(hipMemset(tmp.p, 0, 64));
     // the clamp and R from the measured residuals of twelve candidate clamps (dense8_clip_stats_kernel)
     // (1.75 rms: where a uniform distribution ends; 9-11 rms: one-sided data -- max(N(0,1), 0) reaches 8.4 rms of its centred
@@ -1751,18 +1738,15 @@ static int dense8_build(DenseHandle* h) {
     }
     DevBuf clipbuf;   // counts u32 [NCLIP][NCUT]
     const size_t clip_bytes = I8_NCLIP * I8_NCUT * 4;
-    if (clipbuf.reserve(clip_bytes) != SQ_OK) return quit(SQ_OK);
+    if (clipbuf.reserve(clip_bytes) != SQ_OK) return SQ_OK;
     SQ_HIP(hipMemset(clipbuf.p, 0, clip_bytes));
     // large matrices choose from every 8th row (the kernel evaluates twelve clamps per element: 16 ms of a 40 ms build at
     // 10 M x 128 when it reads every row; the choice needs the shape of the residuals' tail, not every row)
     const int clip_step = n >= 2000000 ? 8 : 1;
-    if (const int rc = dense8_clip_stats_launch(row8, dim3(stat_blocks), h->db, n, h->ld, d, centerp, nx64, ca, clipbuf.as<u32>(), clip_step)) {
-        clipbuf.release();
-        return quit(rc);
-    }
+    if (const int rc = dense8_clip_stats_launch(row8, dim3(stat_blocks), h->db, n, h->ld, d, centerp, nx64, ca, clipbuf.as<u32>(), clip_step)) return rc;
     u32 counts[I8_NCLIP][I8_NCUT];
     SQ_HIP(hipMemcpy(counts, clipbuf.p, clip_bytes, hipMemcpyDeviceToHost));
-    clipbuf.release();
+    clipbuf.release();   // (not at scope exit: the copy is built next)
     for (auto& row : counts)
         for (u32& v : row) v = (u32)std::min<unsigned long long>(0xffffffffull, (unsigned long long)v * (unsigned)clip_step);
     // rows beyond R are candidates of every query: a few hundred at most (a query has a few thousand candidates anyway)
@@ -1776,7 +1760,7 @@ static int dense8_build(DenseHandle* h) {
                 if (best_c < 0 || r < best_r) best_c = c, best_m = m, best_r = r;
                 break;
             }
-    if (best_c < 0) return quit(SQ_OK);   // every clamp leaves too many rows beyond every bound (heavy tails): the bf16 filter's relative bound suits such data
+    if (best_c < 0) return SQ_OK;   // every clamp leaves too many rows beyond every bound (heavy tails): the bf16 filter's relative bound suits such data
     const double dx = (double)ca.dx[best_c];
     {
         const dim3 grid((unsigned)((n_alloc + 3) / 4));
@@ -1784,7 +1768,7 @@ static int dense8_build(DenseHandle* h) {
         float* nr8 = h->nrow8.as<float>();
         float* r2p = r2row.as<float>();
         if (const int rc = dense8_build_launch(row8, grid, h->db, n, h->ld, d, n_alloc, centerp, nx64, ca.inv_dx[best_c], ca.dx[best_c], o8, nr8, r2p, 0ll))
-            return quit(rc);
+            return rc;
         SQ_HIP(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(nr8 + n_alloc), 0x7f800000, 64));   // (+inf behind the last unit)
         if (spare8) SQ_HIP(hipMemset(o8 + (size_t)n_alloc * row8, 0, spare8));
     }
@@ -1796,9 +1780,9 @@ static int dense8_build(DenseHandle* h) {
     double cut = best_r * best_r * (1.0 + 1e-4);   // (the choice was made in float32)
     if (const int rc = launch<dense8_flag_kernel>(dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, r2row.as<float>(), h->nrow8.as<float>(), n,
                                                   (float)cut, flagged, 0ll))
-        return quit(rc);
+        return rc;
     if (const int rc = launch<dense8_resid_stats_kernel>(dim3(1024), dim3(256), 0, nullptr, r2row.as<float>(), h->nrow8.as<float>(), n, sum_r2, maxb))
-        return quit(rc);
+        return rc;
     struct {
         double energy, sum_r2;
         u32 max_r2, max_n, flagged, pad;
@@ -1810,7 +1794,7 @@ static int dense8_build(DenseHandle* h) {
     memcpy(&max_n, &host.max_n, 4);
     const u32 nflag = host.flagged;
     if ((double)max_r2 < cut) cut = (double)max_r2 * (1.0 + 1e-6);   // nothing near the bound: R is simply the largest
-    if ((double)nflag > 4.0 * budget) return quit(SQ_OK);
+    if ((double)nflag > 4.0 * budget) return SQ_OK;
     h->dx8 = dx;
     h->rmax8 = sqrt(cut) * (1.0 + 1e-6);
     h->xmax8 = cosine ? 1.0 + 1e-6 : sqrt((double)max_n) * (1.0 + 1e-6);   // (cosine: unit rows; their row term is 0)
@@ -1831,7 +1815,7 @@ static int dense8_build(DenseHandle* h) {
     h->n8_built = n;
     h->overflow8 = 0;
     h->use8 = true;
-    return quit(SQ_OK);
+    return SQ_OK;
 }
 
 // Everything an index derives from its float32 rows, built from scratch: the L2 filter's origin, the row statistics, the
@@ -1861,22 +1845,6 @@ static int dense_build_all(DenseHandle* h) {
     return SQ_OK;
 }
 
-// Room for `n_new` rows in every per-row buffer, contents kept (grown by half again at least, so a stream of
-// small appends copies the matrix O(log) times).
-static int grow_keep(DevBuf& b, size_t used, size_t need) {
-    if (need <= b.cap) return SQ_OK;
-    DevBuf nb;
-    SQ_TRY(nb.reserve(std::max(need, used + used / 2)));
-    if (used && b.p) {
-        if (hipMemcpy(nb.p, b.p, used, hipMemcpyDeviceToDevice) != hipSuccess) {
-            nb.release();
-            return fail(SQ_ERR_HIP, "device copy failed while growing an index buffer");
-        }
-    }
-    b.release();
-    b = nb;
-    return SQ_OK;
-}
 // The int8 copy after an append (h->n is the new row count; the rows are in place).  The step and the residual cut of
 // the build stay: new rows are quantised with them, rows they do not suit become always-candidates like the build's own.
 // An index that has doubled since the clamp was chosen -- or that collected too many always-candidates -- chooses again
@@ -1899,36 +1867,30 @@ static int dense8_append(DenseHandle* h, long long n_old) {
     const int row8 = h->row8, d = h->d;
     const long long n_pad64 = dense8_pass_rows(h, n), n_alloc = (n + 127) / 128 * 128;
     const size_t spare8 = dense8_is_wide(h) ? I8W_SPARE : 0;
-    auto drop = [&]() {
-        h->use8 = false;
-        h->scan8.release();
-        h->nrow8.release();
-        return SQ_OK;
-    };
-    if (grow_keep(h->scan8, (size_t)h->n_alloc8 * row8, (size_t)n_alloc * row8 + spare8) != SQ_OK ||
-        grow_keep(h->nrow8, (size_t)(h->n_alloc8 + 64) * 4, (size_t)(n_alloc + 64) * 4) != SQ_OK) {
-        (void)hipGetLastError();
-        return drop();
-    }
+    struct DropUnfinished {   // on every way out but the end: a copy that lacks the new rows is not kept (nor used)
+        DenseHandle* h;
+        bool finished = false;
+        ~DropUnfinished() {
+            if (finished) return;
+            h->use8 = false;
+            h->scan8.release();
+            h->nrow8.release();
+        }
+    } drop{h};
     DevBuf tmp, r2row;
-    if (tmp.reserve(64) != SQ_OK || r2row.reserve((size_t)n_alloc * 4) != SQ_OK) {
-        tmp.release();
-        r2row.release();
+    if (grow_keep(h->scan8, (size_t)h->n_alloc8 * row8, (size_t)n_alloc * row8 + spare8) != SQ_OK ||
+        grow_keep(h->nrow8, (size_t)(h->n_alloc8 + 64) * 4, (size_t)(n_alloc + 64) * 4) != SQ_OK || tmp.reserve(64) != SQ_OK ||
+        r2row.reserve((size_t)n_alloc * 4) != SQ_OK) {
         (void)hipGetLastError();
-        return drop();
+        return SQ_OK;   // (no memory for the copy is not an error: the index goes on without one)
     }
-    auto done = [&](int rc) {
-        tmp.release();
-        r2row.release();
-        return rc;
-    };
     const long long row_base = n_old / 128 * 128;   // the unit the old rows ended in is redone with the new ones
     {
         const dim3 grid((unsigned)((n_alloc - row_base + 3) / 4));
         signed char* o8 = h->scan8.as<signed char>();
         float* nr8 = h->nrow8.as<float>();
         float* r2p = r2row.as<float>();
-        if (const int rc = dense8_build_launch(row8, grid, h->db, n, h->ld, d, n_alloc, centerp, nx64, h->inv_dxf8, h->dxf8, o8, nr8, r2p, row_base)) return done(rc);
+        if (const int rc = dense8_build_launch(row8, grid, h->db, n, h->ld, d, n_alloc, centerp, nx64, h->inv_dxf8, h->dxf8, o8, nr8, r2p, row_base)) return rc;
         SQ_HIP(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(nr8 + n_alloc), 0x7f800000, 64));
         if (spare8) SQ_HIP(hipMemset(o8 + (size_t)n_alloc * row8, 0, spare8));
     }
@@ -1939,10 +1901,10 @@ static int dense8_append(DenseHandle* h, long long n_old) {
     // the largest |x'|^2 of the new rows BEFORE their always-candidates are marked (a flagged row needs no X)
     if (const int rc = launch<dense8_flag_kernel>(dim3((unsigned)((n - row_base + 255) / 256)), dim3(256), 0, nullptr, r2row.as<float>(), h->nrow8.as<float>(),
                                                   n, h->cut8, flagged, row_base))
-        return done(rc);
+        return rc;
     if (const int rc = launch<dense8_resid_stats_kernel>(dim3(256), dim3(256), 0, nullptr, r2row.as<float>() + row_base, h->nrow8.as<float>() + row_base,
                                                          n - row_base, sum_r2, maxb))
-        return done(rc);
+        return rc;
     struct {
         double energy, sum_r2;
         u32 max_r2, max_n, flagged, pad;
@@ -1956,11 +1918,14 @@ static int dense8_append(DenseHandle* h, long long n_old) {
     h->flagged8 += host.flagged;
     h->n_pad64 = n_pad64;
     h->n_alloc8 = n_alloc;
+    drop.finished = true;
     const double budget = std::max(256.0, 2e-5 * (double)n);
-    if ((double)h->flagged8 > 4.0 * budget) return done(dense8_build(h));   // the new rows do not look like the old ones: choose again
-    return done(SQ_OK);
+    if ((double)h->flagged8 > 4.0 * budget) return dense8_build(h);   // the new rows do not look like the old ones: choose again
+    return SQ_OK;
 }
 
+// Room for `n_new` rows in every per-row buffer, contents kept (grow_keep: a stream of small appends copies the matrix
+// O(log) times).
 static int dense_grow(DenseHandle* h, long long n_new) {
     const long long n_pad_new = (n_new + TILE_ROWS - 1) / TILE_ROWS * TILE_ROWS;
     const bool cosine = h->metric == SQ_METRIC_COSINE;
@@ -2032,7 +1997,7 @@ static int dense_create_impl(const float* db, int64_t n, int d, int metric, int 
         return fail(SQ_ERR_UNSUPPORTED,
                     "sq_dense_create: a borrowed device matrix must be 16-byte aligned with d %% 4 == 0 (d=%d)", d);
     const int d_pad = (d + KT - 1) / KT * KT;
-    auto* h = new DenseHandle();
+    auto h = std::make_unique<DenseHandle>();
     h->kind = H_DENSE;
     h->n = n;
     h->n_live = n;
@@ -2043,14 +2008,7 @@ static int dense_create_impl(const float* db, int64_t n, int d, int metric, int 
     h->id_base = id_base;
     h->overrides = overrides;   // (create-time choices -- "dense_int8" = 0: no int8 copy -- are the handle's own)
     h->refresh_options();
-    if (hipGetDevice(&h->device) != hipSuccess) {
-        delete h;
-        return fail(SQ_ERR_HIP, "sq_dense_create: no HIP device");
-    }
-    auto bail = [&](int rc) {
-        delete h;
-        return rc;
-    };
+    if (hipGetDevice(&h->device) != hipSuccess) return fail(SQ_ERR_HIP, "sq_dense_create: no HIP device");
     if (mem == SQ_MEM_DEVICE) {
         h->db = db;
         h->ld = d;
@@ -2058,8 +2016,7 @@ static int dense_create_impl(const float* db, int64_t n, int d, int metric, int 
         // owned float32 copy, rows padded to a multiple of 4 floats so the exact kernel can use 16-byte loads
         const int ldo = (d + 3) / 4 * 4;
         const size_t bytes = (size_t)n * ldo * 4;
-        int rc = h->owned.reserve(bytes);
-        if (rc != SQ_OK) return bail(rc);
+        SQ_TRY(h->owned.reserve(bytes));
         hipError_t e;
         if (ldo == d) {
             e = hipMemcpy(h->owned.p, db, bytes, hipMemcpyHostToDevice);
@@ -2069,16 +2026,13 @@ static int dense_create_impl(const float* db, int64_t n, int d, int metric, int 
                 e = hipMemcpy2D(h->owned.p, (size_t)ldo * 4, db, (size_t)d * 4, (size_t)d * 4, (size_t)n,
                                 hipMemcpyHostToDevice);
         }
-        if (e != hipSuccess) return bail(fail(SQ_ERR_HIP, "sq_dense_create: H2D copy failed: %s", hipGetErrorString(e)));
+        if (e != hipSuccess) return fail(SQ_ERR_HIP, "sq_dense_create: H2D copy failed: %s", hipGetErrorString(e));
         h->db = h->owned.as<float>();
         h->ld = ldo;
     }
-    {
-        const int rc = dense_build_all(h);
-        if (rc != SQ_OK) return bail(rc);
-    }
+    SQ_TRY(dense_build_all(h.get()));
     h->build_us = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t_create).count();
-    *out = register_handle(h);
+    *out = register_handle(h.release());
     return SQ_OK;
 }
 
@@ -2136,6 +2090,45 @@ extern "C" int sq_dense_count(sq_handle_t hid, int64_t* n_rows, int64_t* n_live)
     return SQ_OK;
 }
 
+// sq_dense_remove under the handle's lock, the calls in flight finished; `fresh`: the handle has no bitmap yet
+static int dense_remove_rows(DenseHandle* h, const int64_t* ids, int64_t m, bool fresh) {
+    DevBuf ids_dev, won, status;
+    if (fresh) {
+        const long long words = (h->n + 31) / 32;
+        if (const int rc = h->dead.reserve((size_t)words * 4)) return rc;
+        if (hipMemset(h->dead.p, 0, h->dead.cap) != hipSuccess) return fail(SQ_ERR_HIP, "sq_dense_remove: memset failed");
+        h->dead_words = words;
+    }
+    if (const int rc = ids_dev.reserve((size_t)m * 8)) return rc;
+    if (const int rc = won.reserve((size_t)m * 4)) return rc;
+    if (const int rc = status.reserve(4)) return rc;
+    if (hipMemcpy(ids_dev.p, ids, (size_t)m * 8, hipMemcpyHostToDevice) != hipSuccess || hipMemset(status.p, 0, 4) != hipSuccess)
+        return fail(SQ_ERR_HIP, "sq_dense_remove: copy of the ids failed");
+    const dim3 grid((unsigned)((m + 255) / 256)), blk(256);
+    // pass 1: validate and mark
+    if (const int rc = launch<dense_remove_kernel>(grid, blk, 0, nullptr, ids_dev.as<long long>(), (long long)m, h->id_base, h->n, h->dead.as<u32>(),
+                                                   won.as<u32>(), status.as<u32>()))
+        return rc;
+    u32 st = 0;
+    if (hipMemcpy(&st, status.p, 4, hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(SQ_ERR_HIP, "sq_dense_remove: %s", hipGetErrorString(hipGetLastError()));
+    if (st != 0) {
+        // pass 2, refused: the bits this call set are cleared again; nothing else was written
+        if (const int rc = launch<dense_remove_undo_kernel>(grid, blk, 0, nullptr, ids_dev.as<long long>(), (long long)m, h->id_base, h->dead.as<u32>(),
+                                                            won.as<u32>()))
+            return rc;
+        if (hipDeviceSynchronize() != hipSuccess) return fail(SQ_ERR_HIP, "sq_dense_remove: undo failed");
+        return fail(SQ_ERR_INVALID, "sq_dense_remove: %s%s%s; nothing was removed", (st & DENSE_REMOVE_RANGE) ? "an id is out of range" : "",
+                    st == 3u ? ", " : "", (st & DENSE_REMOVE_DEAD) ? "an id is already removed or listed twice" : "");
+    }
+    // pass 2: the per-row terms of every copy the handle keeps
+    if (const int rc = launch<dense_remove_apply_kernel>(grid, blk, 0, nullptr, ids_dev.as<long long>(), (long long)m, h->id_base, dense_dead_terms(h)))
+        return rc;
+    if (hipDeviceSynchronize() != hipSuccess) return fail(SQ_ERR_HIP, "sq_dense_remove: %s", hipGetErrorString(hipGetLastError()));
+    h->n_live -= m;
+    return SQ_OK;
+}
+
 extern "C" int sq_dense_remove(sq_handle_t hid, const int64_t* ids, int64_t m) {
     auto* h = static_cast<DenseHandle*>(lookup_handle(hid, H_DENSE));
     if (!h) return fail(SQ_ERR_INVALID, "sq_dense_remove: unknown handle");
@@ -2150,51 +2143,12 @@ extern "C" int sq_dense_remove(sq_handle_t hid, const int64_t* ids, int64_t m) {
         return fail(SQ_ERR_INVALID, "sq_dense_remove: %lld ids for %lld live rows (an index keeps at least one row: destroy it instead)",
                     (long long)m, h->n_live);
     const bool fresh = h->dead.p == nullptr;
-    DevBuf ids_dev, won, status;
-    auto done = [&](int rc) {
-        ids_dev.release();
-        won.release();
-        status.release();
-        if (rc != SQ_OK && fresh) {   // a refused first removal leaves no bitmap behind
-            h->dead.release();
-            h->dead_words = 0;
-        }
-        return rc;
-    };
-    if (fresh) {
-        const long long words = (h->n + 31) / 32;
-        if (const int rc = h->dead.reserve((size_t)words * 4)) return done(rc);
-        if (hipMemset(h->dead.p, 0, h->dead.cap) != hipSuccess) return done(fail(SQ_ERR_HIP, "sq_dense_remove: memset failed"));
-        h->dead_words = words;
+    const int rc = dense_remove_rows(h, ids, m, fresh);
+    if (rc != SQ_OK && fresh) {   // a refused first removal leaves no bitmap behind
+        h->dead.release();
+        h->dead_words = 0;
     }
-    if (const int rc = ids_dev.reserve((size_t)m * 8)) return done(rc);
-    if (const int rc = won.reserve((size_t)m * 4)) return done(rc);
-    if (const int rc = status.reserve(4)) return done(rc);
-    if (hipMemcpy(ids_dev.p, ids, (size_t)m * 8, hipMemcpyHostToDevice) != hipSuccess || hipMemset(status.p, 0, 4) != hipSuccess)
-        return done(fail(SQ_ERR_HIP, "sq_dense_remove: copy of the ids failed"));
-    const dim3 grid((unsigned)((m + 255) / 256)), blk(256);
-    // pass 1: validate and mark
-    if (const int rc = launch<dense_remove_kernel>(grid, blk, 0, nullptr, ids_dev.as<long long>(), (long long)m, h->id_base, h->n, h->dead.as<u32>(),
-                                                   won.as<u32>(), status.as<u32>()))
-        return done(rc);
-    u32 st = 0;
-    if (hipMemcpy(&st, status.p, 4, hipMemcpyDeviceToHost) != hipSuccess)
-        return done(fail(SQ_ERR_HIP, "sq_dense_remove: %s", hipGetErrorString(hipGetLastError())));
-    if (st != 0) {
-        // pass 2, refused: the bits this call set are cleared again; nothing else was written
-        if (const int rc = launch<dense_remove_undo_kernel>(grid, blk, 0, nullptr, ids_dev.as<long long>(), (long long)m, h->id_base, h->dead.as<u32>(),
-                                                            won.as<u32>()))
-            return done(rc);
-        if (hipDeviceSynchronize() != hipSuccess) return done(fail(SQ_ERR_HIP, "sq_dense_remove: undo failed"));
-        return done(fail(SQ_ERR_INVALID, "sq_dense_remove: %s%s%s; nothing was removed", (st & DENSE_REMOVE_RANGE) ? "an id is out of range" : "",
-                         st == 3u ? ", " : "", (st & DENSE_REMOVE_DEAD) ? "an id is already removed or listed twice" : ""));
-    }
-    // pass 2: the per-row terms of every copy the handle keeps
-    if (const int rc = launch<dense_remove_apply_kernel>(grid, blk, 0, nullptr, ids_dev.as<long long>(), (long long)m, h->id_base, dense_dead_terms(h)))
-        return done(rc);
-    if (hipDeviceSynchronize() != hipSuccess) return done(fail(SQ_ERR_HIP, "sq_dense_remove: %s", hipGetErrorString(hipGetLastError())));
-    h->n_live -= m;
-    return done(SQ_OK);
+    return rc;
 }
 
 extern "C" int sq_dense_compact(sq_handle_t hid, int64_t* old_to_new) {
@@ -2214,28 +2168,24 @@ extern "C" int sq_dense_compact(sq_handle_t hid, int64_t* old_to_new) {
     const long long cpr = h->ld / 4;   // (the owned matrix: rows of whole 16-byte chunks)
     const long long words = (n_old + 31) / 32;
     DevBuf prefix, total, map, fresh_rows, bounce;
-    auto done = [&](int rc) {
-        for (DevBuf* b : {&prefix, &total, &map, &fresh_rows, &bounce}) b->release();
-        return rc;
-    };
-    if (const int rc = prefix.reserve((size_t)words * 8)) return done(rc);
-    if (const int rc = total.reserve(8)) return done(rc);
+    if (const int rc = prefix.reserve((size_t)words * 8)) return rc;
+    if (const int rc = total.reserve(8)) return rc;
     if (const int rc = launch<dense_compact_scan_kernel>(dim3(1), dim3(1024), 0, nullptr, h->deadp(), n_old, words, prefix.as<unsigned long long>(),
                                                          total.as<unsigned long long>()))
-        return done(rc);
+        return rc;
     unsigned long long live_dev = 0;
     if (hipMemcpy(&live_dev, total.p, 8, hipMemcpyDeviceToHost) != hipSuccess)
-        return done(fail(SQ_ERR_HIP, "sq_dense_compact: %s", hipGetErrorString(hipGetLastError())));
+        return fail(SQ_ERR_HIP, "sq_dense_compact: %s", hipGetErrorString(hipGetLastError()));
     const long long live = (long long)live_dev;
-    if (live != h->n_live) return done(fail(SQ_ERR_INTERNAL, "sq_dense_compact: the bitmap holds %lld live rows, the handle counts %lld", live, h->n_live));
+    if (live != h->n_live) return fail(SQ_ERR_INTERNAL, "sq_dense_compact: the bitmap holds %lld live rows, the handle counts %lld", live, h->n_live);
     if (old_to_new) {   // before anything changes: a failure here leaves the index as it was
-        if (const int rc = map.reserve((size_t)n_old * 8)) return done(rc);
+        if (const int rc = map.reserve((size_t)n_old * 8)) return rc;
         if (const int rc = launch<dense_compact_map_kernel>(dim3((unsigned)((n_old + 255) / 256)), dim3(256), 0, nullptr, h->deadp(),
                                                             prefix.as<unsigned long long>(), n_old, h->id_base, map.as<long long>()))
-            return done(rc);
+            return rc;
         if (hipMemcpy(old_to_new, map.p, (size_t)n_old * 8, hipMemcpyDeviceToHost) != hipSuccess)
-            return done(fail(SQ_ERR_HIP, "sq_dense_compact: %s", hipGetErrorString(hipGetLastError())));
-        map.release();
+            return fail(SQ_ERR_HIP, "sq_dense_compact: %s", hipGetErrorString(hipGetLastError()));
+        map.release();   // (now: the gather below wants the room)
     }
     // every copy derived from the rows is rebuilt below: their memory goes first, so that the gather finds room
     for (DevBuf* b : {&h->scan, &h->scan8, &h->nrow8, &h->norms, &h->norms1, &h->cos_nx, &h->center, &h->mid_cos_center, &h->mid_cos_rows})
@@ -2251,30 +2201,28 @@ extern "C" int sq_dense_compact(sq_handle_t hid, int64_t* old_to_new) {
     if (fresh_rows.reserve((size_t)live * row_bytes) == SQ_OK) {
         // a second buffer: one pass, and the matrix shrinks to the rows that are left
         for (long long r0 = 0; r0 < n_old; r0 += launch_rows)
-            if (const int rc = gather(fresh_rows.as<uint4>(), r0, std::min(n_old, r0 + launch_rows), 0)) return done(rc);
-        if (hipDeviceSynchronize() != hipSuccess) return done(fail(SQ_ERR_HIP, "sq_dense_compact: gather failed: %s", hipGetErrorString(hipGetLastError())));
-        h->owned.release();
-        h->owned = fresh_rows;
-        fresh_rows = DevBuf{};
+            if (const int rc = gather(fresh_rows.as<uint4>(), r0, std::min(n_old, r0 + launch_rows), 0)) return rc;
+        if (hipDeviceSynchronize() != hipSuccess) return fail(SQ_ERR_HIP, "sq_dense_compact: gather failed: %s", hipGetErrorString(hipGetLastError()));
+        h->owned = std::move(fresh_rows);
     } else {
         // No room for a second matrix: in place, front to back, a piece of rows at a time through a bounce buffer.  Piece j
         // lands at rows [new(r0), new(r1)) with new(r1) <= r1: below every row a later piece has yet to read, and the piece
         // itself has been read into the bounce buffer completely (stream order) before it is written.
         (void)hipGetLastError();
         long long piece = std::min<long long>(launch_rows, std::max<long long>(32, (long long)(((size_t)64 << 20) / row_bytes) / 32 * 32));
-        if (const int rc = bounce.reserve((size_t)piece * row_bytes)) return done(fail(rc, "sq_dense_compact: no memory for the gather; the index must be built again"));
+        if (const int rc = bounce.reserve((size_t)piece * row_bytes)) return fail(rc, "sq_dense_compact: no memory for the gather; the index must be built again");
         std::vector<unsigned long long> pre((size_t)words);
         if (hipMemcpy(pre.data(), prefix.p, (size_t)words * 8, hipMemcpyDeviceToHost) != hipSuccess)
-            return done(fail(SQ_ERR_HIP, "sq_dense_compact: %s", hipGetErrorString(hipGetLastError())));
+            return fail(SQ_ERR_HIP, "sq_dense_compact: %s", hipGetErrorString(hipGetLastError()));
         for (long long r0 = 0; r0 < n_old; r0 += piece) {
             const long long r1 = std::min(n_old, r0 + piece);
             const long long d0 = (long long)pre[(size_t)(r0 >> 5)], d1 = r1 < n_old ? (long long)pre[(size_t)(r1 >> 5)] : live;
             if (d1 == d0) continue;
-            if (const int rc = gather(bounce.as<uint4>(), r0, r1, d0)) return done(rc);
+            if (const int rc = gather(bounce.as<uint4>(), r0, r1, d0)) return rc;
             if (hipMemcpyAsync(h->owned.as<char>() + (size_t)d0 * row_bytes, bounce.p, (size_t)(d1 - d0) * row_bytes, hipMemcpyDeviceToDevice, 0) != hipSuccess)
-                return done(fail(SQ_ERR_HIP, "sq_dense_compact: copy failed: %s", hipGetErrorString(hipGetLastError())));
+                return fail(SQ_ERR_HIP, "sq_dense_compact: copy failed: %s", hipGetErrorString(hipGetLastError()));
         }
-        if (hipDeviceSynchronize() != hipSuccess) return done(fail(SQ_ERR_HIP, "sq_dense_compact: gather failed: %s", hipGetErrorString(hipGetLastError())));
+        if (hipDeviceSynchronize() != hipSuccess) return fail(SQ_ERR_HIP, "sq_dense_compact: gather failed: %s", hipGetErrorString(hipGetLastError()));
     }
     h->db = h->owned.as<float>();
     h->n = h->n_live = live;
@@ -2292,7 +2240,7 @@ extern "C" int sq_dense_compact(sq_handle_t hid, int64_t* old_to_new) {
         if (sl.gexec) (void)hipGraphExecDestroy(sl.gexec), sl.gexec = nullptr;
         sl.gkey = sl.seen_key = 0;
     }
-    return done(dense_build_all(h));
+    return dense_build_all(h);
 }
 
 extern "C" int sq_dense_search(sq_handle_t hid, const float* queries, int nq, int k, void* out_dist, int64_t* out_idx,
@@ -2423,25 +2371,16 @@ extern "C" int sq_dense_distances(const void* query, const void* rows, int dtype
                                      : distances_launch<double>(rows, n, d, query, metric, out, st);
     }
     DevBuf dq, dr, dout;
-    int rc = SQ_OK;
-    auto done = [&](int code) {
-        dq.release();
-        dr.release();
-        dout.release();
-        return code;
-    };
-    if ((rc = dq.reserve((size_t)d * esz)) != SQ_OK) return done(rc);
-    if ((rc = dr.reserve((size_t)n * d * esz)) != SQ_OK) return done(rc);
-    if ((rc = dout.reserve((size_t)n * osz)) != SQ_OK) return done(rc);
+    SQ_TRY(dq.reserve((size_t)d * esz));
+    SQ_TRY(dr.reserve((size_t)n * d * esz));
+    SQ_TRY(dout.reserve((size_t)n * osz));
     if (hipMemcpyAsync(dq.p, query, (size_t)d * esz, hipMemcpyHostToDevice, st) != hipSuccess ||
         hipMemcpyAsync(dr.p, rows, (size_t)n * d * esz, hipMemcpyHostToDevice, st) != hipSuccess)
-        return done(fail(SQ_ERR_HIP, "sq_dense_distances: H2D copy failed"));
-    if ((rc = dtype == SQ_DTYPE_F32 ? distances_launch<float>(dr.p, n, d, dq.p, metric, dout.p, st)
-                                    : distances_launch<double>(dr.p, n, d, dq.p, metric, dout.p, st)) != SQ_OK)
-        return done(rc);
+        return fail(SQ_ERR_HIP, "sq_dense_distances: H2D copy failed");
+    SQ_TRY(dtype == SQ_DTYPE_F32 ? distances_launch<float>(dr.p, n, d, dq.p, metric, dout.p, st)
+                                 : distances_launch<double>(dr.p, n, d, dq.p, metric, dout.p, st));
     if (hipMemcpyAsync(out, dout.p, (size_t)n * osz, hipMemcpyDeviceToHost, st) != hipSuccess ||
         hipStreamSynchronize(st) != hipSuccess)
-        return done(fail(SQ_ERR_HIP, "sq_dense_distances: kernel or D2H copy failed: %s",
-                         hipGetErrorString(hipGetLastError())));
-    return done(SQ_OK);
+        return fail(SQ_ERR_HIP, "sq_dense_distances: kernel or D2H copy failed: %s", hipGetErrorString(hipGetLastError()));
+    return SQ_OK;
 }

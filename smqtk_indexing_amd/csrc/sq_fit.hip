@@ -39,9 +39,6 @@ struct FitHandle : HandleBase {
     DevBuf small;   // pc / r on the device
     DevBuf codes;   // sign bits of v . r of the current iteration
     DevBuf zero;    // a zero mean for the hash kernel
-    ~FitHandle() override {
-        for (DevBuf* b : {&owned, &nrm, &mean, &acc, &v, &small, &codes, &zero}) b->release();
-    }
 };
 
 // element (row, k) of norm(x) as float64
@@ -253,53 +250,45 @@ extern "C" int sq_itqfit_create(const void* x, int dtype, int64_t n, int d, int 
     if (norm_ord != SQ_NORM_NONE && norm_ord != SQ_NORM_L2)
         return fail(SQ_ERR_UNSUPPORTED, "sq_itqfit_create: normalize=%d not supported on the device (None or 2)", norm_ord);
     if (d > FIT_MAX_D) return fail(SQ_ERR_UNSUPPORTED, "sq_itqfit_create: d=%d above %d", d, FIT_MAX_D);
-    auto* h = new FitHandle();
+    auto h = std::make_unique<FitHandle>();
     h->kind = H_FIT;
     h->dtype = dtype;
     h->n = n;
     h->d = d;
     h->norm = norm_ord;
-    auto bail = [&](int rc) {
-        delete h;
-        return rc;
-    };
-    if (hipGetDevice(&h->device) != hipSuccess) return bail(fail(SQ_ERR_HIP, "sq_itqfit_create: no HIP device"));
+    if (hipGetDevice(&h->device) != hipSuccess) return fail(SQ_ERR_HIP, "sq_itqfit_create: no HIP device");
     const size_t esz = dtype == SQ_DTYPE_F32 ? 4 : 8;
     if (mem == SQ_MEM_DEVICE) {
         h->x = x;
     } else {
-        int rc = h->owned.reserve((size_t)n * d * esz);
-        if (rc != SQ_OK) return bail(rc);
+        SQ_TRY(h->owned.reserve((size_t)n * d * esz));
         if (hipMemcpy(h->owned.p, x, (size_t)n * d * esz, hipMemcpyHostToDevice) != hipSuccess)
-            return bail(fail(SQ_ERR_HIP, "sq_itqfit_create: H2D copy failed"));
+            return fail(SQ_ERR_HIP, "sq_itqfit_create: H2D copy failed");
         h->x = h->owned.p;
     }
-    int rc;
-    if ((rc = h->mean.reserve((size_t)d * 8)) != SQ_OK) return bail(rc);
-    if ((rc = h->acc.reserve(std::max((size_t)d * d, (size_t)FIT_MAX_BITS * FIT_MAX_BITS) * 8)) != SQ_OK) return bail(rc);
+    SQ_TRY(h->mean.reserve((size_t)d * 8));
+    SQ_TRY(h->acc.reserve(std::max((size_t)d * d, (size_t)FIT_MAX_BITS * FIT_MAX_BITS) * 8));
     if (norm_ord == SQ_NORM_L2) {
-        if ((rc = h->nrm.reserve((size_t)n * 8)) != SQ_OK) return bail(rc);
+        SQ_TRY(h->nrm.reserve((size_t)n * 8));
         const unsigned g = (unsigned)((n + 31) / 32);
-        rc = dtype == SQ_DTYPE_F32
-                 ? launch<fit_rownorm_kernel<float>>(dim3(g), dim3(256), 0, nullptr, (const float*)h->x, (long long)n, d, h->nrm.as<double>())
-                 : launch<fit_rownorm_kernel<double>>(dim3(g), dim3(256), 0, nullptr, (const double*)h->x, (long long)n, d, h->nrm.as<double>());
-        if (rc != SQ_OK) return bail(rc);
+        SQ_TRY(dtype == SQ_DTYPE_F32
+                   ? launch<fit_rownorm_kernel<float>>(dim3(g), dim3(256), 0, nullptr, (const float*)h->x, (long long)n, d, h->nrm.as<double>())
+                   : launch<fit_rownorm_kernel<double>>(dim3(g), dim3(256), 0, nullptr, (const double*)h->x, (long long)n, d, h->nrm.as<double>()));
     }
-    if (hipMemset(h->acc.p, 0, (size_t)d * 8) != hipSuccess) return bail(fail(SQ_ERR_HIP, "memset failed"));
+    if (hipMemset(h->acc.p, 0, (size_t)d * 8) != hipSuccess) return fail(SQ_ERR_HIP, "memset failed");
     const long long rpb = 1024;
     const unsigned g = (unsigned)((n + rpb - 1) / rpb);
     const double* nrm = norm_ord == SQ_NORM_L2 ? h->nrm.as<double>() : nullptr;
-    rc = dtype == SQ_DTYPE_F32
-             ? launch<fit_colsum_kernel<float>>(dim3(g), dim3(256), 0, nullptr, (const float*)h->x, (long long)n, d, rpb, nrm, h->acc.as<double>())
-             : launch<fit_colsum_kernel<double>>(dim3(g), dim3(256), 0, nullptr, (const double*)h->x, (long long)n, d, rpb, nrm, h->acc.as<double>());
-    if (rc != SQ_OK) return bail(rc);
+    SQ_TRY(dtype == SQ_DTYPE_F32
+               ? launch<fit_colsum_kernel<float>>(dim3(g), dim3(256), 0, nullptr, (const float*)h->x, (long long)n, d, rpb, nrm, h->acc.as<double>())
+               : launch<fit_colsum_kernel<double>>(dim3(g), dim3(256), 0, nullptr, (const double*)h->x, (long long)n, d, rpb, nrm, h->acc.as<double>()));
     std::vector<double> sums((size_t)d);
     if (hipMemcpy(sums.data(), h->acc.p, (size_t)d * 8, hipMemcpyDeviceToHost) != hipSuccess)
-        return bail(fail(SQ_ERR_HIP, "sq_itqfit_create: column means failed: %s", hipGetErrorString(hipGetLastError())));
+        return fail(SQ_ERR_HIP, "sq_itqfit_create: column means failed: %s", hipGetErrorString(hipGetLastError()));
     for (int k = 0; k < d; ++k) out_mean[k] = sums[(size_t)k] / (double)n;
     if (hipMemcpy(h->mean.p, out_mean, (size_t)d * 8, hipMemcpyHostToDevice) != hipSuccess)
-        return bail(fail(SQ_ERR_HIP, "sq_itqfit_create: H2D copy failed"));
-    *out = register_handle(h);
+        return fail(SQ_ERR_HIP, "sq_itqfit_create: H2D copy failed");
+    *out = register_handle(h.release());
     return SQ_OK;
 }
 
@@ -369,28 +358,24 @@ extern "C" int sq_itqfit_iterate(sq_handle_t hid, const double* r, double* out_c
     const int b = h->bits, words = (b + 63) / 64;
     DevBuf& codes = h->codes;
     DevBuf& zero = h->zero;
-    auto done = [&](int rc) { return rc; };
-    int rc;
-    if ((rc = codes.reserve((size_t)h->n * words * 8)) != SQ_OK) return done(rc);
-    if ((rc = zero.reserve((size_t)b * 8)) != SQ_OK) return done(rc);
+    SQ_TRY(codes.reserve((size_t)h->n * words * 8));
+    SQ_TRY(zero.reserve((size_t)b * 8));
     if (hipMemset(zero.p, 0, (size_t)b * 8) != hipSuccess || hipMemset(h->acc.p, 0, (size_t)b * b * 8) != hipSuccess ||
         hipMemcpy(h->small.p, r, (size_t)b * b * 8, hipMemcpyHostToDevice) != hipSuccess)
-        return done(fail(SQ_ERR_HIP, "sq_itqfit_iterate: staging failed"));
-    rc = sq_itq_hash(h->v.p, SQ_DTYPE_F64, h->n, b, zero.as<double>(), SQ_DTYPE_F64, h->small.as<double>(), b, SQ_NORM_NONE,
-                     reinterpret_cast<uint64_t*>(codes.p), SQ_MEM_DEVICE, nullptr);
-    if (rc != SQ_OK) return done(rc);
+        return fail(SQ_ERR_HIP, "sq_itqfit_iterate: staging failed");
+    SQ_TRY(sq_itq_hash(h->v.p, SQ_DTYPE_F64, h->n, b, zero.as<double>(), SQ_DTYPE_F64, h->small.as<double>(), b, SQ_NORM_NONE,
+                       reinterpret_cast<uint64_t*>(codes.p), SQ_MEM_DEVICE, nullptr));
     const long long rpb = 2048;
     const unsigned grid = (unsigned)((h->n + rpb - 1) / rpb);
     const size_t lds = (size_t)2 * 16 * FIT_GT * 8;
     const unsigned tiles = (unsigned)((b + FIT_GT - 1) / FIT_GT);
-    rc = b <= 64 ? launch<fit_gram_kernel<double, 1, 4, 4>>(dim3(grid, tiles, tiles), dim3(256), lds, nullptr, nullptr, nullptr, nullptr,
-                                                            h->v.as<double>(), codes.as<u64>(), words, h->n, b, b, rpb, h->acc.as<double>())
-                 : launch<fit_gram_kernel<double, 1, 8, 8>>(dim3(grid, tiles, tiles), dim3(256), lds, nullptr, nullptr, nullptr, nullptr,
-                                                            h->v.as<double>(), codes.as<u64>(), words, h->n, b, b, rpb, h->acc.as<double>());
-    if (rc != SQ_OK) return done(rc);
+    SQ_TRY(b <= 64 ? launch<fit_gram_kernel<double, 1, 4, 4>>(dim3(grid, tiles, tiles), dim3(256), lds, nullptr, nullptr, nullptr, nullptr,
+                                                              h->v.as<double>(), codes.as<u64>(), words, h->n, b, b, rpb, h->acc.as<double>())
+                   : launch<fit_gram_kernel<double, 1, 8, 8>>(dim3(grid, tiles, tiles), dim3(256), lds, nullptr, nullptr, nullptr, nullptr,
+                                                              h->v.as<double>(), codes.as<u64>(), words, h->n, b, b, rpb, h->acc.as<double>()));
     if (hipMemcpy(out_c, h->acc.p, (size_t)b * b * 8, hipMemcpyDeviceToHost) != hipSuccess)
-        return done(fail(SQ_ERR_HIP, "sq_itqfit_iterate: failed: %s", hipGetErrorString(hipGetLastError())));
-    return done(SQ_OK);
+        return fail(SQ_ERR_HIP, "sq_itqfit_iterate: failed: %s", hipGetErrorString(hipGetLastError()));
+    return SQ_OK;
 }
 
 extern "C" int sq_itqfit_destroy(sq_handle_t hid) {

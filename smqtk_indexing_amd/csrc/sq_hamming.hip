@@ -67,15 +67,12 @@ struct HammingSlot {
     hipEvent_t ev_in = nullptr, ev_done = nullptr;
     hipStream_t own = nullptr;
     HammingCall call;
-    void release() {
-        for (DevBuf* b : {&keys, &cnt, &hist, &thr, &out_keys, &status, &seg, &bcnt, &sort_tmp, &fhist}) b->release();
-        fhist_zeroed = nullptr;
-        status_host.release();
+    ~HammingSlot() {   // (the buffers free themselves, after this body)
         for (auto& e : ev)
-            if (e) (void)hipEventDestroy(e), e = nullptr;
-        if (ev_in) (void)hipEventDestroy(ev_in), ev_in = nullptr;
-        if (ev_done) (void)hipEventDestroy(ev_done), ev_done = nullptr;
-        if (own) (void)hipStreamDestroy(own), own = nullptr;
+            if (e) (void)hipEventDestroy(e);
+        if (ev_in) (void)hipEventDestroy(ev_in);
+        if (ev_done) (void)hipEventDestroy(ev_done);
+        if (own) (void)hipStreamDestroy(own);
     }
 };
 
@@ -96,11 +93,6 @@ struct HammingHandle : HandleBase {
     // shared by all calls: host-memory staging and the exact path (both synchronous)
     DevBuf q_dev, out_dist_dev, out_idx_dev, big_keys, fb_sort;
     PinnedStage stage;
-    ~HammingHandle() override {
-        for (DevBuf* b : {&owned, &rank, &mut_tmp, &q_dev, &out_dist_dev, &out_idx_dev, &big_keys, &fb_sort}) b->release();
-        for (auto& sl : slot) sl.release();
-        stage.release();
-    }
 };
 
 // ------------------------------------------------------------------ per-width shapes of the register kernels
@@ -1237,27 +1229,13 @@ static __global__ void hamming_rank_remove_kernel(u32* __restrict__ rank, long l
     rank[p] = (u32)(r - lower_bound_ll(rr, m, r));  // ranks below r that left
 }
 
-// room for `bytes` in b with its first `used` bytes kept (grown by half again at least)
-static int hamming_grow_keep(DevBuf& b, size_t used, size_t need) {
-    if (need <= b.cap) return SQ_OK;
-    DevBuf nb;
-    SQ_TRY(nb.reserve(std::max(need, used + used / 2)));
-    if (used && b.p && hipMemcpy(nb.p, b.p, used, hipMemcpyDeviceToDevice) != hipSuccess) {
-        nb.release();
-        return fail(SQ_ERR_HIP, "device copy failed while growing the code array");
-    }
-    b.release();
-    b = nb;
-    return SQ_OK;
-}
-
 static int hamming_materialise_rank(HammingHandle* h, long long rows_needed) {
     if (!h->rank.p) {
         SQ_TRY(h->rank.reserve((size_t)std::max(rows_needed, h->n) * 4));
         SQ_TRY(launch<hamming_rank_init_kernel>(dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, nullptr, h->rank.as<u32>(), h->n, h->pmul));
         SQ_HIP(hipDeviceSynchronize());
     } else {
-        SQ_TRY(hamming_grow_keep(h->rank, (size_t)h->n * 4, (size_t)rows_needed * 4));
+        SQ_TRY(grow_keep(h->rank, (size_t)h->n * 4, (size_t)rows_needed * 4));
     }
     h->pmul.rank = h->rank.as<u32>();
     return SQ_OK;
@@ -1272,15 +1250,12 @@ extern "C" int sq_hamming_create(const uint64_t* codes, int64_t n, int words, in
     if (!codes || !out || n <= 0 || words <= 0) return fail(SQ_ERR_INVALID, "sq_hamming_create: bad argument");
     if (n >= (1ll << 32)) return fail(SQ_ERR_UNSUPPORTED, "sq_hamming_create: more than 2^32-1 codes per shard");
     if (words > 64) return fail(SQ_ERR_UNSUPPORTED, "sq_hamming_create: codes wider than 4096 bits");
-    auto* h = new HammingHandle();
+    auto h = std::make_unique<HammingHandle>();
     h->kind = H_HAMMING;
     h->n = n;
     h->words = words;
     h->id_base = id_base;
-    if (hipGetDevice(&h->device) != hipSuccess) {
-        delete h;
-        return fail(SQ_ERR_HIP, "sq_hamming_create: no HIP device");
-    }
+    if (hipGetDevice(&h->device) != hipSuccess) return fail(SQ_ERR_HIP, "sq_hamming_create: no HIP device");
     {
         // stride ~ n / golden ratio, coprime to n (permutation of Z_n); tiny arrays stay in caller order
         u64 mul = 1;
@@ -1300,35 +1275,26 @@ extern "C" int sq_hamming_create(const uint64_t* codes, int64_t n, int words, in
         const size_t bytes = (size_t)n * words * 8;
         const u64* src = reinterpret_cast<const u64*>(codes);
         DevBuf staged;
-        auto bail = [&](int rc) {
-            staged.release();
-            delete h;
-            return rc;
-        };
         if (mem != SQ_MEM_DEVICE) {
             // host codes: straight into the owned buffer when no permutation is needed, else through a staging copy
             DevBuf& first = mul == 1 ? h->owned : staged;
-            int rc = first.reserve(bytes);
-            if (rc != SQ_OK) return bail(rc);
+            SQ_TRY(first.reserve(bytes));
             hipError_t e = hipMemcpy(first.p, codes, bytes, hipMemcpyHostToDevice);
-            if (e != hipSuccess) return bail(fail(SQ_ERR_HIP, "sq_hamming_create: H2D copy failed: %s", hipGetErrorString(e)));
+            if (e != hipSuccess) return fail(SQ_ERR_HIP, "sq_hamming_create: H2D copy failed: %s", hipGetErrorString(e));
             src = first.as<u64>();
         }
         if (mul == 1) {
             h->codes = src;  // caller order: the borrowed device array or the owned upload
         } else {
-            int rc = h->owned.reserve(bytes);
-            if (rc != SQ_OK) return bail(rc);
-            rc = launch<hamming_permute_kernel>(dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, src, (long long)n, words, mul,
-                                                h->owned.as<u64>());
-            if (rc != SQ_OK) return bail(rc);
+            SQ_TRY(h->owned.reserve(bytes));
+            SQ_TRY(launch<hamming_permute_kernel>(dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, src, (long long)n, words, mul,
+                                                  h->owned.as<u64>()));
             hipError_t e = hipDeviceSynchronize();
-            if (e != hipSuccess) return bail(fail(SQ_ERR_HIP, "sq_hamming_create: permutation failed: %s", hipGetErrorString(e)));
+            if (e != hipSuccess) return fail(SQ_ERR_HIP, "sq_hamming_create: permutation failed: %s", hipGetErrorString(e));
             h->codes = h->owned.as<u64>();
         }
-        staged.release();
     }
-    *out = register_handle(h);
+    *out = register_handle(h.release());
     return SQ_OK;
 }
 
@@ -1431,7 +1397,7 @@ extern "C" int sq_hamming_append(sq_handle_t hid, const uint64_t* new_codes, int
             return fail(SQ_ERR_INVALID, "sq_hamming_append: insert positions must be ascending and within [0, n]");
     SQ_HIP(hipSetDevice(h->device));
     const int W = h->words;
-    SQ_TRY(hamming_grow_keep(h->owned, (size_t)n_old * W * 8, (size_t)n_new * W * 8));
+    SQ_TRY(grow_keep(h->owned, (size_t)n_old * W * 8, (size_t)n_new * W * 8));
     h->codes = h->owned.as<u64>();
     SQ_TRY(hamming_materialise_rank(h, n_new));
     SQ_TRY(h->mut_tmp.reserve((size_t)m * 8));

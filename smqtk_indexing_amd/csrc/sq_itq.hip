@@ -348,7 +348,7 @@ static int itq_fast_path(const ItqArgs& a, const ItqFastGeom& g, hipStream_t st,
 // Measurement (option dense_debug bit 16): phase stamps of every workgroup of the wide kernel, cleared before the
 // launch, read back (a blocking copy) and printed after it.
 static int itq_stamps_reserve(int debug, int nrb, hipStream_t st, u64** stamps) {
-    static DevBuf buf;
+    static DevBuf& buf = *new DevBuf;   // never destroyed: a static's destructor would call hipFree after the runtime has gone
     *stamps = nullptr;
     if (!(debug & 16)) return SQ_OK;
     SQ_TRY(buf.reserve((size_t)nrb * 64 * 8));
@@ -542,11 +542,6 @@ struct ItqModelHandle : HandleBase {
     HostPinned stage;   // [rows | codes] of one small batch
     HostPinned cand_host;
     int d = 0, bits = 0, norm = SQ_NORM_NONE, mean_dtype = SQ_DTYPE_F64;
-    ~ItqModelHandle() override {
-        for (DevBuf* b : {&mean, &rot, &x_dev, &out_dev, &xprep, &cand}) b->release();
-        stage.release();
-        cand_host.release();
-    }
 };
 
 }  // namespace sq
@@ -605,26 +600,21 @@ extern "C" int sq_itq_model_create(const double* mean, int mean_dtype, const dou
         return fail(SQ_ERR_INVALID, "sq_itq_model_create: unknown mean dtype %d", mean_dtype);
     if (!itq_norm_supported(norm_ord))
         return fail(SQ_ERR_UNSUPPORTED, "sq_itq_model_create: normalize code %d not supported on the device", norm_ord);
-    auto* h = new ItqModelHandle();
+    auto h = std::make_unique<ItqModelHandle>();
     h->kind = H_ITQ;
     h->d = d;
     h->bits = bits;
     h->norm = norm_ord;
     h->mean_dtype = mean_dtype;
-    auto bail = [&](int rc) {
-        delete h;
-        return rc;
-    };
-    if (hipGetDevice(&h->device) != hipSuccess) return bail(fail(SQ_ERR_HIP, "sq_itq_model_create: no HIP device"));
-    int rc = h->mean.reserve((size_t)d * 8);
-    if (rc == SQ_OK) rc = h->rot.reserve((size_t)d * bits * 8);
-    if (rc == SQ_OK) rc = h->cand.reserve(8);
-    if (rc == SQ_OK) rc = h->cand_host.reserve(8);
-    if (rc != SQ_OK) return bail(rc);
+    if (hipGetDevice(&h->device) != hipSuccess) return fail(SQ_ERR_HIP, "sq_itq_model_create: no HIP device");
+    SQ_TRY(h->mean.reserve((size_t)d * 8));
+    SQ_TRY(h->rot.reserve((size_t)d * bits * 8));
+    SQ_TRY(h->cand.reserve(8));
+    SQ_TRY(h->cand_host.reserve(8));
     if (hipMemcpy(h->mean.p, mean, (size_t)d * 8, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(h->rot.p, rotation, (size_t)d * bits * 8, hipMemcpyHostToDevice) != hipSuccess)
-        return bail(fail(SQ_ERR_HIP, "sq_itq_model_create: H2D copy failed"));
-    *out = register_handle(h);
+        return fail(SQ_ERR_HIP, "sq_itq_model_create: H2D copy failed");
+    *out = register_handle(h.release());
     return SQ_OK;
 }
 

@@ -30,13 +30,6 @@ struct RowsHandle : HandleBase {
     DevBuf csr_off_owned, csr_rows_owned, codes_dev, ham_dist, ham_idx, pre_dev, out_rows;
     HostPinned totals_host;               // [total candidates, largest list]
     PinnedStage stage;
-    ~RowsHandle() override {
-        stage.release();
-        totals_host.release();
-        for (DevBuf* b : {&owned, &q_dev, &cand_dev, &off_dev, &cnt_dev, &keys, &out_keys, &out_dist, &out_pos, &sort_tmp,
-                          &csr_off_owned, &csr_rows_owned, &codes_dev, &ham_dist, &ham_idx, &pre_dev, &out_rows})
-            b->release();
-    }
 };
 
 // Candidate p of query q (row cand[off[q] + p]) -> key (ordered distance, p).  Eight lanes per
@@ -233,31 +226,21 @@ using namespace sq;
 extern "C" int sq_rows_create(const void* rows, int dtype, int64_t n, int d, int mem, sq_handle_t* out) {
     if (!rows || !out || n <= 0 || d <= 0) return fail(SQ_ERR_INVALID, "sq_rows_create: bad argument");
     if (dtype != SQ_DTYPE_F32 && dtype != SQ_DTYPE_F64) return fail(SQ_ERR_INVALID, "sq_rows_create: unknown dtype %d", dtype);
-    auto* h = new RowsHandle();
+    auto h = std::make_unique<RowsHandle>();
     h->kind = H_ROWS;
     h->dtype = dtype;
     h->n = n;
     h->d = d;
-    if (hipGetDevice(&h->device) != hipSuccess) {
-        delete h;
-        return fail(SQ_ERR_HIP, "sq_rows_create: no HIP device");
-    }
+    if (hipGetDevice(&h->device) != hipSuccess) return fail(SQ_ERR_HIP, "sq_rows_create: no HIP device");
     if (mem == SQ_MEM_DEVICE) {
         h->rows = rows;
     } else {
         const size_t bytes = (size_t)n * d * (dtype == SQ_DTYPE_F32 ? 4 : 8);
-        int rc = h->owned.reserve(bytes);
-        if (rc != SQ_OK) {
-            delete h;
-            return rc;
-        }
-        if (hipMemcpy(h->owned.p, rows, bytes, hipMemcpyHostToDevice) != hipSuccess) {
-            delete h;
-            return fail(SQ_ERR_HIP, "sq_rows_create: H2D copy failed");
-        }
+        SQ_TRY(h->owned.reserve(bytes));
+        if (hipMemcpy(h->owned.p, rows, bytes, hipMemcpyHostToDevice) != hipSuccess) return fail(SQ_ERR_HIP, "sq_rows_create: H2D copy failed");
         h->rows = h->owned.p;
     }
-    *out = register_handle(h);
+    *out = register_handle(h.release());
     return SQ_OK;
 }
 
@@ -270,17 +253,8 @@ extern "C" int sq_rows_append(sq_handle_t hid, const void* rows, int64_t n_add, 
     SQ_HIP(hipSetDevice(h->device));
     const size_t esz = h->dtype == SQ_DTYPE_F32 ? 4 : 8;
     const size_t used = (size_t)h->n * h->d * esz, need = (size_t)(h->n + n_add) * h->d * esz;
-    if (need > h->owned.cap) {  // grow by half again at least, contents kept
-        DevBuf nb;
-        SQ_TRY(nb.reserve(std::max(need, used + used / 2)));
-        if (hipMemcpy(nb.p, h->owned.p, used, hipMemcpyDeviceToDevice) != hipSuccess) {
-            nb.release();
-            return fail(SQ_ERR_HIP, "sq_rows_append: device copy failed");
-        }
-        h->owned.release();
-        h->owned = nb;
-        h->rows = h->owned.p;
-    }
+    SQ_TRY(grow_keep(h->owned, used, need));
+    h->rows = h->owned.p;
     if (hipMemcpy(static_cast<char*>(h->owned.p) + used, rows, need - used,
                   mem == SQ_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice) != hipSuccess)
         return fail(SQ_ERR_HIP, "sq_rows_append: copy failed");
@@ -434,10 +408,10 @@ extern "C" int sq_lsh_query(sq_handle_t rows_h, sq_handle_t hamming_h, sq_handle
     long long* pre = h->pre_dev.as<long long>();
     long long* tot = pre + (size_t)nq * m;
     long long* th = reinterpret_cast<long long*>(h->totals_host.p);
-    long long* th_dev = nullptr;
-    SQ_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&th_dev), th, 0));
+    void* th_dev = nullptr;
+    SQ_TRY(h->totals_host.device_ptr(&th_dev));
     SQ_TRY(launch<lsh_bucket_sizes_kernel>(dim3(nq), dim3(256), 0, st, h->ham_idx.as<long long>(), m, h->csr_off, h->n_codes, pre, tot));
-    SQ_TRY(launch<lsh_offsets_kernel>(dim3(1), dim3(1), 0, st, tot, nq, h->off_dev.as<long long>(), th_dev));
+    SQ_TRY(launch<lsh_offsets_kernel>(dim3(1), dim3(1), 0, st, tot, nq, h->off_dev.as<long long>(), static_cast<long long*>(th_dev)));
     SQ_HIP(stream_wait(st));
     const long long total = th[0], maxc = th[1];
     if (maxc >= (1ll << 32)) return fail(SQ_ERR_UNSUPPORTED, "sq_lsh_query: more than 2^32-1 candidates for one query");

@@ -1,0 +1,56 @@
+// Stand-in for <hip/hip_runtime.h>, for tests/host/buffers_main.cpp only: the allocation, free and copy calls that
+// smqtk_indexing_amd/csrc/sq_buffers.hpp uses, on malloc / free / memcpy, so that the owning buffer types run on a CPU
+// under the host sanitizers.  "Device" and pinned memory are plain heap blocks; every copy is done when it returns.
+#pragma once
+#include <cstddef>
+#include <cstdlib>
+#include <cstring>
+
+typedef int hipError_t;
+enum : int { hipSuccess = 0, hipErrorInvalidValue = 1, hipErrorOutOfMemory = 2 };
+typedef struct hipStubStream* hipStream_t;
+enum hipMemcpyKind { hipMemcpyHostToHost, hipMemcpyHostToDevice, hipMemcpyDeviceToHost, hipMemcpyDeviceToDevice };
+enum : unsigned { hipHostMallocDefault = 0 };
+
+namespace hip_stub {
+inline long fail_in = 0;      // N > 0: the N-th allocation from now fails (device and pinned ones count alike)
+inline long allocs = 0, frees = 0, device_ptr_calls = 0;
+inline void* const kPoison = reinterpret_cast<void*>(0x5a5a5a5a5a5a5a50ull);   // what a failed allocation leaves in *p
+
+inline hipError_t alloc(void** p, size_t bytes) {
+    if (fail_in > 0 && --fail_in == 0) {
+        *p = kPoison;
+        return hipErrorOutOfMemory;
+    }
+    *p = malloc(bytes ? bytes : 1);
+    if (!*p) return hipErrorOutOfMemory;
+    memset(*p, 0xcd, bytes);
+    ++allocs;
+    return hipSuccess;
+}
+inline hipError_t release(void* p) {
+    if (p) ++frees;
+    free(p);
+    return hipSuccess;
+}
+}  // namespace hip_stub
+
+inline hipError_t hipMalloc(void** p, size_t bytes) { return hip_stub::alloc(p, bytes); }
+inline hipError_t hipFree(void* p) { return hip_stub::release(p); }
+inline hipError_t hipHostMalloc(void** p, size_t bytes, unsigned) { return hip_stub::alloc(p, bytes); }
+inline hipError_t hipHostFree(void* p) { return hip_stub::release(p); }
+inline hipError_t hipHostGetDevicePointer(void** dev, void* host, unsigned) {
+    ++hip_stub::device_ptr_calls;
+    *dev = host;
+    return host ? hipSuccess : hipErrorInvalidValue;
+}
+inline hipError_t hipMemcpy(void* dst, const void* src, size_t bytes, hipMemcpyKind) {
+    memcpy(dst, src, bytes);
+    return hipSuccess;
+}
+inline hipError_t hipMemcpyAsync(void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t) {
+    return hipMemcpy(dst, src, bytes, kind);
+}
+inline const char* hipGetErrorString(hipError_t e) {
+    return e == hipSuccess ? "no error" : e == hipErrorOutOfMemory ? "out of memory" : "invalid value";
+}
