@@ -77,13 +77,49 @@ struct DenseSlot {
     hipEvent_t ev_in = nullptr, ev_done = nullptr;
     hipStream_t own = nullptr;    // internal stream of the slot (asynchronous calls with "dense_async_streams" = 2)
     DenseCall call;
+    void drop_graph() {   // (a captured call graph holds the index's shape and buffers: sq_dense_compact)
+        if (gexec) (void)hipGraphExecDestroy(gexec), gexec = nullptr;
+        gkey = seen_key = 0;
+    }
     ~DenseSlot() {   // (the buffers free themselves, after this body)
-        if (gexec) (void)hipGraphExecDestroy(gexec);
+        drop_graph();
         for (auto& e : ev)
             if (e) (void)hipEventDestroy(e);
         if (ev_in) (void)hipEventDestroy(ev_in);
         if (ev_done) (void)hipEventDestroy(ev_done);
         if (own) (void)hipStreamDestroy(own);
+    }
+};
+
+// The int8 first-stage filter's copy (sq_dense_i8.hpp): the copy, its row terms, what the build measured and how the
+// filter has fared since.  A handle keeps the two buffers exactly while `use` is set (dense8_build, dense8_append).
+struct Int8Copy {
+    DevBuf scan, nrow;          // int8 rows [n_alloc][row_bytes] (wide rows: + I8W_SPARE), float32 row terms [n_alloc + 64]
+    bool use = false;           // the copy exists (and follows appends)
+    bool suspended = false;     // ... but automatic mode (dense_int8 = -1) leaves it alone: its lists overflowed three calls in a row.  dense_int8 = 1 re-arms it, a rebuild (the index doubled) too
+    int overflow = 0;           // calls in a row in which the filter's lists overflowed (data it does not suit)
+    int row_bytes = 0;          // 128, 256 or 512; rows beyond 512 dimensions (sq_dense_i8_wide.hpp): a multiple of 128
+    long long n_pass = 0;       // rows a pass covers (what sq_stats_t.bytes_scanned prices): whole 64-row units, wide rows whole 32-row tiles
+    long long n_alloc = 0;      // rows the copy is allocated and padded for: a multiple of 128 (the largest ring unit)
+    float dx = 0.f, cut = 0.f;  // the build's step and residual cut (R^2 rounded down): rows appended later are quantised and flagged with them
+    double rmax = 0.0, xmax = 0.0;   // R and X of the filter's error bound: the largest residual and the largest |x'| of the rows under the cut
+    long long flagged = 0;      // always-candidate rows (beyond the cut)
+    long long n8_built = 0;     // rows the clamp was last chosen from, accepted or not (an index twice that size chooses again)
+    void drop() { scan.release(), nrow.release(), use = false; }   // (n8_built stays: the attempt counts)
+    // a call may take the int8 stage / what sq_dense_info reports as "in use" and as the copy's bytes
+    bool active(const Options& o) const { return use && o.dense_int8 != 0 && !(suspended && o.dense_int8 < 0); }
+    bool in_use() const { return use && !suspended; }
+    size_t bytes() const {
+        // (rows beyond 512 dimensions: the bytes the copy occupies, not its allocations -- it follows every append)
+        if (use && row_bytes > I8_MAX_ROW_BYTES) return (size_t)n_alloc * row_bytes + I8W_SPARE + (size_t)(n_alloc + 64) * 4;
+        return scan.cap + nrow.cap;
+    }
+    // an int8 stage takes a call although automatic mode had suspended it (dense_int8 = 1 on the handle): the filter is
+    // armed again (and judged again from the next calls: three heavy ones in a row suspend it)
+    void rearm() { if (suspended) suspended = false, overflow = 0; }
+    void note_overflow(bool heavy, const Options& o) {
+        overflow = heavy ? overflow + 1 : 0;
+        if (overflow >= 3 && o.dense_int8 < 0) suspended = true;
     }
 };
 
@@ -100,20 +136,9 @@ struct DenseHandle : HandleBase {
     int metric = SQ_METRIC_L2;
     long long id_base = 0;
     double xn2_max = 0.0;       // max squared row norm (error bound of the L2 filter)
-    // the int8 first-stage filter (sq_dense_i8.hpp): copy, row terms, and what the build measured
-    DevBuf scan8, nrow8;
-    bool use8 = false;          // the int8 copy exists (and follows appends)
-    bool suspended8 = false;    // ... but automatic mode (dense_int8 = -1) leaves it alone: its lists overflowed three calls in a row.  dense_int8 = 1 re-arms it, a rebuild (the index doubled) too
-    int row8 = 0;               // bytes per row of the copy: 128, 256 or 512; rows beyond 512 dimensions (sq_dense_i8_wide.hpp): a multiple of 128
-    long long n_pad64 = 0;      // rows a pass covers (what sq_stats_t.bytes_scanned prices): whole 64-row units, wide rows whole 32-row tiles
-    long long n_alloc8 = 0;     // rows the copy is allocated and padded for: a multiple of 128 (the largest ring unit)
-    double dx8 = 0.0, rmax8 = 0.0, xmax8 = 0.0;
-    long long flagged8 = 0;
-    int overflow8 = 0;          // calls in a row in which the int8 filter's lists overflowed (data it does not suit): it is dropped
+    Int8Copy i8;                // the int8 first-stage filter
     bool graph_broken = false;  // a call-graph capture failed on this handle: eager launches from then on
-    float dxf8 = 0.f, inv_dxf8 = 0.f, cut8 = 0.f;   // the build's step and residual cut, for rows appended later
     long long build_us = 0, build8_us = 0;   // sq_dense_info: wall time of sq_dense_create / of its int8 part
-    long long n8_built = 0;     // rows the clamp was chosen from (an index twice that size chooses again)
     DevBuf norms1;  // L2: |x|^2 (1 - alpha) for one query plane (`norms`: two planes)
     // rows taken out by sq_dense_remove (sq_dense_remove.hpp): a bitmap over the n rows, allocated at the first removal
     // (null until then: every kernel that takes it does exactly what it did).  Ids stay stable: removed rows keep their
@@ -141,6 +166,13 @@ struct DenseHandle : HandleBase {
     int overflow16 = 0;
     bool first_suspended = false;
     unsigned direct_calls = 0, probe_interval = 16;
+    // what sq_dense_create starts from, for an index whose rows have changed under it (sq_dense_compact): the statistics
+    // and the first filters' record are of the old rows, the captured call graphs hold the old shape and the old buffers
+    void reset_filter_state() {
+        xn2_max = 0.0, mid_cos_n = -1;
+        overflow16 = 0, first_suspended = false, direct_calls = 0, probe_interval = 16;
+        for (auto& sl : slot) sl.drop_graph();
+    }
     PinnedStage stage;
     hipEvent_t ev_ref = nullptr;   // SQ_TRACE (measurement aid): the origin of the printed call timelines
     ~DenseHandle() override {
@@ -255,7 +287,7 @@ static DenseDeadTerms dense_dead_terms(const DenseHandle* h) {
         t.norms = h->norms.as<float>();
         t.norms1 = h->norms1.as<float>();
     }
-    if (h->use8 && h->nrow8.p) t.nrow8 = h->nrow8.as<float>();
+    t.nrow8 = h->i8.nrow.as<float>();   // (null without a copy)
     if (cosine && h->scan.p) {
         t.scan = h->scan.as<uint4>();
         t.scan_cpr = h->d_pad / 8;
@@ -488,14 +520,6 @@ static int dense_tighten_scratch(DenseSlot& s, size_t entries, hipStream_t st, D
     t.thr2k = reinterpret_cast<u32*>(t.thr2 + TG_CAP_Q);
     return SQ_OK;
 }
-// an int8 stage takes a call although automatic mode had suspended it (dense_int8 = 1 on the handle): the filter is armed
-// again (and judged again from the next calls)
-static void dense8_rearm(DenseHandle* h) {
-    if (h->suspended8) {
-        h->suspended8 = false;
-        h->overflow8 = 0;
-    }
-}
 static constexpr u32 kWaveCap = 2048;   // entries of a wave's survivor segment
 
 // The survivors of a pass -- per-wave segments of (first row, mask, query) entries -- and where their keys go: exact
@@ -605,12 +629,12 @@ static int dense_small_enqueue(DenseHandle* h, DenseSlot& s, const DenseCtx& e) 
 static int dense8_wide_enqueue(DenseHandle* h, DenseSlot& s, const DenseCtx& e) {
     const long long n = h->n;
     DenseCall& c = s.call;
-    const int d = h->d, row8 = h->row8, ku = i8w_units(row8), qw = ku * I8W_UNIT;
+    const int d = h->d, row8 = h->i8.row_bytes, ku = i8w_units(row8), qw = ku * I8W_UNIT;
     hipStream_t st = c.st;
     c.int8 = true;
-    dense8_rearm(h);
+    h->i8.rearm();
     c.stats.scan_launches = 2;
-    c.stats.bytes_scanned = h->n_pad64 * ((long long)row8 + 4);
+    c.stats.bytes_scanned = h->i8.n_pass * ((long long)row8 + 4);
     const long long n_tiles = (n + TILE_ROWS - 1) / TILE_ROWS;
     const long long stride = dense_tile_stride(h->opt, n, n_tiles, e.kk, 1, e.cosine, e.cap);
     const long long ns_tiles = (n_tiles + stride - 1) / stride;
@@ -631,12 +655,12 @@ static int dense8_wide_enqueue(DenseHandle* h, DenseSlot& s, const DenseCtx& e) 
     DenseTighten tg;
     if (tighten) SQ_TRY(dense_tighten_scratch(s, (size_t)n_waves * kWaveCap, st, tg));
     const float* centerp = (!e.cosine && h->center.p) ? h->center.as<float>() : nullptr;
-    SQ_TRY(launch<dense8_wide_prep_queries_kernel>(dim3(TILE_ROWS), dim3(256), 0, st, c.q, c.nq, d, centerp, h->dx8, h->rmax8, h->xmax8,
+    SQ_TRY(launch<dense8_wide_prep_queries_kernel>(dim3(TILE_ROWS), dim3(256), 0, st, c.q, c.nq, d, centerp, (double)h->i8.dx, h->i8.rmax, h->i8.xmax,
                                                    s.q8.as<signed char>(), qw, s.par8.as<float2>(), e.qn2, e.thr, e.cnt, e.oflag, s.q_al.as<float>(), ldq,
                                                    e.cosine ? 1 : 0));
     Dense8WideArgs a{};
-    a.scan8 = h->scan8.as<signed char>();
-    a.nrow = h->nrow8.as<float>();
+    a.scan8 = h->i8.scan.as<signed char>();
+    a.nrow = h->i8.nrow.as<float>();
     a.row_bytes = row8;
     a.ku = ku;
     a.n = n;
@@ -742,11 +766,11 @@ static int dense8_enqueue(DenseHandle* h, DenseSlot& s, const DenseCtx& e) {
     DenseCall& c = s.call;
     const int d = h->d;
     c.int8 = true;
-    dense8_rearm(h);
+    h->i8.rearm();
     // (128-byte rows stream in ring units of 64 rows on eight waves.  Two other geometries were built and measured --
     // commit 5048766: 128-row units on four waves 0.197 against 0.204 ms per pass alone but 0.244-0.251 against 0.223-0.226 ms
     // per pipelined step; 32-row units on sixteen waves 0.236 -- and removed again.)
-    const int row8 = h->row8, unit_rows = i8_unit_rows(row8), spu = 2 * (unit_rows / 32), waves8 = i8_waves(row8);   // samples per unit
+    const int row8 = h->i8.row_bytes, unit_rows = i8_unit_rows(row8), spu = 2 * (unit_rows / 32), waves8 = i8_waves(row8);   // samples per unit
     const long long n_units = (n + unit_rows - 1) / unit_rows;
     long long stride = h->opt.sample_stride;
     if (stride <= 0) {
@@ -782,8 +806,8 @@ static int dense8_enqueue(DenseHandle* h, DenseSlot& s, const DenseCtx& e) {
     SQ_TRY(s.q_al.reserve((size_t)c.nq * ldq * 4));
     const float* centerp = (!e.cosine && h->center.p) ? h->center.as<float>() : nullptr;
     Dense8ScanArgs a{};
-    a.scan8 = h->scan8.as<signed char>();
-    a.nrow = h->nrow8.as<float>();
+    a.scan8 = h->i8.scan.as<signed char>();
+    a.nrow = h->i8.nrow.as<float>();
     a.n = n;
     a.n_units = n_units;
     a.qs8 = s.q8.as<signed char>();
@@ -798,7 +822,7 @@ static int dense8_enqueue(DenseHandle* h, DenseSlot& s, const DenseCtx& e) {
     a.plane_rows = c.nq_pad;
     a.debug = h->opt.dense_debug;
     // (cacheable head: 32-64 MB measured best here -- 0.244 ms per step at 10 M rows against 0.250 at the bf16 copy's 192 MB)
-    dense_nt_policy(h->opt, (size_t)h->n_pad64 * row8, row8, 64, e.nqt == 1, a.nt, a.nt_from_row);
+    dense_nt_policy(h->opt, (size_t)h->i8.n_pass * row8, row8, 64, e.nqt == 1, a.nt, a.nt_from_row);
     if (ns_units < (long long)nrb_sample * waves8) nrb_sample = (int)(((ns_units + waves8 - 1) / waves8 + 7) / 8 * 8);
     // Three launches instead of six (sq_dense_i8.hpp, "a call in three launches"): one query tile, and a head grid whose
     // M = workgroups x waves x 2 lane minima per query number at least 4 k (the threshold is then within a few per cent of
@@ -846,9 +870,9 @@ static int dense8_enqueue(DenseHandle* h, DenseSlot& s, const DenseCtx& e) {
             ha.nq = c.nq;
             ha.d = d;
             ha.center = centerp;
-            ha.dx = h->dx8;
-            ha.r_max = h->rmax8;
-            ha.x_max = h->xmax8;
+            ha.dx = (double)h->i8.dx;
+            ha.r_max = h->i8.rmax;
+            ha.x_max = h->i8.xmax;
             ha.cosine = e.cosine ? 1 : 0;
             ha.qn2 = e.qn2;
             ha.cnt = e.cnt;
@@ -893,8 +917,8 @@ static int dense8_enqueue(DenseHandle* h, DenseSlot& s, const DenseCtx& e) {
             });
         }
         SQ_TRY(with_row8(row8, [&](auto ks) {
-            return launch<dense8_prep_queries_kernel<decltype(ks)::value / 2>>(dim3(c.nq_pad / 4), dim3(64), 0, cs, c.q, c.nq, d, centerp, h->dx8, h->rmax8,
-                                                                               h->xmax8, s.q8.as<signed char>(), s.par8.as<float2>(), e.qn2, e.thr, e.cnt,
+            return launch<dense8_prep_queries_kernel<decltype(ks)::value / 2>>(dim3(c.nq_pad / 4), dim3(64), 0, cs, c.q, c.nq, d, centerp, (double)h->i8.dx, h->i8.rmax,
+                                                                               h->i8.xmax, s.q8.as<signed char>(), s.par8.as<float2>(), e.qn2, e.thr, e.cnt,
                                                                                e.oflag, s.q_al.as<float>(), ldq, ind, e.cosine ? 1 : 0, c.nq_pad);
         }));
         Dense8ScanArgs b = a;
@@ -921,13 +945,13 @@ static int dense8_enqueue(DenseHandle* h, DenseSlot& s, const DenseCtx& e) {
         });
     };
     c.stats.scan_launches = 2;
-    c.stats.bytes_scanned = h->n_pad64 * ((long long)row8 + 4) * e.nqt;
+    c.stats.bytes_scanned = h->i8.n_pass * ((long long)row8 + 4) * e.nqt;
     return dense8_launch_chain(
         h, s,
         {(u64)(fused ? 1 : 0), (u64)(tighten ? 1 : 0), (u64)(uintptr_t)s.wave_score.p, (u64)(uintptr_t)s.hist8.p, (u64)lane_m, (u64)c.nq, (u64)c.k, (u64)row8,
          (u64)e.qt, (u64)e.nqt, (u64)wpb, (u64)stride, (u64)nrb, (u64)nrb_sample, (u64)ns, (u64)a.nt, (u64)a.nt_from_row, (u64)n, (u64)h->n_live, (u64)e.cap,
-         (u64)h->opt.dense_debug, (u64)h->id_base, (u64)(uintptr_t)c.st, (u64)(uintptr_t)h->db, (u64)(uintptr_t)centerp, (u64)(uintptr_t)h->scan8.p,
-         (u64)(uintptr_t)h->nrow8.p, (u64)(uintptr_t)s.q8.p, (u64)(uintptr_t)s.par8.p, (u64)(uintptr_t)s.sample.p, (u64)(uintptr_t)s.keys.p,
+         (u64)h->opt.dense_debug, (u64)h->id_base, (u64)(uintptr_t)c.st, (u64)(uintptr_t)h->db, (u64)(uintptr_t)centerp, (u64)(uintptr_t)h->i8.scan.p,
+         (u64)(uintptr_t)h->i8.nrow.p, (u64)(uintptr_t)s.q8.p, (u64)(uintptr_t)s.par8.p, (u64)(uintptr_t)s.sample.p, (u64)(uintptr_t)s.keys.p,
          (u64)(uintptr_t)s.wave_out.p, (u64)(uintptr_t)s.wave_cnt.p, (u64)(uintptr_t)s.q_al.p, (u64)(uintptr_t)e.cnt, (u64)(uintptr_t)e.thr,
          (u64)(uintptr_t)e.qn2, (u64)(uintptr_t)e.oflag, (u64)(uintptr_t)s.out_keys.p, (u64)(uintptr_t)e.hs_cnt_dev, (u64)(uintptr_t)cnx,
          (u64)(uintptr_t)e.cnq, (u64)(e.cosine ? 1 : 0)},
@@ -1107,12 +1131,12 @@ static int dense_enqueue(DenseHandle* h, DenseSlot& s, const float* q, int nq, i
     const int nq_pad = e.nqt * e.group_q;
     // Which first stage takes the call.  The shortcut past a suspended filter and the two int8 stages need no bfloat16
     // copy; the bfloat16 chain does, and builds it here when option "dense_bf16" left it for the first call that wants it.
-    const bool int8_on = filter_ok && h->use8 && h->opt.dense_int8 != 0 && !(h->suspended8 && h->opt.dense_int8 < 0);
+    const bool int8_on = filter_ok && h->i8.active(h->opt);
     const bool take_mid = filter_ok && h->first_suspended && h->opt.dense_mid_tier != 0 && !h->opt.force_fallback && dense_mid_shape_ok(h) &&
                           ++h->direct_calls % h->probe_interval != 0;
-    const bool take_i8_wide = !take_mid && int8_on && h->row8 > I8_MAX_ROW_BYTES && nq <= TILE_ROWS;
-    const bool take_i8 = !take_mid && int8_on && h->row8 <= I8_MAX_ROW_BYTES &&
-                         (nq <= TILE_ROWS || (h->row8 == 128 && (qt == 2 || qt == 4) && nq <= h->opt.dense_int8_batch));
+    const bool take_i8_wide = !take_mid && int8_on && h->i8.row_bytes > I8_MAX_ROW_BYTES && nq <= TILE_ROWS;
+    const bool take_i8 = !take_mid && int8_on && h->i8.row_bytes <= I8_MAX_ROW_BYTES &&
+                         (nq <= TILE_ROWS || (h->i8.row_bytes == 128 && (qt == 2 || qt == 4) && nq <= h->opt.dense_int8_batch));
     bool take_bf16 = filter_ok && !take_mid && !take_i8_wide && !take_i8 && h->opt.dense_bf16 != 0;
     if (take_bf16 && !h->scan.p) {
         SQ_TRY(dense_bf16_materialize(h));   // (finishes the calls in flight first; no memory for the copy is no error)
@@ -1247,8 +1271,7 @@ static int dense_resolve_wait(DenseHandle* h, DenseSlot& s, const DenseCtx& e) {
         const long long cands = h->stats.candidates;   // (of this call: summed above)
         // (... or pass so many rows that the re-rank outweighs the bytes saved: the bf16 filter passes ~50 k of 10 M)
         const bool heavy = 2 * over > nq || cands > (long long)nq * std::max<long long>(24ll * 1024, n / 128);
-        h->overflow8 = heavy ? h->overflow8 + 1 : 0;
-        if (h->overflow8 >= 3 && h->opt.dense_int8 < 0) h->suspended8 = true;
+        h->i8.note_overflow(heavy, h->opt);
     }
     if (!c.small && (!c.int8 || h->opt.dense_int8 > 0)) {   // (an int8 stage in automatic mode suspends itself first, above)
         const bool heavy = 2 * over > nq;
@@ -1662,266 +1685,205 @@ static int dense_bf16_materialize(DenseHandle* h) {
 static bool dense8_is_wide(const DenseHandle* h) { return h->d > I8_MAX_ROW_BYTES; }
 static bool dense8_wide_wanted(const DenseHandle* h) { return h->opt.dense_int8_wide != 0 && h->d_pad <= MAX_DPAD; }
 // the build kernels for a row width: EPL = row bytes / 64, wide rows in chunks of 512 bytes (EPL = 8)
-template <class... A>
-static int dense8_energy_launch(int row8, dim3 grid, A... a) {
-    return with_row8(row8, [&](auto ks) { return launch<dense8_energy_kernel<decltype(ks)::value / 2>>(grid, dim3(256), 0, nullptr, a...); }, true);
-}
-template <class... A>
-static int dense8_clip_stats_launch(int row8, dim3 grid, A... a) {
-    return with_row8(row8, [&](auto ks) { return launch<dense8_clip_stats_kernel<decltype(ks)::value / 2>>(grid, dim3(256), 0, nullptr, a...); }, true);
-}
-template <class... A>
-static int dense8_build_launch(int row8, dim3 grid, A... a) {
-    return with_row8(row8, [&](auto ks) { return launch<dense8_build_kernel<decltype(ks)::value / 2>>(grid, dim3(256), 0, nullptr, a..., row8); }, true);
+template <class F>
+static int with_epl8(int row8, F&& f) {
+    return with_row8(row8, [&](auto ks) { return f(std::integral_constant<int, decltype(ks)::value / 2>{}); }, true);
 }
 // rows a pass over the copy covers: whole ring units of 64 rows, wide rows whole 32-row tiles
 static long long dense8_pass_rows(const DenseHandle* h, long long n) { return dense8_is_wide(h) ? (n + 31) / 32 * 32 : (n + 63) / 64 * 64; }
 
-static int dense8_build(DenseHandle* h) {
-    h->use8 = false;
-    h->suspended8 = false;
-    h->overflow8 = 0;
-    const bool wide = dense8_is_wide(h);
-    if ((wide && !dense8_wide_wanted(h)) || h->n < 65536 || h->opt.dense_int8 == 0) return SQ_OK;
-    const bool cosine = h->metric == SQ_METRIC_COSINE;
-    const double* nx64 = cosine ? h->cos_nx.as<double>() : nullptr;   // cosine: the copy holds the unit-length rows
-    const long long n = h->n;
-    h->n8_built = n;   // (an attempt counts whether or not the data is accepted: dense8_append tries again when the index has doubled)
-    const int d = h->d;
-    const int row8 = wide ? i8w_row_bytes(d) : i8_row_bytes(d);
-    const size_t spare8 = wide ? I8W_SPARE : 0;   // (the wide kernel's last half unit: sq_dense_i8_wide.hpp)
-    const long long n_pad64 = dense8_pass_rows(h, n), n_alloc = (n + 127) / 128 * 128;
-    const float* centerp = (!cosine && h->center.p) ? h->center.as<float>() : nullptr;
-    DevBuf tmp;   // [sum f64 x2 | max bits u32 x2 | flagged u32]
-    DevBuf r2row;
-    struct DropUnused {   // on every way out from here: a handle that does not use the copy keeps no memory for one
-        DenseHandle* h;
-        ~DropUnused() {
-            if (!h->use8) {
-                h->scan8.release();
-                h->nrow8.release();
-            }
-        }
-    } drop_unused{h};
-    if (tmp.reserve(64) != SQ_OK || r2row.reserve((size_t)n_alloc * 4) != SQ_OK || h->scan8.reserve((size_t)n_alloc * row8 + spare8) != SQ_OK ||
-        h->nrow8.reserve((size_t)(n_alloc + 64) * 4) != SQ_OK) {   // (+ 64: a 32-row unit's DMA fetches 64 row terms)
-        (void)hipGetLastError();
-        return SQ_OK;
-    }
-    const int stat_blocks = cu_count(h->device) * 8;
-    double rms = 0.0, cap_e = (double)__builtin_inff();
+static size_t dense8_spare(const DenseHandle* h) { return dense8_is_wide(h) ? I8W_SPARE : 0; }   // (the wide kernel's last half unit: sq_dense_i8_wide.hpp)
+// On every way out of dense8_build and dense8_append: a handle that does not use the copy keeps no memory for one (the
+// build declined, an allocation failed, an append stopped half-way: a copy that lacks the new rows is not kept either).
+struct Dense8DropUnused {
+    Int8Copy& c;
+    ~Dense8DropUnused() { if (!c.use) c.drop(); }
+};
+struct Dense8Stats {   // what dense8_quantise reads back (the kernels keep the maxima as the bits of non-negative floats)
+    double energy, sum_r2;
+    float max_r2, max_n;
+    u32 flagged, pad;
+};
+// What the build's kernels share: the rows they quantise -- cosine the unit-length rows (nx64: their float64 |x|^2), L2 the
+// rows minus the filter's origin -- and their scratch.
+struct Dense8Work {
+    const double* nx64;
+    const float* center;
+    DevBuf tmp, r2row;   // 64 bytes [Dense8Stats], the rows' squared residuals [n_alloc]
+    explicit Dense8Work(const DenseHandle* h)
+        : nx64(h->metric == SQ_METRIC_COSINE ? h->cos_nx.as<double>() : nullptr), center(h->metric != SQ_METRIC_COSINE ? h->center.as<float>() : nullptr) {}
+};
+
+// The element rms of the rows the copy would hold, from three passes of dense8_energy_kernel: no cap, then 16 x the mean
+// of the pass before.  0: half the rows are non-finite or beyond 16 x the mean -- not this filter's data.
+static int dense8_measure_rms(const DenseHandle* h, Dense8Work& w, int blocks, double* rms) {
+    double cap_e = (double)__builtin_inff();
     for (int pass = 0; pass < 3; ++pass) {
         double er[2] = {0.0, 0.0};
-        SQ_HIP(hipMemset(tmp.p, 0, 64));
-        if (const int rc = dense8_energy_launch(row8, dim3(stat_blocks), h->db, n, h->ld, d, centerp, nx64, cap_e, tmp.as<double>())) return rc;
-        SQ_HIP(hipMemcpy(er, tmp.p, 16, hipMemcpyDeviceToHost));
-        if (!(er[1] >= 0.5 * (double)n)) return SQ_OK;   // (half the rows non-finite or beyond 16 x the mean: not this filter's data)
-        rms = sqrt(er[0] / (er[1] * d));
+        SQ_HIP(hipMemset(w.tmp.p, 0, 64));
+        SQ_TRY(with_epl8(h->i8.row_bytes, [&](auto epl) {
+            return launch<dense8_energy_kernel<decltype(epl)::value>>(dim3(blocks), dim3(256), 0, nullptr, h->db, h->n, h->ld, h->d, w.center, w.nx64, cap_e, w.tmp.as<double>());
+        }));
+        SQ_HIP(hipMemcpy(er, w.tmp.p, 16, hipMemcpyDeviceToHost));
+        if (!(er[1] >= 0.5 * (double)h->n)) return *rms = 0.0, SQ_OK;
+        *rms = sqrt(er[0] / (er[1] * h->d));
         cap_e = 16.0 * er[0] / er[1];
     }
-    if (!(rms > 0.0) || !(rms < 1e30)) return SQ_OK;
-    SQ_HIP(hipMemset(tmp.p, 0, 64));
-    // the clamp and R from the measured residuals of twelve candidate clamps (dense8_clip_stats_kernel)
-    // (1.75 rms: where a uniform distribution ends; 9-11 rms: one-sided data -- max(N(0,1), 0) reaches 8.4 rms of its centred
-    // self; 14-18 rms: sparse rows -- with 10 % of the elements set their rms is a third of an element's own scale)
-    static const double kClip[I8_NCLIP] = {1.75, 2.5, 3.25, 4.0, 4.75, 5.5, 6.5, 7.5, 9.0, 11.0, 14.0, 18.0};
-    static const double kCut[I8_NCUT] = {0.6, 0.8, 1.0, 1.10, 1.15, 1.20, 1.30, 1.50, 2.0, 3.0};   // R in units of Dx sqrt(d / 12)
-    Dense8ClipArgs ca{};
-    const double round_unit = sqrt((double)d / 12.0);
-    for (int c = 0; c < I8_NCLIP; ++c) {
-        ca.dx[c] = (float)(kClip[c] * rms / 127.0);
-        ca.inv_dx[c] = 1.0f / ca.dx[c];
-        for (int m = 0; m < I8_NCUT; ++m) {
-            const double r = kCut[m] * (double)ca.dx[c] * round_unit;
-            ca.cut[c][m] = (float)(r * r);
-        }
-    }
-    DevBuf clipbuf;   // counts u32 [NCLIP][NCUT]
+    return SQ_OK;
+}
+
+// The clamp and R from the measured residuals of the candidate clamps (dense8_clip_stats_kernel, i8_choose_clamp);
+// `best` stays empty where no clamp suits the data (or there is no memory for the counts).
+static int dense8_choose(const DenseHandle* h, const Dense8Work& w, const Dense8ClipArgs& ca, int blocks, I8Clamp* best) {
+    DevBuf clipbuf;   // counts u32 [NCLIP][NCUT] (freed on return: the copy is built next)
     const size_t clip_bytes = I8_NCLIP * I8_NCUT * 4;
     if (clipbuf.reserve(clip_bytes) != SQ_OK) return SQ_OK;
     SQ_HIP(hipMemset(clipbuf.p, 0, clip_bytes));
     // large matrices choose from every 8th row (the kernel evaluates twelve clamps per element: 16 ms of a 40 ms build at
     // 10 M x 128 when it reads every row; the choice needs the shape of the residuals' tail, not every row)
-    const int clip_step = n >= 2000000 ? 8 : 1;
-    if (const int rc = dense8_clip_stats_launch(row8, dim3(stat_blocks), h->db, n, h->ld, d, centerp, nx64, ca, clipbuf.as<u32>(), clip_step)) return rc;
+    const int clip_step = h->n >= 2000000 ? 8 : 1;
+    SQ_TRY(with_epl8(h->i8.row_bytes, [&](auto epl) {
+        return launch<dense8_clip_stats_kernel<decltype(epl)::value>>(dim3(blocks), dim3(256), 0, nullptr, h->db, h->n, h->ld, h->d, w.center, w.nx64, ca, clipbuf.as<u32>(), clip_step);
+    }));
     u32 counts[I8_NCLIP][I8_NCUT];
     SQ_HIP(hipMemcpy(counts, clipbuf.p, clip_bytes, hipMemcpyDeviceToHost));
-    clipbuf.release();   // (not at scope exit: the copy is built next)
-    for (auto& row : counts)
-        for (u32& v : row) v = (u32)std::min<unsigned long long>(0xffffffffull, (unsigned long long)v * (unsigned)clip_step);
-    // rows beyond R are candidates of every query: a few hundred at most (a query has a few thousand candidates anyway)
-    const double budget = std::max(256.0, 2e-5 * (double)n);
-    int best_c = -1, best_m = -1;
-    double best_r = 0.0;
-    for (int c = 0; c < I8_NCLIP; ++c)
-        for (int m = 0; m < I8_NCUT; ++m)
-            if ((double)counts[c][m] <= budget) {
-                const double r = kCut[m] * (double)ca.dx[c] * round_unit;
-                if (best_c < 0 || r < best_r) best_c = c, best_m = m, best_r = r;
-                break;
-            }
-    if (best_c < 0) return SQ_OK;   // every clamp leaves too many rows beyond every bound (heavy tails): the bf16 filter's relative bound suits such data
-    const double dx = (double)ca.dx[best_c];
-    {
-        const dim3 grid((unsigned)((n_alloc + 3) / 4));
-        signed char* o8 = h->scan8.as<signed char>();
-        float* nr8 = h->nrow8.as<float>();
-        float* r2p = r2row.as<float>();
-        if (const int rc = dense8_build_launch(row8, grid, h->db, n, h->ld, d, n_alloc, centerp, nx64, ca.inv_dx[best_c], ca.dx[best_c], o8, nr8, r2p, 0ll))
-            return rc;
-        SQ_HIP(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(nr8 + n_alloc), 0x7f800000, 64));   // (+inf behind the last unit)
-        if (spare8) SQ_HIP(hipMemset(o8 + (size_t)n_alloc * row8, 0, spare8));
-    }
-    double* sum_r2 = tmp.as<double>() + 1;
-    u32* maxb = reinterpret_cast<u32*>(tmp.as<double>() + 2);
-    u32* flagged = maxb + 2;
-    // rows beyond the chosen bound become always-candidates first; R and X are then the largest residual and the largest
-    // |x'| of the rows that REMAIN under the bound (a row 100x the rest would otherwise set X for every query)
-    double cut = best_r * best_r * (1.0 + 1e-4);   // (the choice was made in float32)
-    if (const int rc = launch<dense8_flag_kernel>(dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, r2row.as<float>(), h->nrow8.as<float>(), n,
-                                                  (float)cut, flagged, 0ll))
-        return rc;
-    if (const int rc = launch<dense8_resid_stats_kernel>(dim3(1024), dim3(256), 0, nullptr, r2row.as<float>(), h->nrow8.as<float>(), n, sum_r2, maxb))
-        return rc;
-    struct {
-        double energy, sum_r2;
-        u32 max_r2, max_n, flagged, pad;
-    } host{};
-    SQ_HIP(hipMemcpy(&host, tmp.p, sizeof(host), hipMemcpyDeviceToHost));
+    *best = i8_choose_clamp(counts, ca, h->d, h->n, clip_step);
+    return SQ_OK;
+}
+
+// One quantise step, the build's (row_base 0, the step and cut just chosen) and an append's (from the unit the old rows
+// ended in, the build's step and cut): the rows from row_base on quantised into the copy, +inf behind the last unit, the
+// wide kernel's spare zeroed.  Rows beyond the cut become always-candidates first; the largest residual and the largest
+// |x'|^2 read back are then of the rows that REMAIN under it (a row 100x the rest would otherwise set X for every query).
+static int dense8_quantise(DenseHandle* h, Dense8Work& w, float dx, float cut, long long row_base, long long n_alloc, int stats_blocks, Dense8Stats* out) {
+    Int8Copy& c = h->i8;
+    const long long n = h->n;
+    signed char* o8 = c.scan.as<signed char>();
+    float *nr8 = c.nrow.as<float>(), *r2p = w.r2row.as<float>();
+    SQ_HIP(hipMemset(w.tmp.p, 0, 64));
+    SQ_TRY(with_epl8(c.row_bytes, [&](auto epl) {
+        return launch<dense8_build_kernel<decltype(epl)::value>>(dim3((unsigned)((n_alloc - row_base + 3) / 4)), dim3(256), 0, nullptr, h->db, n, h->ld, h->d, n_alloc,
+                                                                 w.center, w.nx64, 1.0f / dx, dx, o8, nr8, r2p, row_base, c.row_bytes);
+    }));
+    SQ_HIP(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(nr8 + n_alloc), 0x7f800000, 64));   // (+inf behind the last unit)
+    if (dense8_spare(h)) SQ_HIP(hipMemset(o8 + (size_t)n_alloc * c.row_bytes, 0, dense8_spare(h)));
+    Dense8Stats* dev = w.tmp.as<Dense8Stats>();
+    SQ_TRY(launch<dense8_flag_kernel>(dim3((unsigned)((n - row_base + 255) / 256)), dim3(256), 0, nullptr, r2p, nr8, n, cut, &dev->flagged, row_base));
+    SQ_TRY(launch<dense8_resid_stats_kernel>(dim3(stats_blocks), dim3(256), 0, nullptr, r2p + row_base, nr8 + row_base, n - row_base, &dev->sum_r2,
+                                             reinterpret_cast<u32*>(&dev->max_r2)));
+    SQ_HIP(hipMemcpy(out, dev, sizeof(*out), hipMemcpyDeviceToHost));
     SQ_HIP(hipDeviceSynchronize());
-    float max_r2, max_n;
-    memcpy(&max_r2, &host.max_r2, 4);
-    memcpy(&max_n, &host.max_n, 4);
-    const u32 nflag = host.flagged;
-    if ((double)max_r2 < cut) cut = (double)max_r2 * (1.0 + 1e-6);   // nothing near the bound: R is simply the largest
-    if ((double)nflag > 4.0 * budget) return SQ_OK;
-    h->dx8 = dx;
-    h->rmax8 = sqrt(cut) * (1.0 + 1e-6);
-    h->xmax8 = cosine ? 1.0 + 1e-6 : sqrt((double)max_n) * (1.0 + 1e-6);   // (cosine: unit rows; their row term is 0)
-    h->flagged8 = nflag;
+    c.n_pass = dense8_pass_rows(h, n), c.n_alloc = n_alloc;   // (what the copy covers now)
+    return SQ_OK;
+}
+
+// decide, measure the rms, choose the clamp, quantise, publish
+static int dense8_build(DenseHandle* h) {
+    Int8Copy& c = h->i8;
+    c.use = c.suspended = false, c.overflow = 0;
+    Dense8DropUnused drop_unused{c};
+    const bool wide = dense8_is_wide(h), cosine = h->metric == SQ_METRIC_COSINE;
+    const long long n = h->n, n_alloc = (n + 127) / 128 * 128;
+    const int d = h->d, stat_blocks = cu_count(h->device) * 8;
+    // decide: what a handle without a copy would start now (a copy that was there is chosen again on the same terms)
+    if (i8_append_action(h->opt.dense_int8, wide, dense8_wide_wanted(h), false, n, 0) != I8Action::build) return SQ_OK;
+    c.n8_built = n;   // (an attempt counts whether or not the data is accepted: dense8_append tries again when the index has doubled)
+    c.row_bytes = wide ? i8w_row_bytes(d) : i8_row_bytes(d);
+    Dense8Work w(h);
+    if (w.tmp.reserve(64) != SQ_OK || w.r2row.reserve((size_t)n_alloc * 4) != SQ_OK || c.scan.reserve((size_t)n_alloc * c.row_bytes + dense8_spare(h)) != SQ_OK ||
+        c.nrow.reserve((size_t)(n_alloc + 64) * 4) != SQ_OK)   // (+ 64: a 32-row unit's DMA fetches 64 row terms)
+        return (void)hipGetLastError(), SQ_OK;
+    double rms = 0.0;
+    SQ_TRY(dense8_measure_rms(h, w, stat_blocks, &rms));
+    if (!(rms > 0.0) || !(rms < 1e30)) return SQ_OK;
+    const Dense8ClipArgs ca = i8_clip_candidates(rms, d);
+    I8Clamp best;
+    SQ_TRY(dense8_choose(h, w, ca, stat_blocks, &best));
+    if (!best.found()) return SQ_OK;
+    const float dx = ca.dx[best.c];
+    double cut = best.r * best.r * (1.0 + 1e-4);   // (the choice was made in float32)
+    Dense8Stats res{};
+    SQ_TRY(dense8_quantise(h, w, dx, (float)cut, 0, n_alloc, 1024, &res));
+    if ((double)res.max_r2 < cut) cut = (double)res.max_r2 * (1.0 + 1e-6);   // nothing near the bound: R is simply the largest
+    if ((double)res.flagged > 4.0 * i8_always_budget(n)) return SQ_OK;
+    c.dx = dx;
+    c.rmax = sqrt(cut) * (1.0 + 1e-6);
+    c.xmax = cosine ? 1.0 + 1e-6 : sqrt((double)res.max_n) * (1.0 + 1e-6);   // (cosine: unit rows; their row term is 0)
+    c.flagged = res.flagged;
     if (getenv("SQ_INT8_REPORT"))   // (measurement aid: what the build chose)
         fprintf(stderr, "[smqtk_hip] int8 filter: clamp %.2f rms, step %.5g, R %.5g (%.2f x the rounding residual), X %.5g, %u always-candidate rows of %lld\n",
-                kClip[best_c], dx, h->rmax8, kCut[best_m], h->xmax8, nflag, n);
-    h->n_pad64 = n_pad64;
-    h->n_alloc8 = n_alloc;
-    h->row8 = row8;
-    h->dxf8 = ca.dx[best_c];
-    h->inv_dxf8 = ca.inv_dx[best_c];
-    {   // appended rows are flagged against R^2 itself (rounded down): R may be smaller than the bound the build flagged with
-        float c8 = (float)cut;
-        if ((double)c8 > cut) c8 = __builtin_nextafterf(c8, 0.f);
-        h->cut8 = c8;
-    }
-    h->n8_built = n;
-    h->overflow8 = 0;
-    h->use8 = true;
+                kClip[best.c], (double)dx, c.rmax, kCut[best.m], c.xmax, res.flagged, n);
+    // appended rows are flagged against R^2 itself (rounded down): R may be smaller than the bound the build flagged with
+    c.cut = (float)cut;
+    if ((double)c.cut > cut) c.cut = __builtin_nextafterf(c.cut, 0.f);
+    c.use = true;
     return SQ_OK;
 }
 
 // Everything an index derives from its float32 rows, built from scratch: the L2 filter's origin, the row statistics, the
 // bfloat16 scan copy, the int8 copy.  sq_dense_create, and sq_dense_compact over the rows that are left.
 static int dense_build_all(DenseHandle* h) {
-    const long long n = h->n;
-    const int d = h->d, d_pad = h->d_pad, metric = h->metric;
+    const int d_pad = h->d_pad;
+    const bool cosine = h->metric == SQ_METRIC_COSINE;
     // the filter's origin (L2): the column means
-    if (metric == SQ_METRIC_L2 && d_pad <= MAX_DPAD && !h->opt.dense_no_center) SQ_TRY(dense_column_means(h, h->center, nullptr));
+    if (!cosine && d_pad <= MAX_DPAD && !h->opt.dense_no_center) SQ_TRY(dense_column_means(h, h->center, nullptr));
     // row statistics, then the bfloat16 scan copy (skipped for rows wider than the scan kernel covers)
-    int rc = h->norms.reserve((size_t)h->n_pad * 4);
-    if (rc == SQ_OK && metric == SQ_METRIC_L2) rc = h->norms1.reserve((size_t)h->n_pad * 4);
-    if (rc == SQ_OK && metric == SQ_METRIC_COSINE) rc = h->cos_nx.reserve((size_t)n * 8);
-    if (rc == SQ_OK && metric == SQ_METRIC_COSINE) {
-        rc = h->zeros.reserve(256);
-        if (rc == SQ_OK && hipMemset(h->zeros.p, 0, 256) != hipSuccess) rc = fail(SQ_ERR_HIP, "dense index build: memset failed");
+    SQ_TRY(h->norms.reserve((size_t)h->n_pad * 4));
+    if (!cosine) SQ_TRY(h->norms1.reserve((size_t)h->n_pad * 4));
+    if (cosine) {
+        SQ_TRY(h->cos_nx.reserve((size_t)h->n * 8));
+        SQ_TRY(h->zeros.reserve(256));
+        SQ_HIP(hipMemset(h->zeros.p, 0, 256));
     }
     // ("dense_bf16" = 1 only: -1 leaves the copy to the first search that streams it, 0 builds none)
-    if (rc == SQ_OK && d_pad <= MAX_DPAD && h->opt.dense_bf16 == 1) rc = h->scan.reserve((size_t)h->n_pad * d_pad * 2);
-    if (rc == SQ_OK) rc = dense_build_rows(h, 0);
-    if (rc == SQ_OK && hipDeviceSynchronize() != hipSuccess) rc = fail(SQ_ERR_HIP, "dense index build failed");
+    if (d_pad <= MAX_DPAD && h->opt.dense_bf16 == 1) SQ_TRY(h->scan.reserve((size_t)h->n_pad * d_pad * 2));
+    SQ_TRY(dense_build_rows(h, 0));
+    SQ_HIP(hipDeviceSynchronize());
     const auto t8 = std::chrono::steady_clock::now();
-    if (rc == SQ_OK) rc = dense8_build(h);
-    if (rc == SQ_OK && hipDeviceSynchronize() != hipSuccess) rc = fail(SQ_ERR_HIP, "dense index build: int8 copy failed");
-    if (rc != SQ_OK) return rc;
+    SQ_TRY(dense8_build(h));
+    SQ_HIP(hipDeviceSynchronize());
     h->build8_us = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t8).count();
     return SQ_OK;
 }
 
 // The int8 copy after an append (h->n is the new row count; the rows are in place).  The step and the residual cut of
 // the build stay: new rows are quantised with them, rows they do not suit become always-candidates like the build's own.
-// An index that has doubled since the clamp was chosen -- or that collected too many always-candidates -- chooses again
-// from all its rows; one that had no copy (too small, or declined) tries when it has doubled since its last attempt.
+// An index that has doubled since its last attempt (i8_append_action) or collected too many always-candidates chooses again.
 static int dense8_append(DenseHandle* h, long long n_old) {
-    const long long n = h->n;
-    // (a wide copy that exists follows the appends whatever "dense_int8_wide" says by now; none is started without it)
-    if (h->opt.dense_int8 == 0 || (dense8_is_wide(h) && !h->use8 && !dense8_wide_wanted(h))) return SQ_OK;
-    if (!h->use8) {
-        if (n >= 65536 && n >= 2 * h->n8_built) {
-            h->n8_built = n;   // (the attempt counts whether or not the build accepts the data)
-            return dense8_build(h);
-        }
-        return SQ_OK;
-    }
-    if (n >= 2 * h->n8_built) return dense8_build(h);
-    const bool cosine = h->metric == SQ_METRIC_COSINE;
-    const double* nx64 = cosine ? h->cos_nx.as<double>() : nullptr;
-    const float* centerp = (!cosine && h->center.p) ? h->center.as<float>() : nullptr;
-    const int row8 = h->row8, d = h->d;
-    const long long n_pad64 = dense8_pass_rows(h, n), n_alloc = (n + 127) / 128 * 128;
-    const size_t spare8 = dense8_is_wide(h) ? I8W_SPARE : 0;
-    struct DropUnfinished {   // on every way out but the end: a copy that lacks the new rows is not kept (nor used)
-        DenseHandle* h;
-        bool finished = false;
-        ~DropUnfinished() {
-            if (finished) return;
-            h->use8 = false;
-            h->scan8.release();
-            h->nrow8.release();
-        }
-    } drop{h};
-    DevBuf tmp, r2row;
-    if (grow_keep(h->scan8, (size_t)h->n_alloc8 * row8, (size_t)n_alloc * row8 + spare8) != SQ_OK ||
-        grow_keep(h->nrow8, (size_t)(h->n_alloc8 + 64) * 4, (size_t)(n_alloc + 64) * 4) != SQ_OK || tmp.reserve(64) != SQ_OK ||
-        r2row.reserve((size_t)n_alloc * 4) != SQ_OK) {
-        (void)hipGetLastError();
-        return SQ_OK;   // (no memory for the copy is not an error: the index goes on without one)
-    }
-    const long long row_base = n_old / 128 * 128;   // the unit the old rows ended in is redone with the new ones
-    {
-        const dim3 grid((unsigned)((n_alloc - row_base + 3) / 4));
-        signed char* o8 = h->scan8.as<signed char>();
-        float* nr8 = h->nrow8.as<float>();
-        float* r2p = r2row.as<float>();
-        if (const int rc = dense8_build_launch(row8, grid, h->db, n, h->ld, d, n_alloc, centerp, nx64, h->inv_dxf8, h->dxf8, o8, nr8, r2p, row_base)) return rc;
-        SQ_HIP(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(nr8 + n_alloc), 0x7f800000, 64));
-        if (spare8) SQ_HIP(hipMemset(o8 + (size_t)n_alloc * row8, 0, spare8));
-    }
-    SQ_HIP(hipMemset(tmp.p, 0, 64));
-    double* sum_r2 = tmp.as<double>() + 1;
-    u32* maxb = reinterpret_cast<u32*>(tmp.as<double>() + 2);
-    u32* flagged = maxb + 2;
-    // the largest |x'|^2 of the new rows BEFORE their always-candidates are marked (a flagged row needs no X)
-    if (const int rc = launch<dense8_flag_kernel>(dim3((unsigned)((n - row_base + 255) / 256)), dim3(256), 0, nullptr, r2row.as<float>(), h->nrow8.as<float>(),
-                                                  n, h->cut8, flagged, row_base))
-        return rc;
-    if (const int rc = launch<dense8_resid_stats_kernel>(dim3(256), dim3(256), 0, nullptr, r2row.as<float>() + row_base, h->nrow8.as<float>() + row_base,
-                                                         n - row_base, sum_r2, maxb))
-        return rc;
-    struct {
-        double energy, sum_r2;
-        u32 max_r2, max_n, flagged, pad;
-    } host{};
-    SQ_HIP(hipMemcpy(&host, tmp.p, sizeof(host), hipMemcpyDeviceToHost));
-    SQ_HIP(hipDeviceSynchronize());
-    float max_n;
-    memcpy(&max_n, &host.max_n, 4);
-    if (!cosine && max_n > 0.f) h->xmax8 = std::max(h->xmax8, sqrt((double)max_n) * (1.0 + 1e-6));
+    Int8Copy& c = h->i8;
+    const long long n = h->n, n_alloc = (n + 127) / 128 * 128;
+    const I8Action act = i8_append_action(h->opt.dense_int8, dense8_is_wide(h), dense8_wide_wanted(h), c.use, n, c.n8_built);
+    if (act != I8Action::extend) return act == I8Action::build ? dense8_build(h) : SQ_OK;
+    c.use = false;   // (until the copy holds the new rows)
+    Dense8DropUnused drop_unused{c};
+    Dense8Work w(h);
+    if (grow_keep(c.scan, (size_t)c.n_alloc * c.row_bytes, (size_t)n_alloc * c.row_bytes + dense8_spare(h)) != SQ_OK ||
+        grow_keep(c.nrow, (size_t)(c.n_alloc + 64) * 4, (size_t)(n_alloc + 64) * 4) != SQ_OK || w.tmp.reserve(64) != SQ_OK ||
+        w.r2row.reserve((size_t)n_alloc * 4) != SQ_OK)
+        return (void)hipGetLastError(), SQ_OK;   // (no memory for the copy is not an error: the index goes on without one)
+    // the unit the old rows ended in is redone with the new ones; the largest |x'|^2 is of the new rows that are not flagged
+    // (a flagged row needs no X)
+    Dense8Stats res{};
+    SQ_TRY(dense8_quantise(h, w, c.dx, c.cut, n_old / 128 * 128, n_alloc, 256, &res));
+    if (h->metric != SQ_METRIC_COSINE && res.max_n > 0.f) c.xmax = std::max(c.xmax, sqrt((double)res.max_n) * (1.0 + 1e-6));
     // (the redone unit's old always-candidates are counted again: an over-estimate on the safe side)
-    h->flagged8 += host.flagged;
-    h->n_pad64 = n_pad64;
-    h->n_alloc8 = n_alloc;
-    drop.finished = true;
-    const double budget = std::max(256.0, 2e-5 * (double)n);
-    if ((double)h->flagged8 > 4.0 * budget) return dense8_build(h);   // the new rows do not look like the old ones: choose again
+    c.flagged += res.flagged;
+    c.use = true;
+    if ((double)c.flagged > 4.0 * i8_always_budget(n)) return dense8_build(h);   // the new rows do not look like the old ones: choose again
     return SQ_OK;
+}
+
+static void dense_set_rows(DenseHandle* h, long long n) { h->n = n, h->n_pad = (n + TILE_ROWS - 1) / TILE_ROWS * TILE_ROWS; }
+// `n` rows of `d` floats into the owned matrix at `dst`, whose rows are padded with zeros to `ld` floats
+static int dense_upload_rows(float* dst, long long ld, const float* rows, long long n, int d, hipMemcpyKind kind) {
+    hipError_t e;
+    if (ld == d) {
+        e = hipMemcpy(dst, rows, (size_t)n * d * 4, kind);
+    } else {
+        e = hipMemset(dst, 0, (size_t)n * ld * 4);
+        if (e == hipSuccess) e = hipMemcpy2D(dst, (size_t)ld * 4, rows, (size_t)d * 4, (size_t)d * 4, (size_t)n, kind);
+    }
+    return e == hipSuccess ? SQ_OK : fail(SQ_ERR_HIP, "copy of the rows failed: %s", hipGetErrorString(e));
 }
 
 // Room for `n_new` rows in every per-row buffer, contents kept (grow_keep: a stream of small appends copies the matrix
@@ -1945,8 +1907,59 @@ static int dense_grow(DenseHandle* h, long long n_new) {
 
 using namespace sq;
 
+// What an index keeps resident and what its build cost (bench.py's `resident_bytes` / `index_build_ms`).
+extern "C" int sq_dense_info(sq_handle_t hid, int64_t* out, int n_out) {
+    auto* h = static_cast<DenseHandle*>(lookup_handle(hid, H_DENSE));
+    if (!h) return fail(SQ_ERR_INVALID, "sq_dense_info: unknown handle");
+    if (!out || n_out < SQ_DENSE_INFO_FIELDS) return fail(SQ_ERR_INVALID, "sq_dense_info: room for %d values needed", SQ_DENSE_INFO_FIELDS);
+    std::lock_guard<std::mutex> l(h->mu);
+    out[0] = h->n;
+    out[1] = h->d;
+    out[2] = (int64_t)h->n * h->ld * 4;                                  // the float32 rows (the re-rank reads them) ...
+    out[3] = h->owned.p ? 1 : 0;                                          // ... owned by the library (1) or borrowed from the caller (0)
+    out[4] = (int64_t)h->scan.cap;                                        // bfloat16 scan copy
+    out[5] = (int64_t)h->i8.bytes();                                      // int8 scan copy + its row terms
+    out[6] = (int64_t)(h->norms.cap + h->norms1.cap + h->cos_nx.cap + h->center.cap + h->zeros.cap);   // row statistics
+    out[7] = h->i8.in_use() ? 1 : 0;                                      // the int8 first stage is in use
+    out[8] = h->build_us;                                                 // sq_dense_create: wall time of the whole build
+    out[9] = h->build8_us;                                                // ... of which the int8 copy (statistics, clamp choice, copy)
+    return SQ_OK;
+}
+
 static int dense_create_impl(const float* db, int64_t n, int d, int metric, int mem, int64_t id_base,
-                             const std::vector<std::pair<int Options::*, int>>& overrides, sq_handle_t* out);
+                             const std::vector<std::pair<int Options::*, int>>& overrides, sq_handle_t* out) {
+    const auto t_create = std::chrono::steady_clock::now();
+    if (!db || !out || n <= 0 || d <= 0) return fail(SQ_ERR_INVALID, "sq_dense_create: bad argument");
+    if (metric != SQ_METRIC_L2 && metric != SQ_METRIC_COSINE) return fail(SQ_ERR_INVALID, "sq_dense_create: unknown metric %d", metric);
+    if (n >= (1ll << 32)) return fail(SQ_ERR_UNSUPPORTED, "sq_dense_create: more than 2^32-1 rows per shard");
+    if (mem == SQ_MEM_DEVICE && ((reinterpret_cast<uintptr_t>(db) & 15u) != 0 || (d & 3) != 0))
+        return fail(SQ_ERR_UNSUPPORTED, "sq_dense_create: a borrowed device matrix must be 16-byte aligned with d %% 4 == 0 (d=%d)", d);
+    auto h = std::make_unique<DenseHandle>();
+    h->kind = H_DENSE;
+    dense_set_rows(h.get(), n);
+    h->n_live = n;
+    h->d = d;
+    h->d_pad = (d + KT - 1) / KT * KT;
+    h->metric = metric;
+    h->id_base = id_base;
+    h->overrides = overrides;   // (create-time choices -- "dense_int8" = 0: no int8 copy -- are the handle's own)
+    h->refresh_options();
+    if (hipGetDevice(&h->device) != hipSuccess) return fail(SQ_ERR_HIP, "sq_dense_create: no HIP device");
+    if (mem == SQ_MEM_DEVICE) {
+        h->db = db;
+        h->ld = d;
+    } else {
+        // owned float32 copy, rows padded to a multiple of 4 floats so the exact kernel can use 16-byte loads
+        h->ld = (d + 3) / 4 * 4;
+        SQ_TRY(h->owned.reserve((size_t)n * h->ld * 4));
+        h->db = h->owned.as<float>();
+        SQ_TRY(dense_upload_rows(h->owned.as<float>(), h->ld, db, n, d, hipMemcpyHostToDevice));
+    }
+    SQ_TRY(dense_build_all(h.get()));
+    h->build_us = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t_create).count();
+    *out = register_handle(h.release());
+    return SQ_OK;
+}
 
 extern "C" int sq_dense_create(const float* db, int64_t n, int d, int metric, int mem, int64_t id_base,
                                sq_handle_t* out) {
@@ -1965,77 +1978,6 @@ extern "C" int sq_dense_create_opts(const float* db, int64_t n, int d, int metri
     return dense_create_impl(db, n, d, metric, mem, id_base, ov, out);
 }
 
-// What an index keeps resident and what its build cost (bench.py's `resident_bytes` / `index_build_ms`).
-extern "C" int sq_dense_info(sq_handle_t hid, int64_t* out, int n_out) {
-    auto* h = static_cast<DenseHandle*>(lookup_handle(hid, H_DENSE));
-    if (!h) return fail(SQ_ERR_INVALID, "sq_dense_info: unknown handle");
-    if (!out || n_out < SQ_DENSE_INFO_FIELDS) return fail(SQ_ERR_INVALID, "sq_dense_info: room for %d values needed", SQ_DENSE_INFO_FIELDS);
-    std::lock_guard<std::mutex> l(h->mu);
-    out[0] = h->n;
-    out[1] = h->d;
-    out[2] = (int64_t)h->n * h->ld * 4;                                  // the float32 rows (the re-rank reads them) ...
-    out[3] = h->owned.p ? 1 : 0;                                          // ... owned by the library (1) or borrowed from the caller (0)
-    out[4] = (int64_t)h->scan.cap;                                        // bfloat16 scan copy
-    out[5] = (int64_t)(h->scan8.cap + h->nrow8.cap);                      // int8 scan copy + its row terms
-    if (h->use8 && h->row8 > I8_MAX_ROW_BYTES)                            // (rows beyond 512 dimensions: the bytes the copy occupies -- it follows every append)
-        out[5] = (int64_t)((size_t)h->n_alloc8 * h->row8 + I8W_SPARE + (size_t)(h->n_alloc8 + 64) * 4);
-    out[6] = (int64_t)(h->norms.cap + h->norms1.cap + h->cos_nx.cap + h->center.cap + h->zeros.cap);   // row statistics
-    out[7] = h->use8 && !h->suspended8 ? 1 : 0;                                             // the int8 first stage is in use
-    out[8] = h->build_us;                                                 // sq_dense_create: wall time of the whole build
-    out[9] = h->build8_us;                                                // ... of which the int8 copy (statistics, clamp choice, copy)
-    return SQ_OK;
-}
-
-static int dense_create_impl(const float* db, int64_t n, int d, int metric, int mem, int64_t id_base,
-                             const std::vector<std::pair<int Options::*, int>>& overrides, sq_handle_t* out) {
-    const auto t_create = std::chrono::steady_clock::now();
-    if (!db || !out || n <= 0 || d <= 0) return fail(SQ_ERR_INVALID, "sq_dense_create: bad argument");
-    if (metric != SQ_METRIC_L2 && metric != SQ_METRIC_COSINE)
-        return fail(SQ_ERR_INVALID, "sq_dense_create: unknown metric %d", metric);
-    if (n >= (1ll << 32)) return fail(SQ_ERR_UNSUPPORTED, "sq_dense_create: more than 2^32-1 rows per shard");
-    if (mem == SQ_MEM_DEVICE && ((reinterpret_cast<uintptr_t>(db) & 15u) != 0 || (d & 3) != 0))
-        return fail(SQ_ERR_UNSUPPORTED,
-                    "sq_dense_create: a borrowed device matrix must be 16-byte aligned with d %% 4 == 0 (d=%d)", d);
-    const int d_pad = (d + KT - 1) / KT * KT;
-    auto h = std::make_unique<DenseHandle>();
-    h->kind = H_DENSE;
-    h->n = n;
-    h->n_live = n;
-    h->n_pad = (n + TILE_ROWS - 1) / TILE_ROWS * TILE_ROWS;
-    h->d = d;
-    h->d_pad = d_pad;
-    h->metric = metric;
-    h->id_base = id_base;
-    h->overrides = overrides;   // (create-time choices -- "dense_int8" = 0: no int8 copy -- are the handle's own)
-    h->refresh_options();
-    if (hipGetDevice(&h->device) != hipSuccess) return fail(SQ_ERR_HIP, "sq_dense_create: no HIP device");
-    if (mem == SQ_MEM_DEVICE) {
-        h->db = db;
-        h->ld = d;
-    } else {
-        // owned float32 copy, rows padded to a multiple of 4 floats so the exact kernel can use 16-byte loads
-        const int ldo = (d + 3) / 4 * 4;
-        const size_t bytes = (size_t)n * ldo * 4;
-        SQ_TRY(h->owned.reserve(bytes));
-        hipError_t e;
-        if (ldo == d) {
-            e = hipMemcpy(h->owned.p, db, bytes, hipMemcpyHostToDevice);
-        } else {
-            e = hipMemset(h->owned.p, 0, bytes);
-            if (e == hipSuccess)
-                e = hipMemcpy2D(h->owned.p, (size_t)ldo * 4, db, (size_t)d * 4, (size_t)d * 4, (size_t)n,
-                                hipMemcpyHostToDevice);
-        }
-        if (e != hipSuccess) return fail(SQ_ERR_HIP, "sq_dense_create: H2D copy failed: %s", hipGetErrorString(e));
-        h->db = h->owned.as<float>();
-        h->ld = ldo;
-    }
-    SQ_TRY(dense_build_all(h.get()));
-    h->build_us = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t_create).count();
-    *out = register_handle(h.release());
-    return SQ_OK;
-}
-
 extern "C" int sq_dense_append(sq_handle_t hid, const float* rows, int64_t n_add, int mem) {
     auto* h = static_cast<DenseHandle*>(lookup_handle(hid, H_DENSE));
     if (!h) return fail(SQ_ERR_INVALID, "sq_dense_append: unknown handle");
@@ -2047,7 +1989,6 @@ extern "C" int sq_dense_append(sq_handle_t hid, const float* rows, int64_t n_add
     SQ_TRY(dense_sync_all(h));
     const long long n_old = h->n, n_new = n_old + n_add;
     if (n_new >= (1ll << 32)) return fail(SQ_ERR_UNSUPPORTED, "sq_dense_append: more than 2^32-1 rows per shard");
-    SQ_HIP(hipSetDevice(h->device));
     SQ_TRY(dense_grow(h, n_new));
     if (h->dead.p) {   // the bitmap of removed rows follows the matrix (new rows are live; holes are not reused)
         const long long words = (n_new + 31) / 32;
@@ -2055,18 +1996,8 @@ extern "C" int sq_dense_append(sq_handle_t hid, const float* rows, int64_t n_add
         SQ_HIP(hipMemset(h->dead.as<u32>() + h->dead_words, 0, h->dead.cap - (size_t)h->dead_words * 4));
         h->dead_words = words;
     }
-    float* dst = h->owned.as<float>() + n_old * h->ld;
-    const hipMemcpyKind kind = mem == SQ_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    hipError_t e;
-    if (h->ld == h->d) {
-        e = hipMemcpy(dst, rows, (size_t)n_add * h->d * 4, kind);
-    } else {
-        e = hipMemset(dst, 0, (size_t)n_add * h->ld * 4);
-        if (e == hipSuccess) e = hipMemcpy2D(dst, (size_t)h->ld * 4, rows, (size_t)h->d * 4, (size_t)h->d * 4, (size_t)n_add, kind);
-    }
-    if (e != hipSuccess) return fail(SQ_ERR_HIP, "sq_dense_append: copy failed: %s", hipGetErrorString(e));
-    h->n = n_new;
-    h->n_pad = (n_new + TILE_ROWS - 1) / TILE_ROWS * TILE_ROWS;
+    SQ_TRY(dense_upload_rows(h->owned.as<float>() + n_old * h->ld, h->ld, rows, n_add, h->d, mem == SQ_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
+    dense_set_rows(h, n_new);
     // the tile the old rows ended in is rebuilt together with the new ones (its padding rows become real rows)
     h->n_live += n_add;
     SQ_TRY(dense_build_rows(h, n_old / TILE_ROWS * TILE_ROWS));
@@ -2170,9 +2101,8 @@ extern "C" int sq_dense_compact(sq_handle_t hid, int64_t* old_to_new) {
     DevBuf prefix, total, map, fresh_rows, bounce;
     if (const int rc = prefix.reserve((size_t)words * 8)) return rc;
     if (const int rc = total.reserve(8)) return rc;
-    if (const int rc = launch<dense_compact_scan_kernel>(dim3(1), dim3(1024), 0, nullptr, h->deadp(), n_old, words, prefix.as<unsigned long long>(),
-                                                         total.as<unsigned long long>()))
-        return rc;
+    SQ_TRY(launch<dense_compact_scan_kernel>(dim3(1), dim3(1024), 0, nullptr, h->deadp(), n_old, words, prefix.as<unsigned long long>(),
+                                             total.as<unsigned long long>()));
     unsigned long long live_dev = 0;
     if (hipMemcpy(&live_dev, total.p, 8, hipMemcpyDeviceToHost) != hipSuccess)
         return fail(SQ_ERR_HIP, "sq_dense_compact: %s", hipGetErrorString(hipGetLastError()));
@@ -2180,17 +2110,15 @@ extern "C" int sq_dense_compact(sq_handle_t hid, int64_t* old_to_new) {
     if (live != h->n_live) return fail(SQ_ERR_INTERNAL, "sq_dense_compact: the bitmap holds %lld live rows, the handle counts %lld", live, h->n_live);
     if (old_to_new) {   // before anything changes: a failure here leaves the index as it was
         if (const int rc = map.reserve((size_t)n_old * 8)) return rc;
-        if (const int rc = launch<dense_compact_map_kernel>(dim3((unsigned)((n_old + 255) / 256)), dim3(256), 0, nullptr, h->deadp(),
-                                                            prefix.as<unsigned long long>(), n_old, h->id_base, map.as<long long>()))
-            return rc;
+        SQ_TRY(launch<dense_compact_map_kernel>(dim3((unsigned)((n_old + 255) / 256)), dim3(256), 0, nullptr, h->deadp(), prefix.as<unsigned long long>(),
+                                                n_old, h->id_base, map.as<long long>()));
         if (hipMemcpy(old_to_new, map.p, (size_t)n_old * 8, hipMemcpyDeviceToHost) != hipSuccess)
             return fail(SQ_ERR_HIP, "sq_dense_compact: %s", hipGetErrorString(hipGetLastError()));
         map.release();   // (now: the gather below wants the room)
     }
     // every copy derived from the rows is rebuilt below: their memory goes first, so that the gather finds room
-    for (DevBuf* b : {&h->scan, &h->scan8, &h->nrow8, &h->norms, &h->norms1, &h->cos_nx, &h->center, &h->mid_cos_center, &h->mid_cos_rows})
-        b->release();
-    h->use8 = false;
+    for (DevBuf* b : {&h->scan, &h->norms, &h->norms1, &h->cos_nx, &h->center, &h->mid_cos_center, &h->mid_cos_rows}) b->release();
+    h->i8.drop();
     const size_t row_bytes = (size_t)h->ld * 4;
     // rows of one gather launch: its grid stays below 2^30 workgroups
     const long long launch_rows = std::max<long long>(32, ((1ll << 30) * 256 / cpr) / 32 * 32);
@@ -2225,21 +2153,12 @@ extern "C" int sq_dense_compact(sq_handle_t hid, int64_t* old_to_new) {
         if (hipDeviceSynchronize() != hipSuccess) return fail(SQ_ERR_HIP, "sq_dense_compact: gather failed: %s", hipGetErrorString(hipGetLastError()));
     }
     h->db = h->owned.as<float>();
-    h->n = h->n_live = live;
-    h->n_pad = (live + TILE_ROWS - 1) / TILE_ROWS * TILE_ROWS;
+    dense_set_rows(h, live);
+    h->n_live = live;
     h->dead.release();
     h->dead_words = 0;
     // the index sq_dense_create would build from these rows: origin, statistics, scan copies, filter state
-    h->xn2_max = 0.0;
-    h->mid_cos_n = -1;
-    h->overflow16 = 0;
-    h->first_suspended = false;
-    h->direct_calls = 0;
-    h->probe_interval = 16;
-    for (auto& sl : h->slot) {   // captured call graphs hold the old shape and the old buffers
-        if (sl.gexec) (void)hipGraphExecDestroy(sl.gexec), sl.gexec = nullptr;
-        sl.gkey = sl.seen_key = 0;
-    }
+    h->reset_filter_state();
     return dense_build_all(h);
 }
 

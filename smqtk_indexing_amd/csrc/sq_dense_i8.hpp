@@ -29,6 +29,7 @@
 // side so that the ds_read_b128 of a fragment (lane = row, 16 consecutive k) is conflict-free (wider rows: I8Geom, i8_swz).  One 16-byte read feeds one MFMA
 // (K = 32) per query plane: four reads and eight MFMAs per tile, against eight and sixteen in the bf16 kernel.
 #pragma once
+#include "sq_dense_i8_policy.hpp"
 #include "sq_dense_scan.hpp"
 
 namespace sq {
@@ -117,12 +118,7 @@ static __global__ __launch_bounds__(256) void dense8_energy_kernel(const float* 
 // of what rounding alone leaves, Dx sqrt(d / 12) -- not of the measured mean, which a few wild rows would own.  A narrow
 // clamp has the finer step but cuts more elements off; the host takes the pair with the least bound R that leaves no
 // more than a few hundred rows beyond it.
-static constexpr int I8_NCLIP = 12, I8_NCUT = 10;
-struct Dense8ClipArgs {
-    float inv_dx[I8_NCLIP], dx[I8_NCLIP];
-    float cut[I8_NCLIP][I8_NCUT];   // r_row^2 thresholds
-};
-
+// (the candidates, Dense8ClipArgs and the host's choice: sq_dense_i8_policy.hpp)
 template <int EPL>
 static __global__ __launch_bounds__(256) void dense8_clip_stats_kernel(const float* __restrict__ db, long long n, long long ld, int d,
                                                                         const float* __restrict__ center, const double* __restrict__ nx64,

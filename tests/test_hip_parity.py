@@ -399,6 +399,35 @@ def test_dense_int8_copy_follows_appends(metric):
     idx.close()
 
 
+def test_dense_int8_copy_declined_keeps_no_memory():
+    """A build that declines leaves no int8 copy behind.  70 001 rows that all equal one vector: minus their column means
+    they are exactly zero, the element rms is 0 and no clamp can be chosen -- the index reports no bytes for the copy and
+    answers from the later stages.  Appending as many Gaussian rows doubles it: a build is attempted again over all the
+    rows, and whatever it decides, the index holds memory for the copy exactly when it uses one."""
+    rng = np.random.default_rng(77)
+    n, d, k = 70_001, 32, 5
+    db = np.tile(rng.standard_normal(d).astype(np.float32), (n, 1))
+    qs = rng.standard_normal((3, d)).astype(np.float32)
+
+    def check(idx, rows):
+        dd, ii = idx.search(qs, k)
+        for qi in range(len(qs)):
+            rd, ri = O.dense_topk(rows, qs[qi], k)
+            np.testing.assert_array_equal(ii[qi], ri)
+            np.testing.assert_array_equal(dd[qi].view(np.uint32), rd.view(np.uint32))
+
+    idx = _lib.DenseIndex(db)
+    info = idx.info()
+    assert info["int8_copy_bytes"] == 0 and not info["int8_in_use"], info
+    check(idx, db)
+    more = rng.standard_normal((n, d)).astype(np.float32)
+    idx.append(more)
+    check(idx, np.concatenate([db, more]))
+    info = idx.info()
+    assert (info["int8_copy_bytes"] > 0) == info["int8_in_use"], info
+    idx.close()
+
+
 @pytest.mark.parametrize("d,family", [(128, "long_query"), (64, "two_clusters"), (256, "long_query"), (512, "mixed"), (128, "mixed"),
                                       (100, "two_clusters"), (300, "mixed"), (36, "long_query")])   # (rows with a partial last unit)
 def test_dense_middle_tier_certifies_what_the_bf16_filter_cannot(d, family):
