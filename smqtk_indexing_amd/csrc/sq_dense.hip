@@ -1460,12 +1460,16 @@ static int dense_exact_path(DenseHandle* h, DenseSlot& s, const DenseCtx& e, con
     long long fb_stride = std::min<long long>(64, std::min<long long>((long long)e.cap / (4ll * e.kk), n / (8ll * e.kk)));
     if (n < 65536 || fb_stride < 2 || (h->opt.dense_debug & 128)) fb_stride = 0;  // debug 128: measurement, full select
     const long long fb_ns = fb_stride ? (n + fb_stride - 1) / fb_stride : 0;
-    // group size: the key arrays of a group stay under 4 GB; rows beyond the group kernel's depth go one by one
-    int gmax = (int)std::min<long long>(EXACT_GROUP, std::max<long long>(1, (4ll << 30) / (n * (long long)e.key_bytes)));
-    if (d > (128 << EXACT_GROUP_DEPTH) || (h->opt.dense_debug & 256)) gmax = 1;    // debug 256: measurement, one query per pass
+    // The group kernel takes a row width when its eight staged queries fit the LDS (round_up(d, 4) <= 5112) and the
+    // row's summation tree fits the kernel's fixed depth (every width the LDS admits does; the rule is the tree's depth,
+    // not d <= 128 << depth: 8191 elements need 7 levels).  Every other width goes one query per pass.
     const size_t grp_lds = (size_t)EXACT_GROUP * ((d + 3) / 4 * 4) * 4;
     constexpr int grp_lds_max = 160 * 1024 - 256;   // (the attribute is set once per device: the largest group any index asks for)
-    const bool grp_ok = grp_lds <= (size_t)grp_lds_max && d <= (128 << EXACT_GROUP_DEPTH);
+    const bool grp_ok = grp_lds <= (size_t)grp_lds_max && pw_tree_depth(d) <= EXACT_GROUP_DEPTH;
+    // group size: the key arrays of a group stay under 4 GB; debug 256: measurement, one query per pass
+    int gmax = 1;
+    if (grp_ok && !(h->opt.dense_debug & 256))
+        gmax = (int)std::min<long long>(EXACT_GROUP, std::max<long long>(1, (4ll << 30) / (n * (long long)e.key_bytes)));
     // the exact path keeps its own per-query counters: the slot's belong to a call that may still be in flight
     // when another asynchronous call's queries are redone
     SQ_TRY(h->fb_cnt.reserve((size_t)(c.nq + 64) * 4));
@@ -1500,7 +1504,7 @@ static int dense_exact_path(DenseHandle* h, DenseSlot& s, const DenseCtx& e, con
                 SQ_TRY(launch_lds<dense_exact_group_kernel<M::cosine, K>>(grp_lds_max, dim3(gx), dim3(256), grp_lds, st, h->db, h->ld, d, c.q, grp, n, big,
                                                                           fb_sample, fb_ns, (int)fb_stride, M::cosine ? cnx : nullptr,
                                                                           M::cosine ? e.cnq : nullptr, deadp));
-            } else {  // one query per pass (gmax == 1 here)
+            } else {  // one query per pass (!grp_ok makes gmax 1: gn == 1)
                 const int qi = grp.idx[0];
                 if constexpr (M::cosine)
                     SQ_TRY(launch<dense_exact_cos_kernel>(dim3(gx, 1), dim3(256), 0, st, h->db, h->ld, d, c.q + (long long)qi * d, nullptr, full_cnt + qi,

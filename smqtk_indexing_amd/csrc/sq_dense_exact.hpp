@@ -272,7 +272,7 @@ static __global__ __launch_bounds__(256) void dense_exact_cos_kernel(const float
 // keys: [G][n]; sample: [G][ns] (every sample_stride-th distance, see dense_compact_keys_kernel) or null.
 // Dynamic LDS: G * round_up(d, 4) floats.  Rows 16-byte aligned.
 static constexpr int EXACT_GROUP = 8;
-static constexpr int EXACT_GROUP_DEPTH = 6;  // rows up to 128 * 2^6 = 8192 elements
+// (EXACT_GROUP_DEPTH = 6, sq_pairwise.hpp: the rows this kernel takes are those with pw_tree_depth(d) <= 6)
 struct ExactGroup {
     int idx[EXACT_GROUP];  // query indices of the group (unused slots repeat the first)
     int count;

@@ -11,6 +11,12 @@
 // so reproducing the order makes float results bit identical.  The scalar
 // restatement that pins this is oracle/cpu_ref.py:np_pairwise_sum_f32.
 //
+// The depth of that tree is NOT ceil(log2(n / 128)): the right part of a split is n - split, which exceeds n / 2 whenever
+// n / 2 is no multiple of 8 (and whenever n is odd), and the excess accumulates down the right spine.  n = 8191 splits
+// into right parts of 4103, 2055, 1031, 519, 263, 135 and 71 elements: depth 7, where 8192 needs 6.  Up to 8192 elements
+// 441 widths need depth 7, all of them in 7689 .. 8191; pw_tree_depth() below is the rule, and what a fixed-depth
+// walk (pw_tree_multi) may be given is decided by it, never by comparing n with 128 << depth.
+//
 // An aligned group of 8 lanes calls these together; lane j8 owns accumulator
 // r[j8]; every lane of the group returns the same value.  `term(i)` yields
 // element i already rounded to T.  No FMA contraction anywhere.
@@ -47,14 +53,29 @@ __device__ __forceinline__ T pw_leaf(F& term, int off, int n, int j8) {
 // leaf).  Pending left sums sit in a 12-deep shift register of scalars with
 // static indices, so everything stays in a handful of VGPRs (an indexed stack
 // of (offset, size, state, sum) cost ~100 registers or scratch and held the
-// kernels that use this at one wave per SIMD).  Depth 12: n <= 128 * 2^12.
+// kernels that use this at one wave per SIMD).  Depth 12: a buffer of 8192 elements or fewer
+// needs 7 at the most (pw_tree_depth; tests/host/pairwise_main.cpp walks every width).
 static constexpr int PW_MAX_DEPTH = 12;
 static constexpr int PW_MAX_N = 128 << PW_MAX_DEPTH;
 
-__device__ __forceinline__ int pw_split(int m) {
-    int m2 = m / 2;
+__host__ __device__ constexpr __forceinline__ int pw_split(int m) {
+    const int m2 = m / 2;
     return m2 - (m2 % 8);
 }
+
+// The deepest path of the split tree of n elements of one buffer (0: n is a single leaf).  Host and device, and a
+// constant expression: it sizes and guards the fixed-depth walks.
+__host__ __device__ constexpr int pw_tree_depth(int n) {
+    if (n <= 128) return 0;
+    const int l = pw_tree_depth(pw_split(n)), r = pw_tree_depth(n - pw_split(n));
+    return 1 + (l > r ? l : r);
+}
+static_assert(pw_tree_depth(128) == 0 && pw_tree_depth(129) == 1 && pw_tree_depth(8192) == 6 && pw_tree_depth(8191) == 7, "numpy's split rule");
+
+// The depth of the exact path's group walk (dense_exact_group_kernel, sq_dense_exact.hpp: pw_tree_multi with 8 sums
+// per level in registers).  It takes rows with pw_tree_depth(d) <= 6: every width up to 7688, and 7751 of the 8192
+// widths up to 8192 -- not "rows up to 128 * 2^6 elements".
+static constexpr int EXACT_GROUP_DEPTH = 6;
 
 // numpy's add-reduce walks an array through its iterator's buffer: NPY_BUFSIZE = 8192 elements at a time, each buffer
 // summed pairwise as above and the buffers' sums added in order -- np.sum of 8300 float32 values is
@@ -120,7 +141,8 @@ __device__ __forceinline__ T pw_tree_buffer(L&& leaf0, const int base, const int
 }
 
 // The same walk for G sums that share their leaves' inputs (G queries against one row): `leaf(off, n, v)`
-// fills the G leaf sums, the pending left sums are G shift registers of depth D (n <= 128 * 2^D).
+// fills the G leaf sums, the pending left sums are G shift registers of depth D.  The caller guarantees
+// pw_tree_depth(n) <= D: a deeper tree pushes its root's left sum out of the register and the result is wrong.
 template <class T, int G, int D, class L>
 __device__ __forceinline__ void pw_tree_multi(L&& leaf, int n, T (&out)[G]) {
     if (n <= 128) {

@@ -1,10 +1,23 @@
-// Stand-in for <hip/hip_runtime.h>, for tests/host/buffers_main.cpp only: the allocation, free and copy calls that
+// Stand-in for <hip/hip_runtime.h>, for the host programs of tests/host only: the allocation, free and copy calls that
 // smqtk_indexing_amd/csrc/sq_buffers.hpp uses, on malloc / free / memcpy, so that the owning buffer types run on a CPU
 // under the host sanitizers.  "Device" and pinned memory are plain heap blocks; every copy is done when it returns.
+// For smqtk_indexing_amd/csrc/sq_pairwise.hpp (tests/host/pairwise_main.cpp): the function qualifiers as nothing, the
+// round-to-nearest adds as plain adds (the programs are compiled with -ffp-contract=off), and a cross-lane exchange
+// that only has to compile -- the eight-lane leaf that uses it is not instantiated on a host.
 #pragma once
 #include <cstddef>
 #include <cstdlib>
 #include <cstring>
+
+#define __host__
+#define __device__
+#define __forceinline__ inline
+inline float __fadd_rn(float a, float b) { return a + b; }
+inline double __dadd_rn(double a, double b) { return a + b; }
+template <class T>
+inline T __shfl_xor(T, int) {
+    abort();   // one thread has no neighbouring lanes
+}
 
 typedef int hipError_t;
 enum : int { hipSuccess = 0, hipErrorInvalidValue = 1, hipErrorOutOfMemory = 2 };
