@@ -438,6 +438,13 @@ int sq_lsh_query(sq_handle_t rows, sq_handle_t hamming, sq_handle_t itq, const v
                  int n_codes_wanted, int metric, int k_out, void* out_dist, int64_t* out_rows, int mem, void* stream);
 int sq_rows_destroy(sq_handle_t h);
 
+/* -------------------------------------------------------------- IVF-Flat
+ * The inverted-list index (sq_ivf_*: k-means training, lists, probed-list scan) is an extension library of its own,
+ * libsmqtk_hip_ivf.so, declared in include/smqtk_hip_ivf.h.  It is built from csrc/sq_ivf.hip on top of this library --
+ * its coarse index is a dense index of this ABI, its handles live in this library's registry, so sq_get_stats,
+ * sq_handle_set_option (option "ivf_key_budget_mb") and sq_last_error serve them -- and this library's own set of
+ * entry points stays as it is. */
+
 /* ----------------------------------------------------------------- merge
  * Host-side k-way merge of per-shard top-k lists after the RCCL all-gather
  * (BASELINE.json north_star; no reference counterpart: the reference is

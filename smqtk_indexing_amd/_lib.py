@@ -37,6 +37,8 @@ SQ_MAX_K = 16384
 SQ_ITQFIT_MAX_D = 8192      # sq_itqfit_*: widest descriptor / longest code the device fit takes (smqtk_hip.h)
 SQ_ITQFIT_MAX_BITS = 256
 SQ_HAMMING_PLAN_FIELDS = 8  # words of the plan report of sq_hamming_search (smqtk_hip.h)
+SQ_IVF_INFO_FIELDS = 10     # words of sq_ivf_info (smqtk_hip_ivf.h)
+SQ_IVF_MAX_LISTS = 65536    # lists an IVF index may have: its coarse index answers from exact keys of every centroid
 
 LIB_NAME = "libsmqtk_hip.so"
 # SMQTK_HIP_LIBRARY: another build of the same library (measurement: kernel variants side by side)
@@ -55,6 +57,12 @@ EXPORTS = (
     "sq_itqfit_create", "sq_itqfit_set_mean", "sq_itqfit_cov", "sq_itqfit_project", "sq_itqfit_iterate",
     "sq_itqfit_destroy",
 )
+
+# The IVF-Flat extension library (include/smqtk_hip_ivf.h), beside the main one: built on top of it, with entry points of
+# its own -- the main library's set above stays as it is.
+IVF_LIB_NAME = "libsmqtk_hip_ivf.so"
+IVF_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), IVF_LIB_NAME)
+IVF_EXPORTS = ("sq_ivf_kmeans", "sq_ivf_create", "sq_ivf_add", "sq_ivf_lists", "sq_ivf_info", "sq_ivf_search", "sq_ivf_destroy")
 
 
 class HipError(RuntimeError):
@@ -174,6 +182,36 @@ def load() -> ctypes.CDLL:
         return _lib
 
 
+_ivf_lib: Optional[ctypes.CDLL] = None
+
+
+def load_ivf() -> ctypes.CDLL:
+    """Load the IVF-Flat extension library (once), after the main library it is built on.  Raises HipError when it is
+    missing: there is no fallback."""
+    global _ivf_lib
+    load()
+    with _lock:
+        if _ivf_lib is None:
+            if not os.path.isfile(IVF_LIB_PATH):
+                raise HipError(f"{IVF_LIB_NAME} not found at {IVF_LIB_PATH}; build it with `make -C smqtk_indexing_amd/csrc`")
+            try:
+                lib = ctypes.CDLL(IVF_LIB_PATH)
+            except OSError as ex:
+                raise HipError(f"cannot load {IVF_LIB_PATH}: {ex}") from ex
+            c_int, c_i64, c_vp = ctypes.c_int, ctypes.c_int64, ctypes.c_void_p
+            lib.sq_ivf_kmeans.argtypes = [c_vp, c_i64, c_int, c_vp, c_int, c_int, c_int]
+            lib.sq_ivf_create.argtypes = [c_vp, c_int, c_int, c_int, c_i64, ctypes.POINTER(c_i64)]
+            lib.sq_ivf_add.argtypes = [c_i64, c_vp, c_i64, c_int]
+            lib.sq_ivf_lists.argtypes = [c_i64, c_vp, c_vp]
+            lib.sq_ivf_info.argtypes = [c_i64, ctypes.POINTER(c_i64), c_int]
+            lib.sq_ivf_search.argtypes = [c_i64, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_int, c_vp]
+            lib.sq_ivf_destroy.argtypes = [c_i64]
+            for name in IVF_EXPORTS:
+                getattr(lib, name).restype = c_int
+            _ivf_lib = lib
+        return _ivf_lib
+
+
 def _check(rc: int, what: str) -> None:
     if rc != SQ_OK:
         msg = load().sq_last_error()
@@ -199,6 +237,11 @@ def device_count() -> int:
 
 def usable() -> bool:
     return device_count() > 0
+
+
+def ivf_usable() -> bool:
+    """A GPU, the main library and the IVF-Flat extension library beside it."""
+    return usable() and os.path.isfile(IVF_LIB_PATH)
 
 
 def device_name(device: int = 0) -> Tuple[str, int, int]:
@@ -562,6 +605,99 @@ class DenseIndex(_Handle):
     def sync(self) -> None:
         """Finish every asynchronous search in flight (``sq_dense_sync``)."""
         _check(load().sq_dense_sync(self.handle), "sq_dense_sync")
+
+
+def ivf_kmeans(x: np.ndarray, centroids: np.ndarray, iters: int = 10) -> np.ndarray:
+    """``sq_ivf_kmeans``: ``iters`` Lloyd iterations over the rows of ``x`` (``[n, d]`` float32, host) from the initial
+    ``centroids`` (``[nlist, d]``); returns the trained centroids (float32).  Deterministic: the same inputs give the
+    same bits.  An empty list keeps its centroid."""
+    x = _host(x, np.float32)
+    c = np.array(centroids, dtype=np.float32, order="C", copy=True)
+    if x.ndim != 2 or c.ndim != 2 or c.shape[1] != x.shape[1]:
+        raise ValueError("x must be [n, d] and centroids [nlist, d]")
+    _check(load_ivf().sq_ivf_kmeans(_ptr(x), int(x.shape[0]), int(x.shape[1]), _ptr(c), int(c.shape[0]), int(iters), SQ_MEM_HOST),
+           "sq_ivf_kmeans")
+    return c
+
+
+class IvfIndex(_Handle):
+    """Inverted lists over float32 rows (``sq_ivf_*``): rows in the list of their nearest centroid, a search scans the
+    lists of the ``nprobe`` nearest centroids exactly.  L2 only.  Use as a context manager or ``close()`` it."""
+    _destroy_name = "sq_ivf_destroy"
+
+    def close(self) -> None:
+        if self.handle:
+            h, self.handle = self.handle, 0
+            try:
+                load_ivf().sq_ivf_destroy(h)
+            except Exception:
+                pass
+    INFO_FIELDS = ("rows", "d", "nlist", "longest_list", "empty_lists", "rows_bytes", "ids_offsets_bytes", "coarse_bytes",
+                   "add_us", "key_budget_bytes")
+
+    def __init__(self, centroids: np.ndarray, id_base: int = 0, metric: int = SQ_METRIC_L2):
+        super().__init__()
+        c = _host(centroids, np.float32)
+        if c.ndim != 2:
+            raise ValueError("centroids must be float32[nlist, d]")
+        self.nlist, self.d, self.id_base, self.n = int(c.shape[0]), int(c.shape[1]), int(id_base), 0
+        h = ctypes.c_int64(0)
+        _check(load_ivf().sq_ivf_create(_ptr(c), self.nlist, self.d, int(metric), self.id_base, ctypes.byref(h)), "sq_ivf_create")
+        self.handle = int(h.value)
+
+    def __enter__(self) -> "IvfIndex":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+    def add(self, rows, n: Optional[int] = None, device_ptr: bool = False) -> None:
+        """Rows (``[m, d]`` float32 host array, or a device pointer + ``n``) into their lists; they get the next
+        insertion numbers (``sq_ivf_add``)."""
+        if device_ptr:
+            assert n is not None
+            ptr, mem, m = _ptr(rows), SQ_MEM_DEVICE, int(n)
+        else:
+            rows = _host(rows, np.float32)
+            if rows.ndim != 2 or rows.shape[1] != self.d:
+                raise ValueError("rows must be float32[m, d]")
+            ptr, mem, m = _ptr(rows), SQ_MEM_HOST, int(rows.shape[0])
+        if m == 0:
+            return
+        _check(load_ivf().sq_ivf_add(self.handle, ptr, m, mem), "sq_ivf_add")
+        self.n += m
+
+    def search(self, queries: np.ndarray, k: int, nprobe: int = 1) -> Tuple[np.ndarray, np.ndarray]:
+        """(dist float32 ``[nq, k]``, ids int64 ``[nq, k]``) of the ``k`` nearest rows among the lists of the
+        ``nprobe`` nearest centroids; ``-1`` / ``+inf`` behind the last candidate."""
+        q = _host(queries, np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        if q.shape[1] != self.d:
+            raise ValueError("query dimension does not match the index")
+        nq = q.shape[0]
+        dist = np.empty((nq, k), dtype=np.float32)
+        idx = np.empty((nq, k), dtype=np.int64)
+        _check(load_ivf().sq_ivf_search(self.handle, _ptr(q), nq, int(k), int(nprobe), _ptr(dist), _ptr(idx), SQ_MEM_HOST, None),
+               "sq_ivf_search")
+        return dist, idx
+
+    def search_device(self, q_ptr: int, nq: int, k: int, nprobe: int, out_dist_ptr: int, out_idx_ptr: int, stream: int = 0) -> None:
+        """Device pointers throughout; blocking, as :meth:`search`."""
+        _check(load_ivf().sq_ivf_search(self.handle, _ptr(q_ptr), int(nq), int(k), int(nprobe), _ptr(out_dist_ptr), _ptr(out_idx_ptr),
+                                    SQ_MEM_DEVICE, ctypes.c_void_p(stream or None)), "sq_ivf_search")
+
+    def lists(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(``list_off[nlist + 1]``, ids of all rows list by list) -- ``sq_ivf_lists``."""
+        off = np.empty(self.nlist + 1, dtype=np.int64)
+        ids = np.empty(self.n, dtype=np.int64)
+        _check(load_ivf().sq_ivf_lists(self.handle, _ptr(off), _ptr(ids) if self.n else None), "sq_ivf_lists")
+        return off, ids
+
+    def info(self) -> dict:
+        out = (ctypes.c_int64 * SQ_IVF_INFO_FIELDS)()
+        _check(load_ivf().sq_ivf_info(self.handle, out, SQ_IVF_INFO_FIELDS), "sq_ivf_info")
+        return dict(zip(self.INFO_FIELDS, (int(v) for v in out)))
 
 
 def dense_distances(query: np.ndarray, rows: np.ndarray, metric: int = SQ_METRIC_L2) -> np.ndarray:

@@ -63,6 +63,7 @@ struct Options {
     int hamming_async_order = 1; // as dense_async_order
     int hamming_ring = -1;       // Hamming stream kernel: -1 = automatic (LDS-DMA ring for arrays beyond the MALL), 0 = register loads, 1 = ring (1 .. 7, 8, 16 words, 16-byte aligned arrays; the register kernel otherwise)
     int hamming_tighten = 1;     // fused Hamming searches: stream threshold from a lower sample rank than k (far fewer candidates); a bet the pick kernel checks -- a lost one redoes the call with the safe rule; 0 = the safe rank-k rule
+    int ivf_key_budget_mb = 0;   // IVF search: MB of key scratch a call may hold -- a batch runs in query slices under it (0 = 256; sq_ivf_plan.hpp)
     int hamming_fused = 1;       // Hamming searches of up to 32 queries (64 .. 448-bit codes, k <= 2048) as three launches (head: sampled histogram + thresholds by the last workgroup; stream; pick: exact k-th distance + gather + sort per query) instead of a memset and five; 0 = the general chain
 };
 extern Options g_opt;   // process-wide defaults (sq_set_option); a handle may override any of them (sq_handle_set_option)
@@ -96,7 +97,7 @@ inline hipError_t event_wait(hipEvent_t ev) {
 }
 
 // ------------------------------------------------------------------ handles
-enum HandleKind { H_HAMMING = 1, H_DENSE = 2, H_ROWS = 3, H_FIT = 4, H_ITQ = 5 };
+enum HandleKind { H_HAMMING = 1, H_DENSE = 2, H_ROWS = 3, H_FIT = 4, H_ITQ = 5, H_IVF = 6 };
 
 struct HandleBase {
     int kind = 0;

@@ -114,6 +114,7 @@ int Options::*option_member(const char* name) {
         {"hamming_ring", &Options::hamming_ring},
         {"hamming_fused", &Options::hamming_fused},
         {"hamming_tighten", &Options::hamming_tighten},
+        {"ivf_key_budget_mb", &Options::ivf_key_budget_mb},
     };
     if (!name) return nullptr;
     for (const auto& f : kFields)
@@ -131,7 +132,7 @@ extern "C" int sq_set_option(const char* name, int64_t value) {
 }
 
 static HandleBase* any_handle(sq_handle_t hid) {
-    for (int kind : {H_DENSE, H_HAMMING, H_ROWS, H_FIT, H_ITQ})
+    for (int kind : {H_DENSE, H_HAMMING, H_ROWS, H_FIT, H_ITQ, H_IVF})
         if (HandleBase* h = lookup_handle(hid, kind)) return h;
     return nullptr;
 }
@@ -173,6 +174,7 @@ extern "C" int sq_get_stats(sq_handle_t hid, sq_stats_t* out) {
     HandleBase* h = lookup_handle(hid, H_DENSE);
     if (!h) h = lookup_handle(hid, H_HAMMING);
     if (!h) h = lookup_handle(hid, H_ITQ);   // (the last sq_itq_model_hash: which path hashed the rows, smqtk_hip.h)
+    if (!h) h = lookup_handle(hid, H_IVF);   // (the last sq_ivf_search: slices, rows and bytes scanned)
     if (!h) return fail(SQ_ERR_INVALID, "sq_get_stats: unknown handle");
     std::lock_guard<std::mutex> l(h->mu);
     *out = h->stats;
