@@ -60,7 +60,12 @@ extern "C" {
  *                  handle or process-wide; a single query whose candidates alone exceed the budget still runs.
  *                  sq_get_stats: scan_launches (slices scanned), candidates (rows scanned, summed over queries),
  *                  bytes_scanned (candidates x row stride x 4), and with option "profile" scan_ms / total_ms.
- *                  An index with no rows answers with padding only. */
+ *                  An index with no rows answers with padding only.
+ *                  Limits, as run on an MI355X under ROCm's HIP runtime: the scan stages a query in round_up(d, 4) * 4
+ *                  bytes of dynamic LDS, so a row of more than 40960 floats (160 KiB) cannot be searched; the widest row
+ *                  tested is 16389 floats (65568 bytes, which a plain launch takes).  The queries of a slice are the
+ *                  second dimension of the scan's grid and nothing but the key budget bounds a slice; the runtime
+ *                  reports 65536 as that dimension's maximum, accepts more, and a slice of 70000 queries is tested. */
 #define SQ_IVF_INFO_FIELDS 10
 int sq_ivf_kmeans(const float* x, int64_t n, int d, float* centroids /* in: initial, out: trained */,
                   int nlist, int iters, int mem);

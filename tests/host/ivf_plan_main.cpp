@@ -1,8 +1,8 @@
 // The host arithmetic of the IVF-Flat index (smqtk_indexing_amd/csrc/sq_ivf_plan.hpp) on a CPU: compiled with
 // -fsanitize=address,undefined and run by tests/test_host_logic_ivf.py.  Checked here: the counting sort's offsets
 // against a direct stable sort; the scan's chunks covering every candidate once, through the same ivf_locate the kernel
-// calls, at list lengths 0, 1, chunk - 1, chunk and chunk + 1; slice sizes that keep the key scratch under the budget;
-// 64-bit products at 2^32 - 1 rows.
+// calls, at list lengths 0, 1, chunk - 1, chunk and chunk + 1; ivf_locate over prefix arrays of 65, 257 and 700 entries
+// with runs of empty lists; slice sizes that keep the key scratch under the budget; 64-bit products at 2^32 - 1 rows.
 #include "../../smqtk_indexing_amd/csrc/sq_ivf_plan.hpp"
 
 #include <algorithm>
@@ -96,6 +96,31 @@ static void chunks(const std::vector<long long>& sizes) {
         for (int v : h) CHECK(v == 1);
 }
 
+// A prefix array of np entries as a query probing more lists than a wave has lanes meets it: lists of 1 to 48 rows with
+// runs of empty ones (equal prefix values) at the front, across entries 63 / 64 and 255 / 256, at the end, and one
+// scattered in every 11.  Every position is located in the LAST list whose prefix is at or below it -- found here by
+// walking down from the end -- and that list is not empty.
+static void long_prefix(int np) {
+    std::vector<long long> sizes((size_t)np);
+    for (int j = 0; j < np; ++j) {
+        const bool empty = j < 3 || (j >= 62 && j <= 65) || (j >= 254 && j <= 257) || j >= np - 3 || rnd(11) == 0;
+        sizes[(size_t)j] = empty ? 0 : 1 + (long long)rnd(48);
+    }
+    std::vector<long long> pre((size_t)np + 1, 0);
+    for (int j = 0; j < np; ++j) pre[(size_t)j + 1] = pre[(size_t)j] + sizes[(size_t)j];
+    const long long total = pre[(size_t)np];
+    CHECK(total > 0 && pre[3] == 0 && pre[(size_t)np - 3] == total);
+    if (np > 66) CHECK(pre[62] == pre[66]);
+    if (np > 258) CHECK(pre[254] == pre[258]);
+    for (long long p = 0; p < total; ++p) {
+        int want = np - 1;
+        while (pre[(size_t)want] > p) --want;
+        const int j = ivf_locate(pre.data(), np, p);
+        CHECK(j == want && sizes[(size_t)j] > 0 && p - pre[(size_t)j] < sizes[(size_t)j]);
+    }
+    chunks(sizes);
+}
+
 static void slices() {
     const long long budget = kIvfKeyBudget;
     const long long ks[] = {1, 100, 16384, 16385, 30000, 1000000};
@@ -159,6 +184,8 @@ int main() {
                 chunks({a, b, c});
                 chunks({0, a, 0, 0, b, 4 * C + 3, c, 0});
             }
+    for (int np : {65, 257, 700})
+        for (int rep = 0; rep < 4; ++rep) long_prefix(np);
     slices();
     wide();
     printf("ivf plan ok: chunk=%d budget=%lld max_lists=%d\n", kIvfChunk, kIvfKeyBudget, kIvfMaxLists);

@@ -10,48 +10,22 @@ n % 8, leaves shorter than 8, trees whose right spine is deeper than their left,
 LDS or not), the 64-float staging stride of the cosine re-rank, the 160 KiB of LDS that hold the group kernel's eight
 queries (round_up(d, 4) <= 5112), the depth its walk is compiled for, and numpy's 8192-element buffers.
 
-WIDTHS is derived from those rules below, not typed in.  The reference everywhere is numpy and scipy on the same inputs
-(oracle/cpu_ref.py: euclidean_distance, cosine_distance, dense_distances, dense_topk).  L2: distances equal to the last
-bit, ids equal.  Cosine: rtol 1e-12, atol 1e-15, and where an id differs O.assert_topk_equivalent(rtol=1e-12) decides.
+WIDTHS is derived from those rules in tests/width_cases.py, not typed in.  The reference everywhere is numpy and scipy on
+the same inputs (oracle/cpu_ref.py: euclidean_distance, cosine_distance, dense_distances, dense_topk).  L2: distances
+equal to the last bit, ids equal.  Cosine: rtol 1e-12, atol 1e-15, and where an id differs
+O.assert_topk_equivalent(rtol=1e-12) decides.
 """
 import numpy as np
 import pytest
 
 from oracle import cpu_ref as O
 from smqtk_indexing_amd import _lib
+from tests.width_cases import BEYOND, BUF, EXTREMES, GROUP_LDS_EDGE, N_INDEX, WIDTHS, _depth, _split
 
 pytestmark = pytest.mark.gpu
 
 METRICS = {"euclidean": _lib.SQ_METRIC_L2, "cosine": _lib.SQ_METRIC_COSINE}
-BUF = 8192                                   # numpy's reduction buffer (sq_pairwise.hpp: PW_BUFSIZE)
-
-
-def _split(n):
-    return n // 2 - (n // 2) % 8
-
-
-def _depth(n):
-    return 0 if n <= 128 else 1 + max(_depth(_split(n)), _depth(n - _split(n)))
-
-
-def _depth_extremes():
-    """For each depth of the split tree of one buffer: the smallest and the largest width that has it."""
-    by_depth = {}
-    for n in range(129, BUF + 1):
-        by_depth.setdefault(_depth(n), []).append(n)
-    return {dep: (min(ns), max(ns)) for dep, ns in sorted(by_depth.items())}
-
-
-EXTREMES = _depth_extremes()
-GROUP_LDS_EDGE = (160 * 1024 - 256) // (8 * 4)           # 5112: eight staged queries of round_up(d, 4) floats fill the LDS
-WIDTHS = sorted(set(range(1, 18)) | set(range(120, 137))                                # tails, short leaves, the first split
-                | {153, 156, 157, 160}                                                  # ldq <= 156
-                | {255}                                                                 # a left leaf beside a right subtree
-                | {w for pair in EXTREMES.values() for w in pair}
-                | {GROUP_LDS_EDGE - 3, GROUP_LDS_EDGE, GROUP_LDS_EDGE + 1, GROUP_LDS_EDGE + 4, GROUP_LDS_EDGE + 5, 6000})
-BEYOND = (BUF + 1, BUF + 7, BUF + 8, 2 * BUF + 5)        # numpy's buffers: 8193, 8199, 8200, 16389
 K = 10
-N_INDEX = 33 * 32 - 7                                    # 1049 rows: the smallest shape tests/test_hip_scan_variants.py runs off the all-keys route
 NOISE = np.float32(1e-3)
 
 

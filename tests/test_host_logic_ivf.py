@@ -9,8 +9,8 @@ The host side of the IVF-Flat index, without a GPU.
 2. tests/host/ivf_plan_main.cpp over smqtk_indexing_amd/csrc/sq_ivf_plan.hpp (plain C++), compiled with ROCm's clang++
    under AddressSanitizer and UndefinedBehaviorSanitizer and linked statically against the sanitizer runtime: nothing is
    preloaded and nothing is loaded into Python.  It checks the counting sort's offsets against a direct sort, the scan's
-   chunks at list lengths 0, 1, chunk - 1, chunk, chunk + 1, the slice sizes under the key budget, and the 64-bit
-   products at 2^32 - 1 rows.
+   chunks at list lengths 0, 1, chunk - 1, chunk, chunk + 1, `ivf_locate` over prefix arrays of 65, 257 and 700 entries
+   with runs of empty lists, the slice sizes under the key budget, and the 64-bit products at 2^32 - 1 rows.
 """
 import math
 import os
