@@ -46,7 +46,7 @@ inline int fail(int code, const char* fmt, ...) {
 // one owns it -- a handle, a per-call slot or a function's locals need no list of what to free -- and release() is for
 // giving memory back early.
 
-// Device memory.  reserve() never shrinks and does not keep the contents (grow_keep does).
+// Device memory.  reserve() never shrinks and does not keep the contents (grow_keep does); alloc_exact() replaces it.
 struct DevBuf {
     void* p = nullptr;
     size_t cap = 0;
@@ -65,10 +65,11 @@ struct DevBuf {
     // (a local may go out of scope while a kernel that reads it is still queued -- an error return between a launch and
     // its wait: hipFree waits for the device first, which the explicit release() calls have always relied on)
     ~DevBuf() { release(); }
-    int reserve(size_t bytes) {
-        if (bytes <= cap) return SQ_OK;
+    int reserve(size_t bytes) { return bytes <= cap ? SQ_OK : alloc_exact(bytes + (bytes >> 3) + 256); }
+    // a new block of exactly `want` bytes (16 for none), whatever the buffer held: arrays that are replaced whole, not grown
+    int alloc_exact(size_t want) {
         release();
-        size_t want = bytes + (bytes >> 3) + 256;
+        if (want == 0) want = 16;
         hipError_t e = hipMalloc(&p, want);
         if (e != hipSuccess) {
             p = nullptr;

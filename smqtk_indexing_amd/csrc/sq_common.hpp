@@ -95,6 +95,9 @@ inline hipError_t stream_wait(hipStream_t st) {
 inline hipError_t event_wait(hipEvent_t ev) {
     return poll_then_block([ev] { return hipEventQuery(ev); }, [ev] { return hipEventSynchronize(ev); });
 }
+}  // namespace sq
+#include "sq_pipeline.hpp"   // the call slots' events and streams, the ring of slots, the host-memory call: they wait with the two above
+namespace sq {
 
 // ------------------------------------------------------------------ handles
 enum HandleKind { H_HAMMING = 1, H_DENSE = 2, H_ROWS = 3, H_FIT = 4, H_ITQ = 5, H_IVF = 6 };
@@ -124,6 +127,23 @@ struct HandleBase {
 sq_handle_t register_handle(HandleBase* h);
 HandleBase* lookup_handle(sq_handle_t id, int kind);
 HandleBase* remove_handle(sq_handle_t id, int kind);
+
+// The bodies of sq_*_sync / sq_*_destroy of a handle with pipelined calls: `drain(h)` finishes every call in flight; a null `h`: no such handle.
+template <class H, class Drain>
+inline int handle_sync(H* h, const char* who, Drain drain) {
+    if (!h) return fail(SQ_ERR_INVALID, "%s: unknown handle", who);
+    std::lock_guard<std::mutex> lock(h->mu);
+    h->refresh_options();
+    SQ_HIP(hipSetDevice(h->device));
+    return drain(h);
+}
+template <class H, class Drain>
+inline int handle_destroy(H* h, const char* who, Drain drain) {
+    if (!h) return fail(SQ_ERR_INVALID, "%s: unknown handle", who);
+    (void)handle_sync(h, who, drain);  // nothing of this handle is left on the device when its buffers go
+    delete h;
+    return SQ_OK;
+}
 
 inline int cu_count(int device) {
     static int cached[64] = {0};

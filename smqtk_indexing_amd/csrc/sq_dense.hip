@@ -26,7 +26,7 @@
 //      (or overflow their list) are redone on the exact full-keys path.
 //
 // Host driver: dense_enqueue chooses the stage that takes a call (dense_small_ / dense8_wide_ / dense8_ / dense_bf16_enqueue);
-// the chains end in dense_survivor_tail.  dense_resolve: dense_resolve_wait, dense_mid_tier, dense_exact_path.
+// the chains end in dense_survivor_tail.  dense_resolve: dense_resolve_wait, dense_mid_tier, dense_exact_path.  Slots: sq_pipeline.hpp.
 #include <algorithm>
 #include <type_traits>
 #include <vector>
@@ -43,10 +43,8 @@
 
 namespace sq {
 
-// Per-call workspace.  A synchronous search uses slot 0; asynchronous searches (SQ_MEM_DEVICE_ASYNC)
-// alternate between the two slots so that the kernels of call i + 1 are enqueued -- and, with the slots'
-// own streams, partly run -- while call i is still on the device; the status words of call i are read when
-// call i + 1 has been enqueued (dense_resolve).
+// Per-call workspace: the slots of the handle's CallRing (sq_pipeline.hpp has the rotation).  The kernels of call i + 1 are enqueued --
+// and, with the slots' own streams, partly run -- while call i is still on the device; dense_resolve reads a call's status words.
 struct DenseCall {
     bool pending = false;
     const float* q = nullptr;
@@ -74,20 +72,16 @@ struct DenseSlot {
     hipGraphExec_t gexec = nullptr;
     u64 gkey = 0, seen_key = 0;   // what gexec was captured for / the key of the slot's last eager call
     hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // call start, scan start, scan end, call end, re-rank end
-    hipEvent_t ev_in = nullptr, ev_done = nullptr;
-    hipStream_t own = nullptr;    // internal stream of the slot (asynchronous calls with "dense_async_streams" = 2)
+    SlotSync sync;                // the slot's internal stream (asynchronous calls with "dense_async_streams" = 2) and its ordering events (sq_pipeline.hpp)
     DenseCall call;
     void drop_graph() {   // (a captured call graph holds the index's shape and buffers: sq_dense_compact)
         if (gexec) (void)hipGraphExecDestroy(gexec), gexec = nullptr;
         gkey = seen_key = 0;
     }
-    ~DenseSlot() {   // (the buffers free themselves, after this body)
+    ~DenseSlot() {   // (the buffers and `sync` free themselves, after this body)
         drop_graph();
         for (auto& e : ev)
             if (e) (void)hipEventDestroy(e);
-        if (ev_in) (void)hipEventDestroy(ev_in);
-        if (ev_done) (void)hipEventDestroy(ev_done);
-        if (own) (void)hipStreamDestroy(own);
     }
 };
 
@@ -149,9 +143,7 @@ struct DenseHandle : HandleBase {
     const u32* deadp() const { return dead.as<u32>(); }
     DevBuf zeros;   // cosine: the 32 zero "norms" every tile of an AGPR-configuration scan starts from (norm_step 0)
     static constexpr int kMaxDepth = 6;
-    DenseSlot slot[kMaxDepth];
-    int depth = 2;                       // asynchronous calls in flight (option dense_async_depth, fixed while any is)
-    unsigned long long async_calls = 0;  // asynchronous calls so far (slot = calls % depth)
+    CallRing<DenseSlot, kMaxDepth> ring;   // the call slots (option dense_async_depth: 2 .. kMaxDepth in flight)
     // workspace shared by all calls: host-memory staging, the exact path (runs synchronously), index build
     DevBuf q_dev, out_dist_dev, out_idx_dev, big_keys, fb_sample, fb_keys, fb_out, scratch, fb_cnt, fb_sort;
     DevBuf mid_q, mid_planes, mid_small, mid_qal, mid_wave_out, mid_wave_cnt, mid_keys, mid_out, mid_sample;  // the middle tier (synchronous)
@@ -171,7 +163,7 @@ struct DenseHandle : HandleBase {
     void reset_filter_state() {
         xn2_max = 0.0, mid_cos_n = -1;
         overflow16 = 0, first_suspended = false, direct_calls = 0, probe_interval = 16;
-        for (auto& sl : slot) sl.drop_graph();
+        for (auto& sl : ring.slot) sl.drop_graph();
     }
     PinnedStage stage;
     hipEvent_t ev_ref = nullptr;   // SQ_TRACE (measurement aid): the origin of the printed call timelines
@@ -719,7 +711,7 @@ template <class Chain>
 static int dense8_launch_chain(DenseHandle* h, DenseSlot& s, std::initializer_list<u64> by_value, Chain&& chain) {
     const DenseCall& c = s.call;
     hipStream_t st = c.st;
-    if (c.use_event && !c.prof && h->opt.dense_graph != 0 && !h->graph_broken && st != nullptr && st == s.own) {   // (never a capture on the caller's stream)
+    if (c.use_event && !c.prof && h->opt.dense_graph != 0 && !h->graph_broken && st != nullptr && st == s.sync.own) {   // (never a capture on the caller's stream)
         u64 key = 0xcbf29ce484222325ull;
         for (u64 v : by_value) key = (key ^ v) * 0x100000001b3ull;
         if (key == 0) key = 1;
@@ -1110,7 +1102,7 @@ static int dense_enqueue(DenseHandle* h, DenseSlot& s, const float* q, int nq, i
     const int kk = (int)(k < h->n_live ? k : h->n_live);   // (removed rows are no neighbours: sq_dense_remove)
     const bool cosine = h->metric == SQ_METRIC_COSINE;
     // (profile = N > 1: every N-th asynchronous call only -- four event records per call weigh on a small shard's step)
-    const bool prof = h->opt.profile == 1 || (h->opt.profile > 1 && (!use_event || h->async_calls % (unsigned)h->opt.profile == 0));
+    const bool prof = h->opt.profile == 1 || (h->opt.profile > 1 && (!use_event || h->ring.calls % (unsigned)h->opt.profile == 0));
     const size_t key_bytes = cosine ? sizeof(K128) : sizeof(u64);
     u32 cap = h->opt.candidate_cap > 0 ? (u32)h->opt.candidate_cap : 65536u;
     if (cap < (u32)(4 * kk)) cap = (u32)(4 * kk);
@@ -1196,10 +1188,7 @@ static int dense_enqueue(DenseHandle* h, DenseSlot& s, const float* q, int nq, i
         c.mid_direct = filter_ok && h->opt.dense_mid_tier != 0 && !h->opt.force_fallback && dense_mid_shape_ok(h);
     }
     if (prof) SQ_HIP(hipEventRecord(s.ev[3], st));
-    if (use_event) {
-        if (!s.ev_done) SQ_HIP(hipEventCreateWithFlags(&s.ev_done, hipEventDisableTiming));
-        SQ_HIP(hipEventRecord(s.ev_done, st));
-    }
+    if (use_event) SQ_TRY(s.sync.mark_done(st));
     c.pending = true;
     return SQ_OK;
 }
@@ -1236,7 +1225,7 @@ static int dense_resolve_wait(DenseHandle* h, DenseSlot& s, const DenseCtx& e) {
     const DenseCall& c = s.call;
     const long long n = h->n;
     const int nq = c.nq;
-    SQ_HIP(c.use_event ? event_wait(s.ev_done) : stream_wait(c.st));  // counts and status words are in e.hs_cnt / e.hs now
+    SQ_TRY(s.sync.wait(c.use_event, c.st));  // counts and status words are in e.hs_cnt / e.hs now
     SQ_HIP(hipGetLastError());
     double clk_tail_ms = -1.0;
     if (s.clk8_wgs > 0 && (h->opt.dense_debug & 8192)) SQ_TRY(dense_body_clocks(h, s, clk_tail_ms));
@@ -1251,7 +1240,7 @@ static int dense_resolve_wait(DenseHandle* h, DenseSlot& s, const DenseCtx& e) {
             const int order[5] = {0, 1, 2, 4, 3};
             for (int j = 0; j < 5; ++j) (void)hipEventElapsedTime(&at[j], h->ev_ref, s.ev[order[j]]);
             fprintf(stderr, "[smqtk_hip] trace slot %d: start %.1f | head-> %.1f | scan-> %.1f | rerank-> %.1f | select-> %.1f us\n",
-                    (int)(&s - h->slot), at[0] * 1e3f, at[1] * 1e3f, at[2] * 1e3f, at[3] * 1e3f, at[4] * 1e3f);
+                    (int)(&s - h->ring.slot), at[0] * 1e3f, at[1] * 1e3f, at[2] * 1e3f, at[3] * 1e3f, at[4] * 1e3f);
         }
         if (c.stats.scan_launches == 2) {  // (the filter path: a re-rank kernel followed the scan)
             float t3 = 0;
@@ -1571,15 +1560,13 @@ static int dense_resolve(DenseHandle* h, DenseSlot& s) {
 
 // Finish every asynchronous call still in flight, oldest first.
 static int dense_sync_all(DenseHandle* h) {
-    for (int j = 0; j < h->depth; ++j)  // slot of call (async_calls - depth + j): oldest first
-        SQ_TRY(dense_resolve(h, h->slot[(h->async_calls + (unsigned)j) % (unsigned)h->depth]));
-    return SQ_OK;
+    return h->ring.drain([h](DenseSlot& s) { return dense_resolve(h, s); });
 }
 
 static int dense_search_device(DenseHandle* h, const float* q, int nq, int k, void* out_dist, long long* out_idx,
                                hipStream_t st) {
-    SQ_TRY(dense_enqueue(h, h->slot[0], q, nq, k, out_dist, out_idx, st, false));
-    return dense_resolve(h, h->slot[0]);
+    SQ_TRY(dense_enqueue(h, h->ring.slot[0], q, nq, k, out_dist, out_idx, st, false));
+    return dense_resolve(h, h->ring.slot[0]);
 }
 
 // Large batches run in chunks so that the per-query workspace (candidate key lists of `cap` keys, the
@@ -2184,17 +2171,10 @@ extern "C" int sq_dense_search(sq_handle_t hid, const float* queries, int nq, in
         // could not certify) one call later.  With "dense_async_streams" = 2 the two slots run on streams of
         // their own, ordered behind the caller's stream by an event, so the small kernels at the end of call
         // i - 1 (re-rank, select) and at the start of call i (query prep, sample pass, threshold) overlap.
-        {
-            int want = h->opt.dense_async_depth;
-            want = want < 2 ? 2 : want > DenseHandle::kMaxDepth ? DenseHandle::kMaxDepth : want;
-            if (want != h->depth) {  // a new depth starts from an empty pipeline
-                SQ_TRY(dense_sync_all(h));
-                h->depth = want;
-                h->async_calls = 0;
-            }
-        }
-        DenseSlot& s = h->slot[h->async_calls % (unsigned)h->depth];
-        SQ_TRY(dense_resolve(h, s));  // (the call `depth` back; normally resolved during an earlier call)
+        const auto resolve = [h](DenseSlot& sl) { return dense_resolve(h, sl); };
+        SQ_TRY(h->ring.set_depth(h->opt.dense_async_depth, resolve));
+        DenseSlot& s = h->ring.next();
+        SQ_TRY(resolve(s));  // (the call `depth` back; normally resolved during an earlier call)
         g_hostprof.lap(1);
         hipStream_t run = st;
         if (h->opt.dense_async_streams == 2) {
@@ -2206,73 +2186,47 @@ extern "C" int sq_dense_search(sq_handle_t hid, const float* queries, int nq, in
             // reads the matrix once: it overlaps like a one-tile batch)
             const int tiles = (nq + TILE_ROWS - 1) / TILE_ROWS;
             const bool one_group = tiles <= scan_query_tiles(h->opt, h->d_pad, tiles);
-            DenseSlot& owner = one_group ? s : h->slot[0];
-            if (!owner.own) SQ_HIP(hipStreamCreateWithFlags(&owner.own, hipStreamNonBlocking));
-            if (h->opt.dense_async_order) {
-                if (!s.ev_in) SQ_HIP(hipEventCreateWithFlags(&s.ev_in, hipEventDisableTiming));
-                SQ_HIP(hipEventRecord(s.ev_in, st));    // the caller's earlier work on `stream` (the queries) comes first
-                SQ_HIP(hipStreamWaitEvent(owner.own, s.ev_in, 0));
-            }  // else: the caller vouches for its queries ("dense_async_order" = 0: an event on a busy or foreign stream
-               // costs ~10 us of start latency per call, as much as a small shard's whole sample pass)
-            run = owner.own;
+            SQ_TRY((one_group ? s : h->ring.slot[0]).sync.stream(&run));
+            // the caller's earlier work on `stream` (the queries) comes first -- unless the caller vouches for them ("dense_async_order"
+            // = 0: an event on a busy or foreign stream costs ~10 us of start latency per call, a small shard's whole sample pass)
+            if (h->opt.dense_async_order) SQ_TRY(s.sync.order_behind(st, run));
         }
         g_hostprof.lap(2);
         SQ_TRY(dense_enqueue(h, s, queries, nq, k, out_dist, reinterpret_cast<long long*>(out_idx), run, true));
         g_hostprof.lap(3);
         g_hostprof.ns[5]++;
-        h->async_calls++;
+        DenseSlot& oldest = h->ring.advance();
         // the oldest call still in flight (depth - 1 calls back): its results are final on return -- unless the caller
         // asked not to wait here ("dense_async_wait" = 0): that call is then finished at the start of the next call (its
         // slot is the next one to be reused), and whatever the host does between the two calls overlaps the device
         if (!h->opt.dense_async_wait) return SQ_OK;
-        const int rc_wait = dense_resolve(h, h->slot[h->async_calls % (unsigned)h->depth]);
+        const int rc_wait = resolve(oldest);
         g_hostprof.lap(4);
         return rc_wait;
     }
     SQ_TRY(dense_sync_all(h));
     if (mem != SQ_MEM_HOST)
         return dense_search_chunked(h, queries, nq, k, out_dist, reinterpret_cast<long long*>(out_idx), st);
-    const size_t qb = (size_t)nq * h->d * 4;
-    SQ_TRY(h->q_dev.reserve(qb));
-    SQ_TRY(h->out_dist_dev.reserve((size_t)nq * k * dsz));
-    SQ_TRY(h->out_idx_dev.reserve((size_t)nq * k * 8));
-    SQ_TRY(h->stage.begin(qb + (size_t)nq * k * (dsz + 8)));
-    SQ_HIP(h->stage.in(h->q_dev.p, queries, qb, st));
-    SQ_TRY(dense_search_chunked(h, h->q_dev.as<float>(), nq, k, h->out_dist_dev.p, h->out_idx_dev.as<long long>(), st));
-    SQ_HIP(h->stage.out(out_dist, h->out_dist_dev.p, (size_t)nq * k * dsz, st));
-    SQ_HIP(h->stage.out(out_idx, h->out_idx_dev.p, (size_t)nq * k * 8, st));
-    SQ_HIP(stream_wait(st));
-    h->stage.finish();
-    return SQ_OK;
+    return staged_call(h->stage, st, {{h->q_dev, queries, (size_t)nq * h->d * 4}},
+                       {{out_dist, h->out_dist_dev, (size_t)nq * k * dsz}, {out_idx, h->out_idx_dev, (size_t)nq * k * 8}}, [&] {
+                           return dense_search_chunked(h, h->q_dev.as<float>(), nq, k, h->out_dist_dev.p, h->out_idx_dev.as<long long>(), st);
+                       });
 }
 
 extern "C" int sq_dense_sync(sq_handle_t hid) {
-    auto* h = static_cast<DenseHandle*>(lookup_handle(hid, H_DENSE));
-    if (!h) return fail(SQ_ERR_INVALID, "sq_dense_sync: unknown handle");
-    std::lock_guard<std::mutex> lock(h->mu);
-    h->refresh_options();
-    SQ_HIP(hipSetDevice(h->device));
-    if (g_hostprof.on && g_hostprof.ns[5] > 0) {
-        const double c = (double)g_hostprof.ns[5] * 1e3;
-        fprintf(stderr, "[smqtk_hip] host us per async call over %lld calls: entry %.2f | resolve of the slot %.2f | stream setup %.2f | enqueue %.2f | wait %.2f\n",
-                g_hostprof.ns[5], g_hostprof.ns[0] / c, g_hostprof.ns[1] / c, g_hostprof.ns[2] / c, g_hostprof.ns[3] / c, g_hostprof.ns[4] / c);
-        for (auto& v : g_hostprof.ns) v = 0;
-    }
-    return dense_sync_all(h);
+    return handle_sync(static_cast<DenseHandle*>(lookup_handle(hid, H_DENSE)), "sq_dense_sync", [](DenseHandle* h) {
+        if (g_hostprof.on && g_hostprof.ns[5] > 0) {
+            const double c = (double)g_hostprof.ns[5] * 1e3;
+            fprintf(stderr, "[smqtk_hip] host us per async call over %lld calls: entry %.2f | resolve of the slot %.2f | stream setup %.2f | enqueue %.2f | wait %.2f\n",
+                    g_hostprof.ns[5], g_hostprof.ns[0] / c, g_hostprof.ns[1] / c, g_hostprof.ns[2] / c, g_hostprof.ns[3] / c, g_hostprof.ns[4] / c);
+            for (auto& v : g_hostprof.ns) v = 0;
+        }
+        return dense_sync_all(h);
+    });
 }
 
 extern "C" int sq_dense_destroy(sq_handle_t hid) {
-    auto* hb = remove_handle(hid, H_DENSE);
-    if (!hb) return fail(SQ_ERR_INVALID, "sq_dense_destroy: unknown handle");
-    auto* h = static_cast<DenseHandle*>(hb);
-    (void)hipSetDevice(h->device);
-    {
-        std::lock_guard<std::mutex> lock(h->mu);
-        h->refresh_options();
-        (void)dense_sync_all(h);  // nothing of this handle is left on the device when its buffers go
-    }
-    delete h;
-    return SQ_OK;
+    return handle_destroy(static_cast<DenseHandle*>(remove_handle(hid, H_DENSE)), "sq_dense_destroy", dense_sync_all);
 }
 
 template <class T>

@@ -26,10 +26,9 @@ struct RowPerm {
     const u32* rank;  // non-null: physical row p holds the code of sorted rank rank[p]
 };
 
-// Per-call workspace.  A synchronous search uses slot 0; asynchronous searches (SQ_MEM_DEVICE_ASYNC) rotate through
-// `depth` slots, each with a stream of its own, so that the short kernels around the scan (histogram, threshold,
-// compaction, select) of neighbouring calls overlap the scans and the host reads a call's status words one call later
-// -- the scheme of the dense search (sq_dense.hip).
+// Per-call workspace: the slots of the handle's CallRing (sq_pipeline.hpp has the rotation), each with a stream of its own, so
+// that the short kernels around the scan (histogram, threshold, compaction, select) of neighbouring calls overlap the scans
+// and the host reads a call's status words one call later -- the scheme of the dense search (sq_dense.hip).
 struct HammingPlan {   // what hamming_plan() decides for a call (the rules are there)
     int kk = 0;                   // min(k, n)
     u32 cap = 0;                  // candidates per query
@@ -64,15 +63,11 @@ struct HammingSlot {
     void* fhist_zeroed = nullptr; // the allocation of fhist that has been wiped once
     HostPinned status_host;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t ev_in = nullptr, ev_done = nullptr;
-    hipStream_t own = nullptr;
+    SlotSync sync;                // the slot's stream and its ordering events (sq_pipeline.hpp)
     HammingCall call;
-    ~HammingSlot() {   // (the buffers free themselves, after this body)
+    ~HammingSlot() {   // (the buffers and `sync` free themselves, after this body)
         for (auto& e : ev)
             if (e) (void)hipEventDestroy(e);
-        if (ev_in) (void)hipEventDestroy(ev_in);
-        if (ev_done) (void)hipEventDestroy(ev_done);
-        if (own) (void)hipStreamDestroy(own);
     }
 };
 
@@ -86,10 +81,8 @@ struct HammingHandle : HandleBase {
     DevBuf rank;                  // u32[n] explicit ranks, after the first append / remove
     DevBuf mut_tmp;               // scratch of the mutation kernels
     static constexpr int kMaxDepth = 4;
-    HammingSlot slot[kMaxDepth];
+    CallRing<HammingSlot, kMaxDepth> ring;   // the call slots (option hamming_async_depth: 2 .. kMaxDepth in flight)
     bool no_fused = false;               // set while a fused call whose tightened threshold fell short is redone by the general chain
-    int depth = 2;                       // asynchronous calls in flight (option hamming_async_depth, fixed while any is)
-    unsigned long long async_calls = 0;  // asynchronous calls so far (slot = calls % depth)
     // shared by all calls: host-memory staging and the exact path (both synchronous)
     DevBuf q_dev, out_dist_dev, out_idx_dev, big_keys, fb_sort;
     PinnedStage stage;
@@ -776,7 +769,7 @@ static HammingPlan hamming_plan(const HammingHandle* h, int nq, int k, bool use_
     const int W = h->words;
     HammingPlan p;
     const int kk = p.kk = (int)(k < n ? k : n);
-    p.prof = h->opt.profile == 1 || (h->opt.profile > 1 && (!use_event || h->async_calls % (unsigned)h->opt.profile == 0));
+    p.prof = h->opt.profile == 1 || (h->opt.profile > 1 && (!use_event || h->ring.calls % (unsigned)h->opt.profile == 0));
     u32 cap = h->opt.candidate_cap > 0 ? (u32)h->opt.candidate_cap : 65536u;
     // room for the tie group at the threshold distance (integer distances: the codes AT the threshold can outnumber
     // those below it several times)
@@ -1056,10 +1049,7 @@ static int hamming_enqueue(HammingHandle* h, HammingSlot& s, const u64* qs, int 
     c.stats.scan_launches = 1;
     c.stats.bytes_scanned = h->n * h->words * 8;
     if (p.prof) SQ_HIP(hipEventRecord(s.ev[3], st));
-    if (use_event) {
-        if (!s.ev_done) SQ_HIP(hipEventCreateWithFlags(&s.ev_done, hipEventDisableTiming));
-        SQ_HIP(hipEventRecord(s.ev_done, st));
-    }
+    if (use_event) SQ_TRY(s.sync.mark_done(st));
     c.force_fb = h->opt.force_fallback != 0;
     c.pending = true;
     return SQ_OK;
@@ -1111,7 +1101,7 @@ static int hamming_resolve(HammingHandle* h, HammingSlot& s) {
     hipStream_t st = c.st;
     // status words and candidate counts are in pinned host memory once the call has drained (written by the
     // finalisation): the host decides whether any query needs the exact path
-    SQ_HIP(c.use_event ? event_wait(s.ev_done) : stream_wait(st));
+    SQ_TRY(s.sync.wait(c.use_event, st));
     SQ_HIP(hipGetLastError());
     h->stats = c.stats;
     if (c.plan.prof) {
@@ -1148,15 +1138,13 @@ static int hamming_resolve(HammingHandle* h, HammingSlot& s) {
 
 // Finish every asynchronous call still in flight, oldest first.
 static int hamming_sync_all(HammingHandle* h) {
-    for (int j = 0; j < h->depth; ++j)
-        SQ_TRY(hamming_resolve(h, h->slot[(h->async_calls + (unsigned)j) % (unsigned)h->depth]));
-    return SQ_OK;
+    return h->ring.drain([h](HammingSlot& s) { return hamming_resolve(h, s); });
 }
 
 static int hamming_search_device(HammingHandle* h, const u64* qs, int nq, int k, int* out_dist, long long* out_idx,
                                  hipStream_t st) {
-    SQ_TRY(hamming_enqueue(h, h->slot[0], qs, nq, k, out_dist, out_idx, st, false));
-    return hamming_resolve(h, h->slot[0]);
+    SQ_TRY(hamming_enqueue(h, h->ring.slot[0], qs, nq, k, out_dist, out_idx, st, false));
+    return hamming_resolve(h, h->ring.slot[0]);
 }
 
 // ------------------------------------------------------------------ mutations
@@ -1332,54 +1320,33 @@ extern "C" int sq_hamming_search(sq_handle_t hid, const uint64_t* queries, int n
     if (mem == SQ_MEM_DEVICE_ASYNC) {
         // The pipelined form (see sq_dense_search): call i is enqueued on its slot's own stream before call i - 1 is
         // waited for; a call's status words are read -- and its overflowing queries redone -- `depth - 1` calls later.
-        int want = h->opt.hamming_async_depth;
-        want = want < 2 ? 2 : want > HammingHandle::kMaxDepth ? HammingHandle::kMaxDepth : want;
-        if (want != h->depth) {  // a new depth starts from an empty pipeline
-            SQ_TRY(hamming_sync_all(h));
-            h->depth = want;
-            h->async_calls = 0;
-        }
-        HammingSlot& s = h->slot[h->async_calls % (unsigned)h->depth];
-        SQ_TRY(hamming_resolve(h, s));  // (the call `depth` back; normally resolved during an earlier call)
-        if (!s.own) SQ_HIP(hipStreamCreateWithFlags(&s.own, hipStreamNonBlocking));
-        if (h->opt.hamming_async_order) {
-            if (!s.ev_in) SQ_HIP(hipEventCreateWithFlags(&s.ev_in, hipEventDisableTiming));
-            SQ_HIP(hipEventRecord(s.ev_in, st));  // the caller's earlier work on `stream` (the queries) comes first
-            SQ_HIP(hipStreamWaitEvent(s.own, s.ev_in, 0));
-        }
+        const auto resolve = [h](HammingSlot& sl) { return hamming_resolve(h, sl); };
+        SQ_TRY(h->ring.set_depth(h->opt.hamming_async_depth, resolve));
+        HammingSlot& s = h->ring.next();
+        SQ_TRY(resolve(s));  // (the call `depth` back; normally resolved during an earlier call)
+        hipStream_t run = nullptr;
+        SQ_TRY(s.sync.stream(&run));
+        if (h->opt.hamming_async_order) SQ_TRY(s.sync.order_behind(st, run));  // the caller's earlier work on `stream` (the queries) comes first
         SQ_TRY(hamming_enqueue(h, s, reinterpret_cast<const u64*>(queries), nq, k, out_dist, reinterpret_cast<long long*>(out_idx),
-                               s.own, true));
-        h->async_calls++;
+                               run, true));
+        HammingSlot& oldest = h->ring.advance();
         if (!h->opt.hamming_async_wait) return SQ_OK;
-        return hamming_resolve(h, h->slot[h->async_calls % (unsigned)h->depth]);
+        return resolve(oldest);
     }
     SQ_TRY(hamming_sync_all(h));
     if (mem == SQ_MEM_DEVICE) {
         return hamming_search_device(h, reinterpret_cast<const u64*>(queries), nq, k, out_dist,
                                      reinterpret_cast<long long*>(out_idx), st);
     }
-    size_t qb = (size_t)nq * h->words * 8;
-    SQ_TRY(h->q_dev.reserve(qb));
-    SQ_TRY(h->out_dist_dev.reserve((size_t)nq * k * 4));
-    SQ_TRY(h->out_idx_dev.reserve((size_t)nq * k * 8));
-    SQ_TRY(h->stage.begin(qb + (size_t)nq * k * 12));
-    SQ_HIP(h->stage.in(h->q_dev.p, queries, qb, st));
-    SQ_TRY(hamming_search_device(h, h->q_dev.as<u64>(), nq, k, h->out_dist_dev.as<int>(),
-                                 h->out_idx_dev.as<long long>(), st));
-    SQ_HIP(h->stage.out(out_dist, h->out_dist_dev.p, (size_t)nq * k * 4, st));
-    SQ_HIP(h->stage.out(out_idx, h->out_idx_dev.p, (size_t)nq * k * 8, st));
-    SQ_HIP(stream_wait(st));
-    h->stage.finish();
-    return SQ_OK;
+    return staged_call(h->stage, st, {{h->q_dev, queries, (size_t)nq * h->words * 8}},
+                       {{out_dist, h->out_dist_dev, (size_t)nq * k * 4}, {out_idx, h->out_idx_dev, (size_t)nq * k * 8}}, [&] {
+                           return hamming_search_device(h, h->q_dev.as<u64>(), nq, k, h->out_dist_dev.as<int>(),
+                                                        h->out_idx_dev.as<long long>(), st);
+                       });
 }
 
 extern "C" int sq_hamming_sync(sq_handle_t hid) {
-    auto* h = static_cast<HammingHandle*>(lookup_handle(hid, H_HAMMING));
-    if (!h) return fail(SQ_ERR_INVALID, "sq_hamming_sync: unknown handle");
-    std::lock_guard<std::mutex> lock(h->mu);
-    h->refresh_options();
-    SQ_HIP(hipSetDevice(h->device));
-    return hamming_sync_all(h);
+    return handle_sync(static_cast<HammingHandle*>(lookup_handle(hid, H_HAMMING)), "sq_hamming_sync", hamming_sync_all);
 }
 
 extern "C" int sq_hamming_append(sq_handle_t hid, const uint64_t* new_codes, int64_t m, const int64_t* insert_pos) {
@@ -1454,15 +1421,5 @@ extern "C" int sq_hamming_info(sq_handle_t hid, int64_t* out_n, int* out_words) 
 }
 
 extern "C" int sq_hamming_destroy(sq_handle_t hid) {
-    auto* hb = remove_handle(hid, H_HAMMING);
-    if (!hb) return fail(SQ_ERR_INVALID, "sq_hamming_destroy: unknown handle");
-    auto* h = static_cast<HammingHandle*>(hb);
-    (void)hipSetDevice(h->device);
-    {
-        std::lock_guard<std::mutex> lock(h->mu);
-        h->refresh_options();
-        (void)hamming_sync_all(h);  // nothing of this handle is left on the device when its buffers go
-    }
-    delete h;
-    return SQ_OK;
+    return handle_destroy(static_cast<HammingHandle*>(remove_handle(hid, H_HAMMING)), "sq_hamming_destroy", hamming_sync_all);
 }

@@ -38,19 +38,8 @@ struct IvfHandle : HandleBase {
     }
 };
 
-// exactly `bytes` (DevBuf::reserve adds an eighth for buffers that grow; these are replaced whole)
-static int ivf_alloc(DevBuf& b, size_t bytes) {
-    b.release();
-    if (bytes == 0) bytes = 16;
-    hipError_t e = hipMalloc(&b.p, bytes);
-    if (e != hipSuccess) {
-        b.p = nullptr;
-        (void)hipGetLastError();
-        return fail(SQ_ERR_NOMEM, "hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
-    }
-    b.cap = bytes;
-    return SQ_OK;
-}
+// DevBuf::alloc_exact (these arrays are replaced whole); its failure is reported here, not again by the next launch's check
+static int ivf_alloc(DevBuf& b, size_t bytes) { return b.alloc_exact(bytes) == SQ_OK ? SQ_OK : ((void)hipGetLastError(), SQ_ERR_NOMEM); }
 
 // The coarse index: float32 centroids only -- no scan copies, and the candidate cap at its default, so that up to
 // 65536 centroids are answered from exact keys of all of them.
@@ -338,26 +327,10 @@ static __global__ __launch_bounds__(256) void ivf_kmeans_update_kernel(const flo
     }
 }
 
-static int ivf_search_locked(IvfHandle* h, const float* queries, int nq, int k, int nprobe, float* out_dist, int64_t* out_idx, int mem,
-                             hipStream_t st) {
-    const auto t_call = std::chrono::steady_clock::now();
+// The search with queries and outputs in device memory, enqueued on `st`; the last select is not waited for.
+static int ivf_search_device(IvfHandle* h, const float* q_dev, int nq, int k, int nprobe, float* od, long long* oi, hipStream_t st) {
     const int d = h->d, nlist = h->nlist, np = nprobe < nlist ? nprobe : nlist;
-    const bool host = mem == SQ_MEM_HOST, prof = h->opt.profile != 0;
-    h->stats = sq_stats_t{};
-    const float* q_dev = queries;
-    float* od = out_dist;
-    long long* oi = reinterpret_cast<long long*>(out_idx);
-    if (host) {
-        const size_t qb = (size_t)nq * d * 4;
-        SQ_TRY(h->q_dev.reserve(qb));
-        SQ_TRY(h->out_dist.reserve((size_t)nq * k * 4));
-        SQ_TRY(h->out_idx.reserve((size_t)nq * k * 8));
-        SQ_TRY(h->stage.begin(qb + (size_t)nq * k * 12));
-        SQ_HIP(h->stage.in(h->q_dev.p, queries, qb, st));
-        q_dev = h->q_dev.as<float>();
-        od = h->out_dist.as<float>();
-        oi = h->out_idx.as<long long>();
-    }
+    const bool prof = h->opt.profile != 0;
     // probe: the np nearest centroids per query, (distance, list number) order, on the device
     SQ_TRY(h->probe_dist.reserve((size_t)nq * np * 4));
     SQ_TRY(h->probe_idx.reserve((size_t)nq * np * 8));
@@ -403,15 +376,8 @@ static int ivf_search_locked(IvfHandle* h, const float* queries, int nq, int k, 
         const IvfFinalize fin{q0, k, h->id_base, od, oi};
         SQ_TRY(select_launch_t<u64>(h->keys.as<u64>(), h->cnt.as<u32>() + q0, (u32)mc, mc, k_sel, m, h->out_keys.as<u64>(), fin, st, h->sort_tmp));
     }
-    if (host) {
-        SQ_HIP(h->stage.out(out_dist, od, (size_t)nq * k * 4, st));
-        SQ_HIP(h->stage.out(out_idx, oi, (size_t)nq * k * 8, st));
-    }
-    SQ_HIP(stream_wait(st));
-    if (host) h->stage.finish();
     h->stats.candidates = total;
     h->stats.bytes_scanned = total * h->ld * 4;
-    if (prof) h->stats.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
     return SQ_OK;
 }
 
@@ -508,7 +474,21 @@ extern "C" int sq_ivf_search(sq_handle_t hid, const float* queries, int nq, int 
     std::lock_guard<std::mutex> lock(h->mu);
     h->refresh_options();
     SQ_HIP(hipSetDevice(h->device));
-    return ivf_search_locked(h, queries, nq, k, nprobe, out_dist, out_idx, mem, reinterpret_cast<hipStream_t>(stream));
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const auto t_call = std::chrono::steady_clock::now();
+    h->stats = sq_stats_t{};
+    if (mem == SQ_MEM_HOST) {
+        SQ_TRY(staged_call(h->stage, st, {{h->q_dev, queries, (size_t)nq * h->d * 4}},
+                           {{out_dist, h->out_dist, (size_t)nq * k * 4}, {out_idx, h->out_idx, (size_t)nq * k * 8}}, [&] {
+                               return ivf_search_device(h, h->q_dev.as<float>(), nq, k, nprobe, h->out_dist.as<float>(),
+                                                        h->out_idx.as<long long>(), st);
+                           }));
+    } else {
+        SQ_TRY(ivf_search_device(h, queries, nq, k, nprobe, out_dist, reinterpret_cast<long long*>(out_idx), st));
+        SQ_HIP(stream_wait(st));
+    }
+    if (h->opt.profile != 0) h->stats.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
+    return SQ_OK;
 }
 
 extern "C" int sq_ivf_destroy(sq_handle_t hid) {

@@ -291,29 +291,15 @@ extern "C" int sq_rows_rerank(sq_handle_t hid, const void* queries, int nq, int 
         }
         return SQ_OK;
     }
-    SQ_TRY(h->q_dev.reserve((size_t)nq * h->d * esz));
-    SQ_TRY(h->cand_dev.reserve((size_t)(total > 0 ? total : 1) * 8));
-    SQ_TRY(h->off_dev.reserve((size_t)(nq + 1) * 8));
     SQ_TRY(h->cnt_dev.reserve((size_t)nq * 4));
-    SQ_TRY(h->out_dist.reserve((size_t)nq * k * dsz));
-    SQ_TRY(h->out_pos.reserve((size_t)nq * k * 8));
-    SQ_TRY(h->stage.begin((size_t)nq * h->d * esz + (size_t)total * 8 + (size_t)(nq + 1) * 8 + (size_t)nq * k * (dsz + 8)));
-    SQ_HIP(h->stage.in(h->q_dev.p, queries, (size_t)nq * h->d * esz, st));
-    SQ_HIP(h->stage.in(h->cand_dev.p, cand_rows, (size_t)total * 8, st));
-    SQ_HIP(h->stage.in(h->off_dev.p, cand_offsets, (size_t)(nq + 1) * 8, st));
-    int rc;
-    if (k64)
-        rc = rows_rerank_t<float, u64>(h, nq, metric, maxc, k, st);
-    else if (f32)
-        rc = rows_rerank_t<float, K128>(h, nq, metric, maxc, k, st);
-    else
-        rc = rows_rerank_t<double, K128>(h, nq, metric, maxc, k, st);
-    if (rc != SQ_OK) return rc;
-    SQ_HIP(h->stage.out(out_dist, h->out_dist.p, (size_t)nq * k * dsz, st));
-    SQ_HIP(h->stage.out(out_pos, h->out_pos.p, (size_t)nq * k * 8, st));
-    SQ_HIP(stream_wait(st));
-    h->stage.finish();
-    return SQ_OK;
+    // (maxc > 0: there is a candidate, so none of the inputs is empty)
+    return staged_call(h->stage, st,
+                       {{h->q_dev, queries, (size_t)nq * h->d * esz}, {h->cand_dev, cand_rows, (size_t)total * 8}, {h->off_dev, cand_offsets, (size_t)(nq + 1) * 8}},
+                       {{out_dist, h->out_dist, (size_t)nq * k * dsz}, {out_pos, h->out_pos, (size_t)nq * k * 8}}, [&] {
+                           return k64 ? rows_rerank_t<float, u64>(h, nq, metric, maxc, k, st)
+                                  : f32 ? rows_rerank_t<float, K128>(h, nq, metric, maxc, k, st)
+                                        : rows_rerank_t<double, K128>(h, nq, metric, maxc, k, st);
+                       });
 }
 
 extern "C" int sq_rows_set_buckets(sq_handle_t hid, const int64_t* csr_off, int64_t n_codes, const int64_t* csr_rows, int mem) {
@@ -356,6 +342,44 @@ static int lsh_rerank_t(RowsHandle* h, int nq, int metric, long long maxc, int k
     return launch<lsh_finalize_kernel<K>>(dim3(nq), dim3(256), 0, st, h->out_keys.as<K>(), h->cnt_dev.as<u32>(), k_sel, k_out,
                                           h->cand_dev.as<long long>(), h->off_dev.as<long long>(), out_dist_dev, out_rows_dev);
 }
+
+// sq_lsh_query with the queries in h->q_dev and the outputs in device memory, enqueued on `st`: hash, the m nearest
+// codes, their buckets' rows, the re-rank.  The re-rank is not waited for.
+static int lsh_query_device(RowsHandle* h, sq_handle_t hamming_h, sq_handle_t itq_h, int nq, int m, int words, int metric, int k_out,
+                            void* od, long long* orow, hipStream_t st) {
+    const bool f32 = h->dtype == SQ_DTYPE_F32;
+    const bool k64 = f32 && metric == SQ_METRIC_L2;
+    // hash (lsh.py:473), nearest codes (lsh.py:480-487): device to device
+    SQ_TRY(h->codes_dev.reserve((size_t)nq * words * 8));
+    SQ_TRY(h->ham_dist.reserve((size_t)nq * m * 4));
+    SQ_TRY(h->ham_idx.reserve((size_t)nq * m * 8));
+    SQ_TRY(sq_itq_model_hash(itq_h, h->q_dev.p, h->dtype, nq, h->codes_dev.as<uint64_t>(), SQ_MEM_DEVICE, st));
+    SQ_TRY(sq_hamming_search(hamming_h, h->codes_dev.as<uint64_t>(), nq, m, h->ham_dist.as<int32_t>(), h->ham_idx.as<int64_t>(),
+                             SQ_MEM_DEVICE, st));
+    // bucket expansion (lsh.py:489-501) on the device; only [total, largest list] comes back
+    SQ_TRY(h->pre_dev.reserve((size_t)nq * m * 8 + (size_t)nq * 8));
+    SQ_TRY(h->off_dev.reserve((size_t)(nq + 1) * 8));
+    SQ_TRY(h->cnt_dev.reserve((size_t)nq * 4));
+    SQ_TRY(h->totals_host.reserve(16));
+    long long* pre = h->pre_dev.as<long long>();
+    long long* tot = pre + (size_t)nq * m;
+    long long* th = reinterpret_cast<long long*>(h->totals_host.p);
+    void* th_dev = nullptr;
+    SQ_TRY(h->totals_host.device_ptr(&th_dev));
+    SQ_TRY(launch<lsh_bucket_sizes_kernel>(dim3(nq), dim3(256), 0, st, h->ham_idx.as<long long>(), m, h->csr_off, h->n_codes, pre, tot));
+    SQ_TRY(launch<lsh_offsets_kernel>(dim3(1), dim3(1), 0, st, tot, nq, h->off_dev.as<long long>(), static_cast<long long*>(th_dev)));
+    SQ_HIP(stream_wait(st));
+    const long long total = th[0], maxc = th[1];
+    if (maxc >= (1ll << 32)) return fail(SQ_ERR_UNSUPPORTED, "sq_lsh_query: more than 2^32-1 candidates for one query");
+    SQ_TRY(h->cand_dev.reserve((size_t)(total > 0 ? total : 1) * 8));
+    const long long mc = maxc > 0 ? maxc : 1;
+    SQ_TRY(launch<lsh_fill_candidates_kernel>(dim3((unsigned)((m + 31) / 32), nq), dim3(256), 0, st, h->ham_idx.as<long long>(), m,
+                                              h->csr_off, h->csr_rows, h->n_codes, pre, h->off_dev.as<long long>(), h->cand_dev.as<long long>()));
+    const int k_sel = (int)std::min<long long>(k_out, mc);
+    return k64 ? lsh_rerank_t<float, u64>(h, nq, metric, mc, k_sel, k_out, od, orow, st)
+           : f32 ? lsh_rerank_t<float, K128>(h, nq, metric, mc, k_sel, k_out, od, orow, st)
+                 : lsh_rerank_t<double, K128>(h, nq, metric, mc, k_sel, k_out, od, orow, st);
+}
 }  // namespace sq
 
 extern "C" int sq_hamming_info(sq_handle_t h, int64_t* out_n, int* out_words);
@@ -378,71 +402,19 @@ extern "C" int sq_lsh_query(sq_handle_t rows_h, sq_handle_t hamming_h, sq_handle
     SQ_HIP(hipSetDevice(h->device));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const bool f32 = h->dtype == SQ_DTYPE_F32;
-    const bool k64 = f32 && metric == SQ_METRIC_L2;
-    const size_t esz = f32 ? 4 : 8, dsz = k64 ? 4 : 8;
+    const size_t qb = (size_t)nq * h->d * (f32 ? 4 : 8), dsz = f32 && metric == SQ_METRIC_L2 ? 4 : 8;
     const int m = (int)std::min<long long>(n_codes_wanted, ham_n);  // nearest codes per query
-    const void* q_dev = queries;
-    if (mem != SQ_MEM_DEVICE) {
-        SQ_TRY(h->q_dev.reserve((size_t)nq * h->d * esz));
-        SQ_TRY(h->stage.begin((size_t)nq * h->d * esz + (size_t)nq * k_out * (dsz + 8)));
-        SQ_HIP(h->stage.in(h->q_dev.p, queries, (size_t)nq * h->d * esz, st));
-        q_dev = h->q_dev.p;
-    } else {
+    if (mem == SQ_MEM_DEVICE) {
         // the re-rank kernels read the queries from q_dev: borrow the caller's buffer for this call
-        SQ_TRY(h->q_dev.reserve((size_t)nq * h->d * esz));
-        SQ_HIP(hipMemcpyAsync(h->q_dev.p, queries, (size_t)nq * h->d * esz, hipMemcpyDeviceToDevice, st));
-        q_dev = h->q_dev.p;
+        SQ_TRY(h->q_dev.reserve(qb));
+        SQ_HIP(hipMemcpyAsync(h->q_dev.p, queries, qb, hipMemcpyDeviceToDevice, st));
+        return lsh_query_device(h, hamming_h, itq_h, nq, m, words, metric, k_out, out_dist, reinterpret_cast<long long*>(out_rows), st);
     }
-    // hash (lsh.py:473), nearest codes (lsh.py:480-487): device to device
-    SQ_TRY(h->codes_dev.reserve((size_t)nq * words * 8));
-    SQ_TRY(h->ham_dist.reserve((size_t)nq * m * 4));
-    SQ_TRY(h->ham_idx.reserve((size_t)nq * m * 8));
-    SQ_TRY(sq_itq_model_hash(itq_h, q_dev, h->dtype, nq, h->codes_dev.as<uint64_t>(), SQ_MEM_DEVICE, st));
-    SQ_TRY(sq_hamming_search(hamming_h, h->codes_dev.as<uint64_t>(), nq, m, h->ham_dist.as<int32_t>(), h->ham_idx.as<int64_t>(),
-                             SQ_MEM_DEVICE, st));
-    // bucket expansion (lsh.py:489-501) on the device; only [total, largest list] comes back
-    SQ_TRY(h->pre_dev.reserve((size_t)nq * m * 8 + (size_t)nq * 8));
-    SQ_TRY(h->off_dev.reserve((size_t)(nq + 1) * 8));
-    SQ_TRY(h->cnt_dev.reserve((size_t)nq * 4));
-    SQ_TRY(h->totals_host.reserve(16));
-    long long* pre = h->pre_dev.as<long long>();
-    long long* tot = pre + (size_t)nq * m;
-    long long* th = reinterpret_cast<long long*>(h->totals_host.p);
-    void* th_dev = nullptr;
-    SQ_TRY(h->totals_host.device_ptr(&th_dev));
-    SQ_TRY(launch<lsh_bucket_sizes_kernel>(dim3(nq), dim3(256), 0, st, h->ham_idx.as<long long>(), m, h->csr_off, h->n_codes, pre, tot));
-    SQ_TRY(launch<lsh_offsets_kernel>(dim3(1), dim3(1), 0, st, tot, nq, h->off_dev.as<long long>(), static_cast<long long*>(th_dev)));
-    SQ_HIP(stream_wait(st));
-    const long long total = th[0], maxc = th[1];
-    if (maxc >= (1ll << 32)) return fail(SQ_ERR_UNSUPPORTED, "sq_lsh_query: more than 2^32-1 candidates for one query");
-    void* od = out_dist;
-    long long* orow = reinterpret_cast<long long*>(out_rows);
-    if (mem != SQ_MEM_DEVICE) {
-        SQ_TRY(h->out_dist.reserve((size_t)nq * k_out * dsz));
-        SQ_TRY(h->out_rows.reserve((size_t)nq * k_out * 8));
-        od = h->out_dist.p;
-        orow = h->out_rows.as<long long>();
-    }
-    SQ_TRY(h->cand_dev.reserve((size_t)(total > 0 ? total : 1) * 8));
-    const long long mc = maxc > 0 ? maxc : 1;
-    SQ_TRY(launch<lsh_fill_candidates_kernel>(dim3((unsigned)((m + 31) / 32), nq), dim3(256), 0, st, h->ham_idx.as<long long>(), m,
-                                              h->csr_off, h->csr_rows, h->n_codes, pre, h->off_dev.as<long long>(), h->cand_dev.as<long long>()));
-    const int k_sel = (int)std::min<long long>(k_out, mc);
-    int rc;
-    if (k64)
-        rc = lsh_rerank_t<float, u64>(h, nq, metric, mc, k_sel, k_out, od, orow, st);
-    else if (f32)
-        rc = lsh_rerank_t<float, K128>(h, nq, metric, mc, k_sel, k_out, od, orow, st);
-    else
-        rc = lsh_rerank_t<double, K128>(h, nq, metric, mc, k_sel, k_out, od, orow, st);
-    if (rc != SQ_OK) return rc;
-    if (mem != SQ_MEM_DEVICE) {
-        SQ_HIP(h->stage.out(out_dist, od, (size_t)nq * k_out * dsz, st));
-        SQ_HIP(h->stage.out(out_rows, orow, (size_t)nq * k_out * 8, st));
-        SQ_HIP(stream_wait(st));
-        h->stage.finish();
-    }
-    return SQ_OK;
+    return staged_call(h->stage, st, {{h->q_dev, queries, qb}},
+                       {{out_dist, h->out_dist, (size_t)nq * k_out * dsz}, {out_rows, h->out_rows, (size_t)nq * k_out * 8}}, [&] {
+                           return lsh_query_device(h, hamming_h, itq_h, nq, m, words, metric, k_out, h->out_dist.p,
+                                                   h->out_rows.as<long long>(), st);
+                       });
 }
 
 extern "C" int sq_rows_destroy(sq_handle_t hid) {

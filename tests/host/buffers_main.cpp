@@ -97,6 +97,34 @@ static void sizes() {
     CHECK(h.reserve(4096) == SQ_OK && h.cap == 4096 + 256);
 }
 
+// DevBuf::alloc_exact: the bytes asked for and no more, a new block every time
+static void exact() {
+    const long base = live();
+    {
+        DevBuf b;
+        CHECK(b.alloc_exact(4096) == SQ_OK && b.p && b.cap == 4096 && live() == base + 1);   // no eighth on top
+        fill(b.p, 4096, 8);
+        const long made = hip_stub::allocs;
+        CHECK(b.alloc_exact(100) == SQ_OK && b.cap == 100 && hip_stub::allocs == made + 1 && live() == base + 1);   // replaced, although it fitted
+        fill(b.p, 100, 9);
+        CHECK(b.alloc_exact(0) == SQ_OK && b.p && b.cap == 16 && live() == base + 1);       // nothing is 16 bytes
+        fill(b.p, 16, 10);
+        CHECK(b.reserve(16) == SQ_OK && b.cap == 16 && b.reserve(17) == SQ_OK && b.cap == 17 + 2 + 256);   // reserve() goes on from it
+        hip_stub::fail_in = 1;
+        CHECK(b.alloc_exact(5000) == SQ_ERR_NOMEM);   // DevBuf's failure contract: empty, the old block freed
+        CHECK(b.p == nullptr && b.cap == 0 && live() == base && g_err[0] != 0);
+        DevBuf c;
+        hip_stub::fail_in = 1;
+        CHECK(c.alloc_exact(0) == SQ_ERR_NOMEM && c.p == nullptr && c.cap == 0 && live() == base);   // a failed first allocation
+        hip_stub::fail_in = 2;
+        CHECK(b.alloc_exact(64) == SQ_OK && c.alloc_exact(64) == SQ_ERR_NOMEM && live() == base + 1);
+        CHECK(c.alloc_exact(64) == SQ_OK && c.cap == 64 && live() == base + 2);           // ... and it can be used again
+        DevBuf d(std::move(c));
+        CHECK(c.p == nullptr && d.cap == 64 && live() == base + 2);
+    }
+    CHECK(live() == base);
+}
+
 static void device_pointer() {
     HostPinned h;
     CHECK(h.reserve(64) == SQ_OK);
@@ -206,6 +234,7 @@ int main() {
     lifetime<DevBuf>();
     lifetime<HostPinned>();
     sizes();
+    exact();
     device_pointer();
     growing();
     staging();

@@ -4,10 +4,13 @@
 // For smqtk_indexing_amd/csrc/sq_pairwise.hpp (tests/host/pairwise_main.cpp): the function qualifiers as nothing, the
 // round-to-nearest adds as plain adds (the programs are compiled with -ffp-contract=off), and a cross-lane exchange
 // that only has to compile -- the eight-lane leaf that uses it is not instantiated on a host.
+// For smqtk_indexing_amd/csrc/sq_pipeline.hpp (tests/host/pipeline_main.cpp): streams and events as counted heap objects
+// (a forgotten destroy is a leak, a second one an address error) and a log of what was recorded and waited for on them.
 #pragma once
 #include <cstddef>
 #include <cstdlib>
 #include <cstring>
+#include <vector>
 
 #define __host__
 #define __device__
@@ -22,6 +25,14 @@ inline T __shfl_xor(T, int) {
 typedef int hipError_t;
 enum : int { hipSuccess = 0, hipErrorInvalidValue = 1, hipErrorOutOfMemory = 2 };
 typedef struct hipStubStream* hipStream_t;
+typedef struct hipStubEvent* hipEvent_t;
+struct hipStubStream {
+    unsigned flags;
+};
+struct hipStubEvent {
+    unsigned flags;
+};
+enum : unsigned { hipStreamNonBlocking = 1, hipEventDisableTiming = 2 };
 enum hipMemcpyKind { hipMemcpyHostToHost, hipMemcpyHostToDevice, hipMemcpyDeviceToHost, hipMemcpyDeviceToDevice };
 enum : unsigned { hipHostMallocDefault = 0 };
 
@@ -46,7 +57,50 @@ inline hipError_t release(void* p) {
     free(p);
     return hipSuccess;
 }
+
+inline long streams_created = 0, streams_destroyed = 0, events_created = 0, events_destroyed = 0;
+// append-only: an event recorded on a stream (null: the default stream), a stream made to wait for an event; the
+// programs add waits and marks of their own
+enum Op { kRecord, kStreamWaitEvent, kStreamWait, kEventWait, kMark };
+struct Logged {
+    Op op;
+    hipStream_t stream;
+    hipEvent_t event;
+    bool operator==(const Logged& o) const { return op == o.op && stream == o.stream && event == o.event; }
+};
+inline std::vector<Logged> log;
 }  // namespace hip_stub
+
+inline hipError_t hipStreamCreateWithFlags(hipStream_t* st, unsigned flags) {
+    *st = new hipStubStream{flags};
+    ++hip_stub::streams_created;
+    return hipSuccess;
+}
+inline hipError_t hipStreamDestroy(hipStream_t st) {
+    ++hip_stub::streams_destroyed;
+    delete st;
+    return hipSuccess;
+}
+inline hipError_t hipEventCreateWithFlags(hipEvent_t* ev, unsigned flags) {
+    *ev = new hipStubEvent{flags};
+    ++hip_stub::events_created;
+    return hipSuccess;
+}
+inline hipError_t hipEventDestroy(hipEvent_t ev) {
+    ++hip_stub::events_destroyed;
+    delete ev;
+    return hipSuccess;
+}
+inline hipError_t hipEventRecord(hipEvent_t ev, hipStream_t st) {
+    if (!ev) return hipErrorInvalidValue;
+    hip_stub::log.push_back({hip_stub::kRecord, st, ev});
+    return hipSuccess;
+}
+inline hipError_t hipStreamWaitEvent(hipStream_t st, hipEvent_t ev, unsigned) {
+    if (!ev) return hipErrorInvalidValue;
+    hip_stub::log.push_back({hip_stub::kStreamWaitEvent, st, ev});
+    return hipSuccess;
+}
 
 inline hipError_t hipMalloc(void** p, size_t bytes) { return hip_stub::alloc(p, bytes); }
 inline hipError_t hipFree(void* p) { return hip_stub::release(p); }

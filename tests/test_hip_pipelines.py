@@ -198,6 +198,99 @@ def test_hamming_async_calls_equal_blocking_calls(depth, wait, ring):
     np.testing.assert_array_equal(oi[1].cpu().numpy(), want[1][1])
 
 
+def test_hamming_depth_change_drains_first():
+    """A new hamming_async_depth starts from an empty pipeline: the call that brings it finishes every call in flight
+    before it is enqueued itself, so their outputs are final when it returns -- not only after sync()."""
+    rng = np.random.default_rng(314)
+    dev = _dev()
+    codes_h = _codes(rng, 100_000, 2)
+    codes = torch.from_numpy(codes_h.view(np.int64)).to(dev)
+    idx = _lib.HammingIndex(codes.data_ptr(), n=codes_h.shape[0], words=2, device_ptr=True, keepalive=codes)
+    k, nq, calls = 10, 4, 7
+    qs = [rng.integers(0, 2 ** 64, size=(nq, 2), dtype=np.uint64) for _ in range(calls)]
+    qs[3][1] = codes_h[4567]
+    want = [idx.search(q, k) for q in qs]
+    qd = [torch.from_numpy(q.view(np.int64)).to(dev) for q in qs]
+    od = [torch.zeros((nq, k), dtype=torch.int32, device=dev) for _ in qs]
+    oi = [torch.zeros((nq, k), dtype=torch.int64, device=dev) for _ in qs]
+    idx.set_option("hamming_async_depth", 3)
+    for j in range(calls):
+        if j == calls - 1:
+            idx.set_option("hamming_async_depth", 2)
+        idx.search_device_async(qd[j].data_ptr(), nq, k, od[j].data_ptr(), oi[j].data_ptr(), _stream())
+    for f in range(calls - 1):                          # before sync: the depth change has drained them
+        np.testing.assert_array_equal(od[f].cpu().numpy(), want[f][0])
+        np.testing.assert_array_equal(oi[f].cpu().numpy(), want[f][1])
+    idx.sync()
+    np.testing.assert_array_equal(od[-1].cpu().numpy(), want[-1][0])
+    np.testing.assert_array_equal(oi[-1].cpu().numpy(), want[-1][1])
+    idx.close()
+
+
+def test_host_calls_either_side_of_the_staging_limit():
+    """Calls with host memory carry their queries and answers through a pinned block up to 1 MiB in total
+    (PinnedStage::kStageMax) and copy directly beyond it.  Every entry point that does so -- dense and Hamming search,
+    IVF search, RowMatrix.rerank -- at the largest query count that still stages and at one query more: the answers are
+    those of the same call with device memory, bit for bit.  (The re-rank has no device-memory form: with every row a
+    candidate, in row order, its (distance, position) answer is the dense index's (distance, row) one.)"""
+    stage_max, k, n, d = 1 << 20, 64, 4096, 32
+    rng = np.random.default_rng(2718)
+    dev = _dev()
+    rows = rng.standard_normal((n, d)).astype(np.float32)
+    codes = _codes(rng, n, 1)
+    every_row = np.arange(n, dtype=np.int64)
+
+    def largest_staged(total):                          # the largest nq with total(nq) <= stage_max
+        nq = 1
+        while total(nq + 1) <= stage_max:
+            nq += 1
+        assert total(nq) <= stage_max < total(nq + 1)
+        return nq
+
+    # what each entry point announces to the stage: inputs + outputs, in bytes
+    dense_total = lambda nq: nq * d * 4 + nq * k * (4 + 8)             # noqa: E731 -- float32 queries, float32 + int64 out
+    hamming_total = lambda nq: nq * 1 * 8 + nq * k * (4 + 8)           # noqa: E731 -- one-word codes, int32 + int64 out
+    rerank_total = lambda nq: nq * d * 4 + nq * n * 8 + (nq + 1) * 8 + nq * k * (4 + 8)   # noqa: E731 -- + candidates, offsets
+
+    dense = _lib.DenseIndex(rows)
+    hamming = _lib.HammingIndex(codes)
+    ivf = _lib.IvfIndex(rows[:16].copy())
+    ivf.add(rows)
+    matrix = _lib.RowMatrix(rows)
+    try:
+        for nq0, what in ((largest_staged(dense_total), "dense"), (largest_staged(dense_total), "ivf"),
+                          (largest_staged(hamming_total), "hamming"), (largest_staged(rerank_total), "rerank")):
+            for nq in (nq0, nq0 + 1):
+                if what == "hamming":
+                    q = rng.integers(0, 2 ** 64, size=(nq, 1), dtype=np.uint64)
+                    qd = torch.from_numpy(q.view(np.int64)).to(dev)
+                    dist_d = torch.empty((nq, k), dtype=torch.int32, device=dev)
+                else:
+                    q = rng.standard_normal((nq, d)).astype(np.float32)
+                    qd = torch.from_numpy(q).to(dev)
+                    dist_d = torch.empty((nq, k), dtype=torch.float32, device=dev)
+                idx_d = torch.empty((nq, k), dtype=torch.int64, device=dev)
+                if what == "dense":
+                    dist, idx = dense.search(q, k)
+                    dense.search_device(qd.data_ptr(), nq, k, dist_d.data_ptr(), idx_d.data_ptr(), _stream())
+                elif what == "ivf":
+                    dist, idx = ivf.search(q, k, 16)
+                    ivf.search_device(qd.data_ptr(), nq, k, 16, dist_d.data_ptr(), idx_d.data_ptr(), _stream())
+                elif what == "hamming":
+                    dist, idx = hamming.search(q, k)
+                    hamming.search_device(qd.data_ptr(), nq, k, dist_d.data_ptr(), idx_d.data_ptr(), _stream())
+                else:
+                    dist, idx = matrix.rerank(q, _lib.SQ_METRIC_L2, np.tile(every_row, nq), np.arange(nq + 1, dtype=np.int64) * n, k)
+                    dense.search_device(qd.data_ptr(), nq, k, dist_d.data_ptr(), idx_d.data_ptr(), _stream())
+                torch.cuda.synchronize()
+                np.testing.assert_array_equal(idx, idx_d.cpu().numpy(), err_msg="%s, %d queries" % (what, nq))
+                np.testing.assert_array_equal(dist.view(np.uint32), dist_d.cpu().numpy().view(np.uint32),
+                                              err_msg="%s, %d queries" % (what, nq))
+    finally:
+        for h in (dense, hamming, ivf, matrix):
+            h.close()
+
+
 # ------------------------------------------------------------------------- dynamic-LDS attributes per device
 def test_second_device_gets_its_lds_attributes():
     """The dynamic-LDS limit of a kernel belongs to one device's copy of it: the kernels that launch with more than
