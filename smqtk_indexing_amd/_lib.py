@@ -64,6 +64,14 @@ IVF_LIB_NAME = "libsmqtk_hip_ivf.so"
 IVF_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), IVF_LIB_NAME)
 IVF_EXPORTS = ("sq_ivf_kmeans", "sq_ivf_create", "sq_ivf_add", "sq_ivf_lists", "sq_ivf_info", "sq_ivf_search", "sq_ivf_destroy")
 
+# The IVF-PQ extension library (include/smqtk_hip_pq.h), beside the other two and built on top of both.
+PQ_LIB_NAME = "libsmqtk_hip_pq.so"
+PQ_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), PQ_LIB_NAME)
+PQ_EXPORTS = ("sq_pq_train", "sq_pq_create", "sq_pq_add", "sq_pq_lists", "sq_pq_info", "sq_pq_search", "sq_pq_destroy")
+SQ_PQ_INFO_FIELDS = 10      # words of sq_pq_info (smqtk_hip_pq.h)
+SQ_PQ_MAX_M = 64            # sub-quantisers of an IVF-PQ index: a query's tables stay within 64 KiB of LDS
+SQ_PQ_MAX_KSUB = 256        # entries per codebook: one byte per code
+
 
 class HipError(RuntimeError):
     """A libsmqtk_hip call failed (or the library could not be loaded)."""
@@ -212,6 +220,36 @@ def load_ivf() -> ctypes.CDLL:
         return _ivf_lib
 
 
+_pq_lib: Optional[ctypes.CDLL] = None
+
+
+def load_pq() -> ctypes.CDLL:
+    """Load the IVF-PQ extension library (once), after the two libraries it is built on.  Raises HipError when it is
+    missing: there is no fallback."""
+    global _pq_lib
+    load_ivf()
+    with _lock:
+        if _pq_lib is None:
+            if not os.path.isfile(PQ_LIB_PATH):
+                raise HipError(f"{PQ_LIB_NAME} not found at {PQ_LIB_PATH}; build it with `make -C smqtk_indexing_amd/csrc`")
+            try:
+                lib = ctypes.CDLL(PQ_LIB_PATH)
+            except OSError as ex:
+                raise HipError(f"cannot load {PQ_LIB_PATH}: {ex}") from ex
+            c_int, c_i64, c_vp = ctypes.c_int, ctypes.c_int64, ctypes.c_void_p
+            lib.sq_pq_train.argtypes = [c_vp, c_i64, c_int, c_int, c_int, c_vp, c_int, c_int]
+            lib.sq_pq_create.argtypes = [c_vp, c_int, c_int, c_vp, c_int, c_int, c_i64, ctypes.POINTER(c_i64)]
+            lib.sq_pq_add.argtypes = [c_i64, c_vp, c_i64, c_int]
+            lib.sq_pq_lists.argtypes = [c_i64, c_vp, c_vp, c_vp]
+            lib.sq_pq_info.argtypes = [c_i64, ctypes.POINTER(c_i64), c_int]
+            lib.sq_pq_search.argtypes = [c_i64, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_int, c_vp]
+            lib.sq_pq_destroy.argtypes = [c_i64]
+            for name in PQ_EXPORTS:
+                getattr(lib, name).restype = c_int
+            _pq_lib = lib
+        return _pq_lib
+
+
 def _check(rc: int, what: str) -> None:
     if rc != SQ_OK:
         msg = load().sq_last_error()
@@ -242,6 +280,11 @@ def usable() -> bool:
 def ivf_usable() -> bool:
     """A GPU, the main library and the IVF-Flat extension library beside it."""
     return usable() and os.path.isfile(IVF_LIB_PATH)
+
+
+def pq_usable() -> bool:
+    """A GPU, the main library and both extension libraries beside it."""
+    return ivf_usable() and os.path.isfile(PQ_LIB_PATH)
 
 
 def device_name(device: int = 0) -> Tuple[str, int, int]:
@@ -697,6 +740,103 @@ class IvfIndex(_Handle):
     def info(self) -> dict:
         out = (ctypes.c_int64 * SQ_IVF_INFO_FIELDS)()
         _check(load_ivf().sq_ivf_info(self.handle, out, SQ_IVF_INFO_FIELDS), "sq_ivf_info")
+        return dict(zip(self.INFO_FIELDS, (int(v) for v in out)))
+
+
+def pq_train(x: np.ndarray, codebooks: np.ndarray, iters: int = 10) -> np.ndarray:
+    """``sq_pq_train``: codebook ``j`` of ``codebooks`` (``[m, ksub, d / m]`` float32, the initial entries) becomes
+    :func:`ivf_kmeans` over ``x[:, j * dsub:(j + 1) * dsub]``; returns the trained codebooks.  Deterministic."""
+    x = _host(x, np.float32)
+    c = np.array(codebooks, dtype=np.float32, order="C", copy=True)
+    if x.ndim != 2 or c.ndim != 3 or c.shape[0] * c.shape[2] != x.shape[1]:
+        raise ValueError("x must be [n, d] and codebooks [m, ksub, d / m]")
+    _check(load_pq().sq_pq_train(_ptr(x), int(x.shape[0]), int(x.shape[1]), int(c.shape[0]), int(c.shape[1]), _ptr(c), int(iters),
+                                 SQ_MEM_HOST), "sq_pq_train")
+    return c
+
+
+class PqIndex(_Handle):
+    """Inverted lists of product-quantiser codes (``sq_pq_*``): a row is kept as ``m`` bytes in the list of its nearest
+    centroid, a search adds ``m`` table entries per row of the ``nprobe`` nearest lists.  L2 only.  Use as a context
+    manager or ``close()`` it."""
+    _destroy_name = "sq_pq_destroy"
+    INFO_FIELDS = ("rows", "d", "nlist", "m", "ksub", "codes_bytes", "ids_offsets_bytes", "books_coarse_bytes", "add_us",
+                   "key_budget_bytes")
+
+    def close(self) -> None:
+        if self.handle:
+            h, self.handle = self.handle, 0
+            try:
+                load_pq().sq_pq_destroy(h)
+            except Exception:
+                pass
+
+    def __init__(self, centroids: np.ndarray, codebooks: np.ndarray, id_base: int = 0):
+        super().__init__()
+        c = _host(centroids, np.float32)
+        b = _host(codebooks, np.float32)
+        if c.ndim != 2 or b.ndim != 3 or b.shape[0] * b.shape[2] != c.shape[1]:
+            raise ValueError("centroids must be float32[nlist, d] and codebooks float32[m, ksub, d / m]")
+        self.nlist, self.d, self.id_base, self.n = int(c.shape[0]), int(c.shape[1]), int(id_base), 0
+        self.m, self.ksub = int(b.shape[0]), int(b.shape[1])
+        h = ctypes.c_int64(0)
+        _check(load_pq().sq_pq_create(_ptr(c), self.nlist, self.d, _ptr(b), self.m, self.ksub, self.id_base, ctypes.byref(h)),
+               "sq_pq_create")
+        self.handle = int(h.value)
+
+    def __enter__(self) -> "PqIndex":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+    def add(self, rows, n: Optional[int] = None, device_ptr: bool = False) -> None:
+        """Rows (``[r, d]`` float32 host array, or a device pointer + ``n``) are coded into their lists; they get the
+        next insertion numbers (``sq_pq_add``).  The rows themselves are not kept."""
+        if device_ptr:
+            assert n is not None
+            ptr, mem, r = _ptr(rows), SQ_MEM_DEVICE, int(n)
+        else:
+            rows = _host(rows, np.float32)
+            if rows.ndim != 2 or rows.shape[1] != self.d:
+                raise ValueError("rows must be float32[r, d]")
+            ptr, mem, r = _ptr(rows), SQ_MEM_HOST, int(rows.shape[0])
+        if r == 0:
+            return
+        _check(load_pq().sq_pq_add(self.handle, ptr, r, mem), "sq_pq_add")
+        self.n += r
+
+    def search(self, queries: np.ndarray, k: int, nprobe: int = 1) -> Tuple[np.ndarray, np.ndarray]:
+        """(coded dist float32 ``[nq, k]``, ids int64 ``[nq, k]``) of the ``k`` nearest rows among the lists of the
+        ``nprobe`` nearest centroids; ``-1`` / ``+inf`` behind the last candidate."""
+        q = _host(queries, np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        if q.shape[1] != self.d:
+            raise ValueError("query dimension does not match the index")
+        nq = q.shape[0]
+        dist = np.empty((nq, k), dtype=np.float32)
+        idx = np.empty((nq, k), dtype=np.int64)
+        _check(load_pq().sq_pq_search(self.handle, _ptr(q), nq, int(k), int(nprobe), _ptr(dist), _ptr(idx), SQ_MEM_HOST, None),
+               "sq_pq_search")
+        return dist, idx
+
+    def search_device(self, q_ptr: int, nq: int, k: int, nprobe: int, out_dist_ptr: int, out_idx_ptr: int, stream: int = 0) -> None:
+        """Device pointers throughout; blocking, as :meth:`search`."""
+        _check(load_pq().sq_pq_search(self.handle, _ptr(q_ptr), int(nq), int(k), int(nprobe), _ptr(out_dist_ptr), _ptr(out_idx_ptr),
+                                      SQ_MEM_DEVICE, ctypes.c_void_p(stream or None)), "sq_pq_search")
+
+    def lists(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(``list_off[nlist + 1]``, ids of all rows, their codes uint8 ``[rows, m]``), list by list -- ``sq_pq_lists``."""
+        off = np.empty(self.nlist + 1, dtype=np.int64)
+        ids = np.empty(self.n, dtype=np.int64)
+        codes = np.empty((self.n, self.m), dtype=np.uint8)
+        _check(load_pq().sq_pq_lists(self.handle, _ptr(off), _ptr(ids) if self.n else None, _ptr(codes) if self.n else None), "sq_pq_lists")
+        return off, ids, codes
+
+    def info(self) -> dict:
+        out = (ctypes.c_int64 * SQ_PQ_INFO_FIELDS)()
+        _check(load_pq().sq_pq_info(self.handle, out, SQ_PQ_INFO_FIELDS), "sq_pq_info")
         return dict(zip(self.INFO_FIELDS, (int(v) for v in out)))
 
 

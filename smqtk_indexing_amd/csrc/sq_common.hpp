@@ -100,7 +100,7 @@ inline hipError_t event_wait(hipEvent_t ev) {
 namespace sq {
 
 // ------------------------------------------------------------------ handles
-enum HandleKind { H_HAMMING = 1, H_DENSE = 2, H_ROWS = 3, H_FIT = 4, H_ITQ = 5, H_IVF = 6 };
+enum HandleKind { H_HAMMING = 1, H_DENSE = 2, H_ROWS = 3, H_FIT = 4, H_ITQ = 5, H_IVF = 6, H_PQ = 7 };
 
 struct HandleBase {
     int kind = 0;

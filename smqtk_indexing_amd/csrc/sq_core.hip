@@ -132,7 +132,7 @@ extern "C" int sq_set_option(const char* name, int64_t value) {
 }
 
 static HandleBase* any_handle(sq_handle_t hid) {
-    for (int kind : {H_DENSE, H_HAMMING, H_ROWS, H_FIT, H_ITQ, H_IVF})
+    for (int kind : {H_DENSE, H_HAMMING, H_ROWS, H_FIT, H_ITQ, H_IVF, H_PQ})
         if (HandleBase* h = lookup_handle(hid, kind)) return h;
     return nullptr;
 }
@@ -175,6 +175,7 @@ extern "C" int sq_get_stats(sq_handle_t hid, sq_stats_t* out) {
     if (!h) h = lookup_handle(hid, H_HAMMING);
     if (!h) h = lookup_handle(hid, H_ITQ);   // (the last sq_itq_model_hash: which path hashed the rows, smqtk_hip.h)
     if (!h) h = lookup_handle(hid, H_IVF);   // (the last sq_ivf_search: slices, rows and bytes scanned)
+    if (!h) h = lookup_handle(hid, H_PQ);    // (the last sq_pq_search: slices, rows and code bytes scanned)
     if (!h) return fail(SQ_ERR_INVALID, "sq_get_stats: unknown handle");
     std::lock_guard<std::mutex> l(h->mu);
     *out = h->stats;

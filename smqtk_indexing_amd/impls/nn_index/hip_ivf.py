@@ -34,7 +34,41 @@ def default_nlist(n: int) -> int:
     return max(1, min(int(n), int(4 * math.sqrt(n))))
 
 
-class HipIvfFlatNearestNeighborsIndex(NearestNeighborsIndex):
+def training_draws(n: int, nlist: int, random_seed: int) -> Tuple[np.ndarray, np.ndarray, np.random.RandomState]:
+    """(sample rows, positions of the initial centroids inside the sample, the generator after both draws) for ``n``
+    rows and ``nlist`` lists: at most 256 rows per list drawn without replacement, then ``nlist`` distinct sample rows,
+    both from ``RandomState(random_seed)``.  (The IVF-PQ class draws its initial codebook entries from the generator
+    next.)"""
+    rs = np.random.RandomState(random_seed)
+    m = min(int(n), TRAIN_ROWS_PER_LIST * nlist)
+    sample = np.sort(rs.choice(n, size=m, replace=False)) if m < n else np.arange(n)
+    init = rs.choice(m, size=nlist, replace=False)
+    return sample, init, rs
+
+
+class _ListIndexHostLogic:
+    """What the inverted-list plugin classes (IVF-Flat here, IVF-PQ in hip_ivf_pq.py) share on the host: the matrix of a
+    set of descriptors, the read-only guard and the ``nlist`` rule.  Expects ``self.nlist`` and ``self.read_only``."""
+
+    @staticmethod
+    def _to_matrix(elements: Sequence[DescriptorElement]) -> np.ndarray:
+        vecs = [e.vector() for e in elements]
+        if any(v is None for v in vecs):
+            raise ValueError("descriptor without a vector cannot be indexed")
+        return np.ascontiguousarray(np.vstack(vecs), dtype=np.float32)
+
+    def _guard(self) -> None:
+        if self.read_only:
+            raise ReadOnlyError("Cannot modify container attributes due to "
+                                "being in read-only mode.")
+
+    def effective_nlist(self, n: int) -> int:
+        """The lists an index of ``n`` rows is trained with: the configured number clamped to ``n``, or ``4 sqrt(n)``."""
+        nlist = default_nlist(n) if self.nlist is None else min(self.nlist, int(n))
+        return max(1, min(nlist, _lib.SQ_IVF_MAX_LISTS))
+
+
+class HipIvfFlatNearestNeighborsIndex(_ListIndexHostLogic, NearestNeighborsIndex):
     """L2 kNN over the lists of the ``nprobe`` nearest k-means centroids (HIP kernels)."""
 
     @classmethod
@@ -79,31 +113,10 @@ class HipIvfFlatNearestNeighborsIndex(NearestNeighborsIndex):
             self._blocks = [np.ascontiguousarray(np.vstack(self._blocks), dtype=np.float32)]
         return self._blocks[0]
 
-    @staticmethod
-    def _to_matrix(elements: Sequence[DescriptorElement]) -> np.ndarray:
-        vecs = [e.vector() for e in elements]
-        if any(v is None for v in vecs):
-            raise ValueError("descriptor without a vector cannot be indexed")
-        return np.ascontiguousarray(np.vstack(vecs), dtype=np.float32)
-
-    def _guard(self) -> None:
-        if self.read_only:
-            raise ReadOnlyError("Cannot modify container attributes due to "
-                                "being in read-only mode.")
-
-    def effective_nlist(self, n: int) -> int:
-        """The lists an index of ``n`` rows is trained with: the configured number clamped to ``n``, or ``4 sqrt(n)``."""
-        nlist = default_nlist(n) if self.nlist is None else min(self.nlist, int(n))
-        return max(1, min(nlist, _lib.SQ_IVF_MAX_LISTS))
-
     def training_plan(self, n: int) -> Tuple[np.ndarray, np.ndarray]:
         """(sample rows, positions of the initial centroids inside the sample) for ``n`` rows: at most 256 rows per
         list drawn without replacement, then ``nlist`` distinct sample rows, both from ``RandomState(random_seed)``."""
-        nlist = self.effective_nlist(n)
-        rs = np.random.RandomState(self.random_seed)
-        m = min(int(n), TRAIN_ROWS_PER_LIST * nlist)
-        sample = np.sort(rs.choice(n, size=m, replace=False)) if m < n else np.arange(n)
-        init = rs.choice(m, size=nlist, replace=False)
+        sample, init, _ = training_draws(n, self.effective_nlist(n), self.random_seed)
         return sample, init
 
     def _set_lists(self, elements: List[DescriptorElement], matrix: np.ndarray) -> None:
