@@ -63,6 +63,15 @@ extern "C" {
  * Limits, refused before a device is touched: d % m != 0, m outside 1 .. 64, ksub outside 1 .. 256: SQ_ERR_INVALID;
  * nlist > 65536, a search mode other than the two blocking ones, and d / m > 16384 (pq_tables_kernel stages a query's
  * sub-vector in round_up(d / m, 4) * 4 <= 65536 bytes of dynamic LDS, what a plain launch takes): SQ_ERR_UNSUPPORTED.
+ * d itself has no limit of its own: up to m * 16384.  The coarse index assigns and probes rows of any such width -- its
+ * exact kernel stages a query of up to 40960 floats whole in a workgroup's LDS and a wider one two of numpy's
+ * 8192-element buffers at a time (dense_exact_l2_pieces_kernel).  Before the tests ran m = 3 at d / m = 16384 an add of
+ * rows wider than 40960 floats failed with SQ_ERR_HIP (a launch asking for more LDS than a workgroup has).
+ * Run by the tests (tests/test_hip_pq.py): every m from 1 to 64 (padded code strides, both loads, both ways of staging
+ * the tables), ksub 1, 13, 16, 255 and 256, m * ksub * 4 = 65536 bytes of tables, d / m at the 58 widths of
+ * tests/width_cases.py and at 8193, 8199, 8200 and 16384 (65536 bytes of dynamic LDS pass pq_tables_kernel's plain launch),
+ * scan workgroups that walk up to 16 chunks each, 700 lists, option "profile" 1 and 2, id_base beyond 2^32, a query
+ * whose tables overflow to +inf (real ids ascending at +inf, -1 only behind the last candidate).
  * Left out on purpose: residual coding, OPQ rotations, code sizes other than one byte, a refine stage over kept float32
  * rows, cosine, asynchronous calls, removal in place, retraining. */
 #define SQ_PQ_INFO_FIELDS 10

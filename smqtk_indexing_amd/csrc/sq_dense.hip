@@ -583,6 +583,17 @@ static DenseSurvivors dense_slot_survivors(const DenseHandle* h, DenseSlot& s, l
     return v;
 }
 
+// Exact L2 keys of all n rows for the queries of grid.y (dense_exact_l2_kernel: the query staged in LDS; rows too wide for
+// that: dense_exact_l2_pieces_kernel, one row per lane)
+static int dense_exact_l2_keys(dim3 grid, hipStream_t st, const float* db, long long ld, int d, const float* q, const u32* cnt, long long n, u64* keys,
+                               long long key_stride, float* sample, int sample_stride, const u32* dead) {
+    if (dense_exact_stages_whole(d))
+        return launch<dense_exact_l2_kernel>(grid, dim3(256), (size_t)((d + 3) / 4 * 4) * 4, st, db, ld, d, q, nullptr, cnt, (u32)n, n, 0ll, keys, key_stride,
+                                             sample, sample_stride, dead);
+    return launch<dense_exact_l2_pieces_kernel>(dim3((unsigned)((n + 255) / 256), grid.y), dim3(256), (size_t)kExactPiece * 4, st, db, ld, d, q, nullptr, cnt,
+                                                (u32)n, n, 0ll, keys, key_stride, sample, sample_stride, dead);
+}
+
 // ---- every row is a candidate (n <= cap): exact keys for all rows, no scan
 static int dense_small_enqueue(DenseHandle* h, DenseSlot& s, const DenseCtx& e) {
     const long long n = h->n;
@@ -603,8 +614,7 @@ static int dense_small_enqueue(DenseHandle* h, DenseSlot& s, const DenseCtx& e) 
             SQ_TRY(launch<dense_exact_cos_kernel>(grid, dim3(256), 0, st, h->db, h->ld, d, c.q, nullptr, e.cnt, (u32)n, n, 0ll, keys, e.key_stride,
                                                   h->cos_nx.as<double>(), e.cnq, nullptr, 0, h->deadp()));
         else
-            SQ_TRY(launch<dense_exact_l2_kernel>(grid, dim3(256), (size_t)((d + 3) / 4 * 4) * 4, st, h->db, h->ld, d, c.q, nullptr, e.cnt, (u32)n, n,
-                                                 0ll, keys, e.key_stride, nullptr, 0, h->deadp()));
+            SQ_TRY(dense_exact_l2_keys(grid, st, h->db, h->ld, d, c.q, e.cnt, n, keys, e.key_stride, nullptr, 0, h->deadp()));
         if (c.prof) SQ_HIP(hipEventRecord(s.ev[2], st));
         auto fin = M::finalize(e, e.cnt, (u32)n, 0);
         fin.cnt_out = e.hs_cnt_dev;
@@ -1499,8 +1509,8 @@ static int dense_exact_path(DenseHandle* h, DenseSlot& s, const DenseCtx& e, con
                     SQ_TRY(launch<dense_exact_cos_kernel>(dim3(gx, 1), dim3(256), 0, st, h->db, h->ld, d, c.q + (long long)qi * d, nullptr, full_cnt + qi,
                                                           (u32)n, n, 0ll, big, n, cnx, e.cnq + qi, fb_sample, (int)fb_stride, deadp));
                 else
-                    SQ_TRY(launch<dense_exact_l2_kernel>(dim3(gx, 1), dim3(256), (size_t)((d + 3) / 4 * 4) * 4, st, h->db, h->ld, d, c.q + (long long)qi * d,
-                                                         nullptr, full_cnt + qi, (u32)n, n, 0ll, big, n, fb_sample, (int)fb_stride, deadp));
+                    SQ_TRY(dense_exact_l2_keys(dim3(gx, 1), st, h->db, h->ld, d, c.q + (long long)qi * d, full_cnt + qi, n, big, n, fb_sample,
+                                               (int)fb_stride, deadp));
             }
             if (fb_stride) {
                 SQ_TRY(launch<kth_threshold_f32_kernel<KthIdentity>>(dim3(gn), dim3(1024), 0, st, fb_sample, fb_ns, e.kk, fb_thr, KthIdentity{}));

@@ -238,6 +238,53 @@ static __global__ __launch_bounds__(256) void dense_exact_l2_kernel(const float*
     }
 }
 
+// dense_exact_l2_kernel for rows whose query no workgroup's LDS holds (round_up(d, 4) * 4 bytes beyond kExactStageMax).
+// numpy adds such a row buffer by buffer (PW_BUFSIZE elements each summed pairwise, the buffers' sums added in order:
+// pw_tree), so the query is staged kExactPiece elements -- whole buffers -- at a time and every lane carries ITS row's
+// running total from piece to piece.  One candidate per lane: gridDim.x * 256 >= M.  Dynamic LDS: kExactPiece * 4 bytes.
+static constexpr int kExactStageMax = 160 * 1024;
+static constexpr int kExactPiece = 2 * PW_BUFSIZE;
+inline bool dense_exact_stages_whole(int d) { return (long long)((d + 3) / 4 * 4) * 4 <= kExactStageMax; }
+static __global__ __launch_bounds__(256) void dense_exact_l2_pieces_kernel(const float* __restrict__ db, long long ld, int d,
+                                                                     const float* __restrict__ q_orig,
+                                                                     const u32* __restrict__ cand, const u32* __restrict__ cnt,
+                                                                     u32 cap, long long implicit_n, long long row_offset,
+                                                                     u64* __restrict__ keys, long long key_stride,
+                                                                     float* __restrict__ sample, int sample_stride,
+                                                                     const u32* __restrict__ dead = nullptr) {
+    extern __shared__ __attribute__((aligned(16))) float s_q[];
+    const int q = blockIdx.y;
+    const long long M = cand ? (long long)(cnt[q] < cap ? cnt[q] : cap) : implicit_n;
+    if ((long long)blockIdx.x * 256 >= M) return;
+    const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
+    const bool live = j < M;   // (a lane without a candidate stays for the barriers)
+    const long long row = !live ? 0 : cand ? (long long)cand[(long long)q * cap + j] : row_offset + j;
+    const bool sum = live && !dense_row_dead(dead, row);
+    float total = 0.f;
+    for (int s0 = 0; s0 < d; s0 += kExactPiece) {
+        const int len = d - s0 < kExactPiece ? d - s0 : kExactPiece;
+        if (s0) __syncthreads();
+        for (int i = threadIdx.x; i < len; i += 256) s_q[i] = q_orig[(long long)q * d + s0 + i];
+        __syncthreads();
+        if (sum) {
+            const SqLeafLane w{db + row * ld + s0, s_q};
+            for (int b = 0; b < len; b += PW_BUFSIZE) {
+                const float part = pw_tree_buffer<float>([&w](int off, int n) { return w.leaf(off, n); }, b, len - b < PW_BUFSIZE ? len - b : PW_BUFSIZE);
+                total = s0 + b == 0 ? part : __fadd_rn(total, part);
+            }
+        }
+    }
+    if (!live) return;
+    if (!sum) {   // a removed row: no distance, no sample
+        keys[(long long)q * key_stride + j] = dense_dead_key(u64{}, row);
+        if (sample && j % sample_stride == 0) sample[j / sample_stride] = __builtin_inff();
+        return;
+    }
+    const float dist = sqrt_rn_f32(total);
+    keys[(long long)q * key_stride + j] = ((u64)ordered_f32(dist) << 32) | (u64)(u32)row;
+    if (sample && j % sample_stride == 0) sample[j / sample_stride] = dist == dist ? dist : __builtin_inff();
+}
+
 static __global__ __launch_bounds__(256) void dense_exact_cos_kernel(const float* __restrict__ db, long long ld, int d,
                                                                const float* __restrict__ q_orig,
                                                                const u32* __restrict__ cand, const u32* __restrict__ cnt,

@@ -113,6 +113,19 @@ static void wide() {
     CHECK(pq_scan_groups(ivf_chunks(n), 1, 256) == 1048576 && pq_scan_groups(ivf_chunks(n), 1, 256) * kPqChunksPerGroup * kIvfChunk >= n);
 }
 
+// pq_scan_groups on the triples the strided-scan tests are cut for (tests/pq_cases.py restates the function in Python;
+// tests/test_host_logic_pq.py compares the two line by line): "groups <chunks> <nq> <cus> <value>"
+static void print_groups() {
+    const long long cus[] = {1, 64, 80, 128, 256, 304};
+    const long long nqs[] = {0, 1, 33, 50, 64, 70, 600, 70000};
+    for (long long cu : cus)
+        for (long long nq : nqs) {
+            for (long long ch = 0; ch <= 64; ++ch) printf("groups %lld %lld %lld %lld\n", ch, nq, cu, pq_scan_groups(ch, nq, cu));
+            printf("groups 611 %lld %lld %lld\n", nq, cu, pq_scan_groups(611, nq, cu));
+            printf("groups 16777216 %lld %lld %lld\n", nq, cu, pq_scan_groups(16777216, nq, cu));
+        }
+}
+
 int main() {
     shapes();
     stride();
@@ -120,6 +133,7 @@ int main() {
     groups();
     slices();
     wide();
+    print_groups();
     printf("pq plan ok: max_m=%d max_ksub=%d chunks_per_group=%d lds_max=%lld\n", kPqMaxM, kPqMaxKsub, kPqChunksPerGroup,
            pq_table_bytes(kPqMaxM, kPqMaxKsub));
     return 0;

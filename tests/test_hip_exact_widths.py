@@ -224,3 +224,37 @@ def test_int8_fused_tail_rerank_at_width(metric, d):
             _assert_topk(metric, dist[qi], ids[qi], rd, ri, "query %d" % qi)
     finally:
         idx.close()
+
+
+# ---- 6. L2 rows wider than a workgroup's LDS holds (160 KiB: 40 960 floats): dense_exact_l2_pieces_kernel stages the
+# query two of numpy's 8192-element buffers at a time; 40 960 is the widest row still staged whole
+@pytest.mark.parametrize("d", [40960, 40961, 3 * 16384, 3 * 16384 + 5])
+def test_l2_rows_wider_than_the_lds(d):
+    n, nq = 300, 3
+    rng = np.random.default_rng([6, d])
+    db = rng.standard_normal((n, d), dtype=np.float32) * np.float32(3)
+    db[200] = db[20]
+    qs = rng.standard_normal((nq, d), dtype=np.float32) * np.float32(3)
+    qs[0] = db[20]
+    qs[2] = db[131] + NOISE * rng.standard_normal(d, dtype=np.float32)
+    ref = [O.dense_topk(db, q, K) for q in qs]
+    assert ref[0][1][:2].tolist() == [20, 200]
+    # every row a candidate: exact keys for all rows of all queries in one launch
+    idx = _lib.DenseIndex(db)
+    try:
+        dist, ids = idx.search(qs, K)
+        for qi in range(nq):
+            _assert_topk("euclidean", dist[qi], ids[qi], ref[qi][0], ref[qi][1], "all rows, query %d" % qi)
+    finally:
+        idx.close()
+    # the exact path, forced: one query per pass
+    idx = _lib.DenseIndex(db, options={"candidate_cap": n - 1, "dense_int8": 0})
+    try:
+        idx.set_option("force_fallback", 1)
+        idx.set_option("dense_mid_tier", 0)
+        dist, ids = idx.search(qs, K)
+        assert idx.stats()["fallback_queries"] == nq
+        for qi in range(nq):
+            _assert_topk("euclidean", dist[qi], ids[qi], ref[qi][0], ref[qi][1], "exact path, query %d" % qi)
+    finally:
+        idx.close()

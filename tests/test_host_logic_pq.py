@@ -357,3 +357,17 @@ def test_plan_arithmetic_under_sanitizers(tmp_path):
         assert word not in r.stdout, r.stdout[-4000:]
     fields = dict(w.split("=") for w in r.stdout.split("pq plan ok:")[1].split())
     assert (int(fields["max_m"]), int(fields["max_ksub"]), int(fields["lds_max"])) == (_lib.SQ_PQ_MAX_M, _lib.SQ_PQ_MAX_KSUB, 65536)
+    # the Python restatement of pq_scan_groups (tests/pq_cases.py) against the real function, line by line
+    from tests import pq_cases
+    real = {tuple(map(int, ln.split()[1:4])): int(ln.split()[4]) for ln in r.stdout.splitlines() if ln.startswith("groups ")}
+    assert len(real) > 3000
+    for (chunks, nq, cus), g in real.items():
+        assert pq_cases.pq_scan_groups(chunks, nq, cus) == g, (chunks, nq, cus, g)
+    # ... and the triples the strided-scan tests run are among them, in the regime each is meant for
+    for d, m in pq_cases.S_SHAPES:
+        case = pq_cases.make_strided_case(d, m)
+        for nprobe in pq_cases.S_NPROBES:
+            for nq in pq_cases.S_NQS:
+                plan = pq_cases.strided_plan(case, nprobe, nq, pq_cases.S_CUS)
+                assert real[(plan["chunks"], nq, pq_cases.S_CUS)] == plan["groups"]
+                pq_cases.assert_regime(plan, nq, case.what)
