@@ -26,7 +26,7 @@ extern "C" {
  *             ties to the lowest list: IVF-Flat's rule.
  *   code      code[j] is the nearest entry of codebook j to the row's own sub-vector x_j, same arithmetic, ties to the
  *             lowest entry.  The row is NOT coded as a residual against its centroid: one set of tables serves a query in
- *             every list it probes.  On the device both are sq_dense_search with k = 1, over the coarse index and over m
+ *             every list it probes (residual mode, below, is the other choice).  On the device both are sq_dense_search with k = 1, over the coarse index and over m
  *             small dense indexes of the codebooks that the handle owns (float32 only, no scan copies).
  *   tables    T[j][c] = np.square(codebooks[j][c] - q_j).sum(): float32 in numpy's pairwise order, the square of
  *             euclidean_distance before its root.
@@ -72,13 +72,49 @@ extern "C" {
  * tests/width_cases.py and at 8193, 8199, 8200 and 16384 (65536 bytes of dynamic LDS pass pq_tables_kernel's plain launch),
  * scan workgroups that walk up to 16 chunks each, 700 lists, option "profile" 1 and 2, id_base beyond 2^32, a query
  * whose tables overflow to +inf (real ids ascending at +inf, -1 only behind the last candidate).
- * Left out on purpose: residual coding, OPQ rotations, code sizes other than one byte, a refine stage over kept float32
+ *
+ * Residual mode (sq_pq_create_residual): the same index with the rows coded as residuals against their list's centroid,
+ * FAISS's default for "IVFx,PQy".  A handle made by sq_pq_create is untouched by it.  With the rules above, float32
+ * without contraction:
+ *   list      unchanged: l(x) is the nearest centroid, ties to the lowest list.
+ *   residual  r = x - centroids[l(x)], element by element.
+ *   code      code[j] is the nearest entry of codebook j to r_j (dense search with k = 1), ties to the lowest entry.
+ *   tables    one set per query and probed list l: rq = q - centroids[l], T_l[j][c] = np.square(codebooks[j][c] - rq_j).sum()
+ *             in numpy's pairwise order.
+ *   distance  of a row of list l: sqrt_rn(((T_l[0][code[0]] + T_l[1][code[1]]) + ...) + T_l[m-1][code[m-1]]), left to right.
+ *   result, padding, ids, k, nprobe: as above.
+ *   sq_pq_create_residual   sq_pq_create's arguments; the handle also keeps the centroids on the device as
+ *                  [nlist][round_up(d, 4)] float32, zero padded, counted in word 7 of sq_pq_info.
+ *   sq_pq_residuals  out = x - centroids[l(x)] row by row (pq_residual_kernel behind the coarse assignment); x and out
+ *                  both in `mem` (host or device; they may be the same buffer), centroids in host memory.  Codebooks for
+ *                  this mode are sq_pq_train over its output.  nlist > 65536, more than 2^26 rows, other modes:
+ *                  SQ_ERR_UNSUPPORTED, before a device is touched.
+ *   sq_pq_add      codes pq_residual_kernel's output instead of the rows; everything else as above.
+ *   sq_pq_search   a pair is (query of the slice, probe position), taken row-major.  pq_tables_res_kernel writes
+ *                  [pair][m][ksub] tables (a pair with an empty list is skipped); pq_scan_res_kernel -- grid (groups,
+ *                  pairs) -- stages its pair's tables in LDS and walks chunks g, g + groups, ... of 256 rows of that
+ *                  pair's list, row i of the list at probe position jl writing its key at candidate pre[jl] + i; the
+ *                  select is the one above.  groups = pq_scan_groups(chunks of the longest list, pairs, CUs).  The key
+ *                  budget: queries per slice as above (one pair's tables counted per query); what the budget has left
+ *                  beside the slice's keys holds the tables of clamp(.., 1, 65535) pairs, and a slice's pairs go in
+ *                  ranges of that many, each one tables launch and one scan launch.  scan_launches counts the ranges;
+ *                  option "profile" = 1 sums scan_ms / rerank_ms over them, 2 behaves as 1.
+ * Run by the tests (tests/test_hip_pq_residual.py): nprobe 1 .. beyond nlist, k beyond the rows, host and device memory,
+ * id_base beyond 2^32, an empty index, a query whose tables overflow, three adds against one, a list of 32 chunks in both
+ * regimes of the scan grid, 64 KiB of tables in ranges that begin inside a query, m from 1 to 64, d / m from 1 to 16384,
+ * sq_pq_residuals in host and device memory (d = 35 from an unaligned base, in place), and one list with a zero
+ * centroid, where the answers are the plain mode's bits.
+ * Left out on purpose: OPQ rotations, FAISS's precomputed-table decomposition of the residual distance, code sizes other than one byte, a refine stage over kept float32
  * rows, cosine, asynchronous calls, removal in place, retraining. */
 #define SQ_PQ_INFO_FIELDS 10
 int sq_pq_train(const float* x, int64_t n, int d, int m, int ksub,
                 float* codebooks /* [m][ksub][d/m]; in: initial, out: trained */, int iters, int mem);
 int sq_pq_create(const float* centroids, int nlist, int d, const float* codebooks, int m, int ksub,
                  int64_t id_base, sq_handle_t* out);
+int sq_pq_create_residual(const float* centroids, int nlist, int d, const float* codebooks, int m, int ksub,
+                          int64_t id_base, sq_handle_t* out);
+int sq_pq_residuals(const float* x, int64_t n, int d, const float* centroids /* [nlist][d], host */, int nlist,
+                    float* out /* [n][d], in `mem` as x */, int mem);
 int sq_pq_add(sq_handle_t h, const float* rows, int64_t n_add, int mem);
 int sq_pq_lists(sq_handle_t h, int64_t* list_off /* [nlist+1] */, int64_t* ids /* [rows] */,
                 uint8_t* codes /* [rows][m], list by list */);

@@ -67,7 +67,7 @@ IVF_EXPORTS = ("sq_ivf_kmeans", "sq_ivf_create", "sq_ivf_add", "sq_ivf_lists", "
 # The IVF-PQ extension library (include/smqtk_hip_pq.h), beside the other two and built on top of both.
 PQ_LIB_NAME = "libsmqtk_hip_pq.so"
 PQ_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), PQ_LIB_NAME)
-PQ_EXPORTS = ("sq_pq_train", "sq_pq_create", "sq_pq_add", "sq_pq_lists", "sq_pq_info", "sq_pq_search", "sq_pq_destroy")
+PQ_EXPORTS = ("sq_pq_train", "sq_pq_create", "sq_pq_create_residual", "sq_pq_residuals", "sq_pq_add", "sq_pq_lists", "sq_pq_info", "sq_pq_search", "sq_pq_destroy")
 SQ_PQ_INFO_FIELDS = 10      # words of sq_pq_info (smqtk_hip_pq.h)
 SQ_PQ_MAX_M = 64            # sub-quantisers of an IVF-PQ index: a query's tables stay within 64 KiB of LDS
 SQ_PQ_MAX_KSUB = 256        # entries per codebook: one byte per code
@@ -239,6 +239,8 @@ def load_pq() -> ctypes.CDLL:
             c_int, c_i64, c_vp = ctypes.c_int, ctypes.c_int64, ctypes.c_void_p
             lib.sq_pq_train.argtypes = [c_vp, c_i64, c_int, c_int, c_int, c_vp, c_int, c_int]
             lib.sq_pq_create.argtypes = [c_vp, c_int, c_int, c_vp, c_int, c_int, c_i64, ctypes.POINTER(c_i64)]
+            lib.sq_pq_create_residual.argtypes = lib.sq_pq_create.argtypes
+            lib.sq_pq_residuals.argtypes = [c_vp, c_i64, c_int, c_vp, c_int, c_vp, c_int]
             lib.sq_pq_add.argtypes = [c_i64, c_vp, c_i64, c_int]
             lib.sq_pq_lists.argtypes = [c_i64, c_vp, c_vp, c_vp]
             lib.sq_pq_info.argtypes = [c_i64, ctypes.POINTER(c_i64), c_int]
@@ -755,10 +757,37 @@ def pq_train(x: np.ndarray, codebooks: np.ndarray, iters: int = 10) -> np.ndarra
     return c
 
 
+def pq_residuals(x: np.ndarray, centroids: np.ndarray) -> np.ndarray:
+    """``sq_pq_residuals``: every row of ``x`` (``[n, d]`` float32, host) minus its nearest centroid (``[nlist, d]``,
+    ties to the lowest list), float32 element by element.  What the codebooks of a residual index are trained on:
+    ``pq_train(pq_residuals(x, centroids), ...)``."""
+    x = _host(x, np.float32)
+    c = _host(centroids, np.float32)
+    if x.ndim != 2 or c.ndim != 2 or c.shape[1] != x.shape[1]:
+        raise ValueError("x must be [n, d] and centroids [nlist, d]")
+    out = np.empty_like(x)
+    if x.shape[0] == 0:
+        return out
+    _check(load_pq().sq_pq_residuals(_ptr(x), int(x.shape[0]), int(x.shape[1]), _ptr(c), int(c.shape[0]), _ptr(out), SQ_MEM_HOST),
+           "sq_pq_residuals")
+    return out
+
+
+def pq_residuals_device(x_ptr: int, n: int, d: int, centroids: np.ndarray, out_ptr: int) -> None:
+    """:func:`pq_residuals` with the rows and the output in device memory (``[n, d]`` float32 each; they may be the
+    same buffer); the centroids stay a host array.  Blocking."""
+    c = _host(centroids, np.float32)
+    if c.ndim != 2 or c.shape[1] != int(d):
+        raise ValueError("centroids must be float32[nlist, d]")
+    _check(load_pq().sq_pq_residuals(_ptr(x_ptr), int(n), int(d), _ptr(c), int(c.shape[0]), _ptr(out_ptr), SQ_MEM_DEVICE),
+           "sq_pq_residuals")
+
+
 class PqIndex(_Handle):
     """Inverted lists of product-quantiser codes (``sq_pq_*``): a row is kept as ``m`` bytes in the list of its nearest
-    centroid, a search adds ``m`` table entries per row of the ``nprobe`` nearest lists.  L2 only.  Use as a context
-    manager or ``close()`` it."""
+    centroid, a search adds ``m`` table entries per row of the ``nprobe`` nearest lists.  ``residual=True``
+    (``sq_pq_create_residual``): the rows are coded as residuals against their list's centroid and a query gets one
+    table set per probed list.  L2 only.  Use as a context manager or ``close()`` it."""
     _destroy_name = "sq_pq_destroy"
     INFO_FIELDS = ("rows", "d", "nlist", "m", "ksub", "codes_bytes", "ids_offsets_bytes", "books_coarse_bytes", "add_us",
                    "key_budget_bytes")
@@ -771,17 +800,17 @@ class PqIndex(_Handle):
             except Exception:
                 pass
 
-    def __init__(self, centroids: np.ndarray, codebooks: np.ndarray, id_base: int = 0):
+    def __init__(self, centroids: np.ndarray, codebooks: np.ndarray, id_base: int = 0, residual: bool = False):
         super().__init__()
         c = _host(centroids, np.float32)
         b = _host(codebooks, np.float32)
         if c.ndim != 2 or b.ndim != 3 or b.shape[0] * b.shape[2] != c.shape[1]:
             raise ValueError("centroids must be float32[nlist, d] and codebooks float32[m, ksub, d / m]")
         self.nlist, self.d, self.id_base, self.n = int(c.shape[0]), int(c.shape[1]), int(id_base), 0
-        self.m, self.ksub = int(b.shape[0]), int(b.shape[1])
+        self.m, self.ksub, self.residual = int(b.shape[0]), int(b.shape[1]), bool(residual)
         h = ctypes.c_int64(0)
-        _check(load_pq().sq_pq_create(_ptr(c), self.nlist, self.d, _ptr(b), self.m, self.ksub, self.id_base, ctypes.byref(h)),
-               "sq_pq_create")
+        name = "sq_pq_create_residual" if self.residual else "sq_pq_create"
+        _check(getattr(load_pq(), name)(_ptr(c), self.nlist, self.d, _ptr(b), self.m, self.ksub, self.id_base, ctypes.byref(h)), name)
         self.handle = int(h.value)
 
     def __enter__(self) -> "PqIndex":

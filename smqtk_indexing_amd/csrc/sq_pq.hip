@@ -9,6 +9,11 @@
 // over the m codebooks; k = nprobe for the probe) or of sq_ivf_kmeans (training).  The grouping of rows by list, the
 // prefix of the probed lists' sizes and the select's post-op are IVF-Flat's (sq_ivf_group.hpp).  New device code is the
 // coded storage, pq_tables_kernel and pq_scan_kernel; the host arithmetic is sq_pq_plan.hpp.
+//
+// Residual mode (sq_pq_create_residual) is the same handle with `residual` set: a row is coded as x - centroids[l(x)]
+// (pq_residual_kernel, also behind sq_pq_residuals), a query gets one table set per probed list (pq_tables_res_kernel)
+// and pq_scan_res_kernel walks one (query, probed list) pair's rows per workgroup.  Both scans share pq_stage_tables and
+// pq_row_sum; a handle made by sq_pq_create takes none of the residual branches.
 #include <algorithm>
 #include <chrono>
 #include <vector>
@@ -31,6 +36,10 @@ struct PqHandle : HandleBase {
     DevBuf codes, ids, list_off;         // [n][cs] bytes list-major, [n] insertion numbers, [nlist + 1]
     std::vector<long long> off_host;     // list_off on the host
     long long add_us = 0;
+    // residual mode (sq_pq_create_residual): rows are coded as x - centroids[l(x)], tables are per (query, probed list)
+    bool residual = false;
+    long long cds = 0;                   // floats of a centroid in `cent`
+    DevBuf cent;                         // [nlist][cds] float32, zero padded: what the residual and residual-tables kernels read
     // scratch of a search
     DevBuf q_dev, probe_dist, probe_idx, pre, cnt, tables, keys, out_keys, out_dist, out_idx, sort_tmp;
     HostPinned totals_host;              // [candidates in total, longest candidate list]
@@ -83,6 +92,25 @@ static __global__ __launch_bounds__(256) void pq_scatter_new_kernel(const u32* _
     if (c == 0) new_ids[dst] = (u32)(n_old + i);
 }
 
+// Residual mode: out[i][c] = x[i][c] - cent[assign[i]][c], one element per lane and trip.  x and out (row stride d) may
+// be the same buffer; cent has row stride cds.
+static __global__ __launch_bounds__(256) void pq_residual_kernel(const float* x, long long n, int d, const float* __restrict__ cent,
+                                                                  long long cds, const long long* __restrict__ assign, int nlist, float* out) {
+    const long long total = n * d;
+    for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < total; t += (long long)gridDim.x * 256) {
+        const long long i = t / d;
+        const int c = (int)(t - i * d);
+        long long l = assign[i];
+        l = l < 0 ? 0 : (l >= nlist ? nlist - 1 : l);
+        out[t] = __fsub_rn(x[t], cent[l * cds + c]);
+    }
+}
+static int pq_residual_launch(const float* x, long long n, int d, const float* cent, long long cds, const long long* assign, int nlist,
+                              float* out, hipStream_t st) {
+    const long long blocks = std::min<long long>((n * d + 255) / 256, pq_residual_blocks_max());
+    return launch<pq_residual_kernel>(dim3((unsigned)blocks), dim3(256), 0, st, x, n, d, cent, cds, assign, nlist, out);
+}
+
 // One counting sort: assign, code, group, scatter old and new codes into new buffers, swap.  Nothing of the handle
 // changes before the swap, so a failed allocation leaves the index as it was.
 static int pq_add_part(PqHandle* h, const float* rows, long long n_add, int mem) {
@@ -100,6 +128,12 @@ static int pq_add_part(PqHandle* h, const float* rows, long long n_add, int mem)
     SQ_TRY(assign.reserve((size_t)n_add * 8));
     SQ_TRY(adist.reserve((size_t)n_add * 4));
     SQ_TRY(ivf_assign(h->coarse, src, n_add, d, assign.as<long long>(), adist.as<float>(), st));
+    DevBuf resid;
+    if (h->residual) {   // what is coded is the row's residual against its list's centroid
+        SQ_TRY(ivf_alloc(resid, (size_t)n_add * d * 4));
+        SQ_TRY(pq_residual_launch(src, n_add, d, h->cent.as<float>(), h->cds, assign.as<long long>(), nlist, resid.as<float>(), st));
+        src = resid.as<float>();
+    }
     // the codes in insertion order: sub-vector j of every new row as a contiguous matrix (a 2-D copy), its nearest entry
     SQ_TRY(entry.reserve((size_t)n_add * 8));
     SQ_TRY(ivf_alloc(fresh, (size_t)n_add * cs));
@@ -118,6 +152,7 @@ static int pq_add_part(PqHandle* h, const float* rows, long long n_add, int mem)
     }
     SQ_HIP(hipStreamSynchronize(st));
     up.release();
+    resid.release();
     part.release();
     entry.release();
     IvfGroup g;
@@ -171,6 +206,46 @@ static __global__ __launch_bounds__(256) void pq_tables_kernel(const float* __re
     tables[((long long)ql * m + j) * ksub + c] = w.sum(dsub);
 }
 
+// What both scans share.  Staging: a pair's or a query's tn table floats into LDS, 16 bytes at a time when tn allows.
+__device__ __forceinline__ void pq_stage_tables(float* s_t, const float* __restrict__ tq, int tn) {
+    if ((tn & 3) == 0) {
+        for (int i = threadIdx.x * 4; i < tn; i += 1024) *reinterpret_cast<f32x4*>(s_t + i) = *reinterpret_cast<const f32x4*>(tq + i);
+    } else {
+        for (int i = threadIdx.x; i < tn; i += 256) s_t[i] = tq[i];
+    }
+}
+// A row's sum: its code dwords (V16: 16 bytes at a time), m lookups in the staged tables, added from left to right.
+template <bool V16>
+__device__ __forceinline__ float pq_row_sum(const u32* __restrict__ row, int w, int m, int ksub, const float* s_t) {
+    float acc = 0.f;
+    if constexpr (V16) {
+        for (int c = 0; c < w; c += 4) {
+            const u32x4 v = *reinterpret_cast<const u32x4*>(row + c);
+#pragma unroll
+            for (int b = 0; b < 16; ++b) {
+                const int j = c * 4 + b;
+                if (j < m) {
+                    const float t = s_t[j * ksub + (int)((v[b >> 2] >> (8 * (b & 3))) & 255u)];
+                    acc = j == 0 ? t : __fadd_rn(acc, t);
+                }
+            }
+        }
+    } else {
+        for (int c = 0; c < w; ++c) {
+            const u32 v = row[c];
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                const int j = c * 4 + b;
+                if (j < m) {
+                    const float t = s_t[j * ksub + (int)((v >> (8 * b)) & 255u)];
+                    acc = j == 0 ? t : __fadd_rn(acc, t);
+                }
+            }
+        }
+    }
+    return acc;
+}
+
 // The scan.  Workgroup (blockIdx.x, query) stages the query's tables once -- m * ksub floats of dynamic LDS -- and walks
 // the chunks blockIdx.x, blockIdx.x + gridDim.x, ... of 256 candidates of the query's concatenated range, one candidate
 // per lane.  A lane finds its list in the query's prefix array and reads its row's code dwords (V16: 16 bytes at a time;
@@ -188,12 +263,7 @@ static __global__ __launch_bounds__(256) void pq_scan_kernel(const u32* __restri
     const long long total = pq[np];
     if ((long long)blockIdx.x * kIvfChunk >= total) return;
     const int tn = m * ksub;
-    const float* tq = tables + (long long)ql * tn;
-    if ((tn & 3) == 0) {
-        for (int i = threadIdx.x * 4; i < tn; i += 1024) *reinterpret_cast<f32x4*>(s_t + i) = *reinterpret_cast<const f32x4*>(tq + i);
-    } else {
-        for (int i = threadIdx.x; i < tn; i += 256) s_t[i] = tq[i];
-    }
+    pq_stage_tables(s_t, tables + (long long)ql * tn, tn);
     __syncthreads();
     if (stage_only) {   // measurement (option "profile" = 2): what staging alone costs; one store per lane keeps the staging alive
         const long long p = (long long)blockIdx.x * kIvfChunk + threadIdx.x;
@@ -206,36 +276,117 @@ static __global__ __launch_bounds__(256) void pq_scan_kernel(const u32* __restri
         const int jl = ivf_locate(pq, np, p);
         const long long l = probe[(long long)q * np + jl];
         const long long s = list_off[l] + (p - pq[jl]);
-        const u32* row = codes + s * w;
-        float acc = 0.f;
-        if constexpr (V16) {
-            for (int c = 0; c < w; c += 4) {
-                const u32x4 v = *reinterpret_cast<const u32x4*>(row + c);
-#pragma unroll
-                for (int b = 0; b < 16; ++b) {
-                    const int j = c * 4 + b;
-                    if (j < m) {
-                        const float t = s_t[j * ksub + (int)((v[b >> 2] >> (8 * (b & 3))) & 255u)];
-                        acc = j == 0 ? t : __fadd_rn(acc, t);
-                    }
-                }
-            }
-        } else {
-            for (int c = 0; c < w; ++c) {
-                const u32 v = row[c];
-#pragma unroll
-                for (int b = 0; b < 4; ++b) {
-                    const int j = c * 4 + b;
-                    if (j < m) {
-                        const float t = s_t[j * ksub + (int)((v >> (8 * b)) & 255u)];
-                        acc = j == 0 ? t : __fadd_rn(acc, t);
-                    }
-                }
-            }
-        }
-        const float dist = sqrt_rn_f32(acc);
+        const float dist = sqrt_rn_f32(pq_row_sum<V16>(codes + s * w, w, m, ksub, s_t));
         keys[(long long)ql * key_stride + p] = ((u64)ordered_f32(dist) << 32) | (u64)ids[s];
     }
+}
+
+// ------------------------------------------------------------------ search, residual mode
+// A pair is (query of the slice, probe position), numbered row-major: pair p is query q0 + p / np at position p % np.
+// A launch takes the pairs p0 .. p0 + gridDim.y - 1 of the slice; its tables are [pair of the launch][m][ksub].
+struct PqPair {
+    int ql, jl;          // query inside the slice, probe position
+    long long lo, len;   // the pair's list: first row, rows (0: nothing to do)
+};
+__device__ __forceinline__ PqPair pq_pair(long long p, int q0, int np, const long long* __restrict__ probe,
+                                          const long long* __restrict__ list_off, int nlist, long long* list = nullptr) {
+    PqPair r;
+    r.ql = (int)(p / np);
+    r.jl = (int)(p - (long long)r.ql * np);
+    const long long l = probe[(long long)(q0 + r.ql) * np + r.jl];
+    const bool ok = l >= 0 && l < nlist;
+    r.lo = ok ? list_off[l] : 0;
+    r.len = ok ? list_off[l + 1] - r.lo : 0;
+    if (list) *list = l;
+    return r;
+}
+
+// The tables of a launch's pairs.  Work item (j, pair): the workgroup stages rq_j = q_j - cent[l]_j in LDS (es floats,
+// zero behind dsub), then lane c sums T_l[j][c] = |codebooks[j][c] - rq_j|^2 as pq_tables_kernel does.  A pair whose
+// list is empty is skipped: no scan workgroup reads its tables.
+static __global__ __launch_bounds__(256) void pq_tables_res_kernel(const float* __restrict__ books, long long es, int dsub, int ksub, int m,
+                                                                    const float* __restrict__ queries, int d, const float* __restrict__ cent,
+                                                                    long long cds, int q0, long long p0, int np,
+                                                                    const long long* __restrict__ probe,
+                                                                    const long long* __restrict__ list_off, int nlist,
+                                                                    float* __restrict__ tables) {
+    extern __shared__ __attribute__((aligned(16))) float s_q[];
+    const int j = blockIdx.x;
+    long long l = 0;
+    const PqPair pr = pq_pair(p0 + blockIdx.y, q0, np, probe, list_off, nlist, &l);
+    if (pr.len <= 0) return;
+    const float* qv = queries + (long long)(q0 + pr.ql) * d + (long long)j * dsub;
+    const float* cv = cent + l * cds + (long long)j * dsub;
+    for (int i = threadIdx.x; i < es; i += 256) s_q[i] = i < dsub ? __fsub_rn(qv[i], cv[i]) : 0.f;
+    __syncthreads();
+    const int c = threadIdx.x;
+    if (c >= ksub) return;
+    const SqLeafLane w{books + ((long long)j * ksub + c) * es, s_q};
+    tables[((long long)blockIdx.y * m + j) * ksub + c] = w.sum(dsub);
+}
+
+// The scan.  Workgroup (blockIdx.x, pair) stages its pair's tables and walks the chunks blockIdx.x, blockIdx.x +
+// gridDim.x, ... of 256 rows of the pair's list, one row per lane; row i of the list at probe position jl writes its key
+// at candidate position pre[jl] + i of its query, where the select expects it.  No search for the list, no barrier in
+// the loop; a workgroup whose first chunk lies beyond its list returns before staging.
+template <bool V16>
+static __global__ __launch_bounds__(256) void pq_scan_res_kernel(const u32* __restrict__ codes, int w, int m, int ksub,
+                                                                  const u32* __restrict__ ids, const long long* __restrict__ list_off, int nlist,
+                                                                  const float* __restrict__ tables, int q0, long long p0,
+                                                                  const long long* __restrict__ probe, const long long* __restrict__ pre,
+                                                                  int np, long long key_stride, u64* __restrict__ keys) {
+    extern __shared__ __attribute__((aligned(16))) float s_t[];
+    const PqPair pr = pq_pair(p0 + blockIdx.y, q0, np, probe, list_off, nlist);
+    if ((long long)blockIdx.x * kIvfChunk >= pr.len) return;
+    const int tn = m * ksub;
+    pq_stage_tables(s_t, tables + (long long)blockIdx.y * tn, tn);
+    __syncthreads();
+    u64* out = keys + (long long)pr.ql * key_stride + pre[(long long)(q0 + pr.ql) * (np + 1) + pr.jl];
+    for (long long base = (long long)blockIdx.x * kIvfChunk; base < pr.len; base += (long long)gridDim.x * kIvfChunk) {
+        const long long i = base + threadIdx.x;
+        if (i >= pr.len) break;
+        const long long s = pr.lo + i;
+        const float dist = sqrt_rn_f32(pq_row_sum<V16>(codes + s * w, w, m, ksub, s_t));
+        out[i] = ((u64)ordered_f32(dist) << 32) | (u64)ids[s];
+    }
+}
+
+// The scan of a slice in residual mode: its ns * np pairs in ranges of `ppl`, each range one tables launch and one scan
+// launch into the slice's keys.
+static int pq_scan_residual(PqHandle* h, const float* q_dev, int q0, int ns, int np, long long ppl, long long mc, hipStream_t st) {
+    const int m = h->m, ksub = h->ksub, w = (int)(h->cs / 4);
+    const bool prof = h->opt.profile != 0;
+    const size_t tb = (size_t)pq_table_bytes(m, ksub);
+    const long long pairs = (long long)ns * np, lmax = pq_longest_list(h->off_host.data(), h->nlist);
+    for (long long p0 = 0; p0 < pairs; p0 += ppl) {
+        const long long pl = pairs - p0 < ppl ? pairs - p0 : ppl;
+        if (prof) SQ_HIP(hipEventRecord(h->ev[0], st));
+        SQ_TRY(launch<pq_tables_res_kernel>(dim3((unsigned)m, (unsigned)pl), dim3(256), (size_t)h->es * 4, st, h->books.as<float>(), h->es,
+                                            h->dsub, ksub, m, q_dev, h->d, h->cent.as<float>(), h->cds, q0, p0, np,
+                                            h->probe_idx.as<long long>(), h->list_off.as<long long>(), h->nlist, h->tables.as<float>()));
+        if (prof) SQ_HIP(hipEventRecord(h->ev[1], st));
+        const dim3 grid((unsigned)pq_scan_groups(ivf_chunks(lmax), pl, cu_count(h->device)), (unsigned)pl);
+        const int lds_max = (int)pq_table_bytes(kPqMaxM, kPqMaxKsub);
+        if (w % 4 == 0)
+            SQ_TRY(launch_lds<pq_scan_res_kernel<true>>(lds_max, grid, dim3(256), tb, st, h->codes.as<u32>(), w, m, ksub, h->ids.as<u32>(),
+                                                        h->list_off.as<long long>(), h->nlist, h->tables.as<float>(), q0, p0,
+                                                        h->probe_idx.as<long long>(), h->pre.as<long long>(), np, mc, h->keys.as<u64>()));
+        else
+            SQ_TRY(launch_lds<pq_scan_res_kernel<false>>(lds_max, grid, dim3(256), tb, st, h->codes.as<u32>(), w, m, ksub, h->ids.as<u32>(),
+                                                         h->list_off.as<long long>(), h->nlist, h->tables.as<float>(), q0, p0,
+                                                         h->probe_idx.as<long long>(), h->pre.as<long long>(), np, mc, h->keys.as<u64>()));
+        if (prof) {
+            SQ_HIP(hipEventRecord(h->ev[2], st));
+            SQ_HIP(hipEventSynchronize(h->ev[2]));
+            float ms = 0.f;
+            SQ_HIP(hipEventElapsedTime(&ms, h->ev[1], h->ev[2]));
+            h->stats.scan_ms += ms;
+            SQ_HIP(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
+            h->stats.rerank_ms += ms;
+        }
+        h->stats.scan_launches++;
+    }
+    return SQ_OK;
 }
 
 // The search with queries and outputs in device memory, enqueued on `st`; the last select is not waited for.
@@ -264,13 +415,17 @@ static int pq_search_device(PqHandle* h, const float* q_dev, int nq, int k, int 
     const size_t tb = (size_t)pq_table_bytes(m, ksub);
     SQ_TRY(h->keys.reserve((size_t)slice * mc * 8));
     SQ_TRY(h->out_keys.reserve((size_t)slice * k_sel * 8));
-    if (maxc > 0) SQ_TRY(h->tables.reserve((size_t)slice * tb));
+    // residual mode: one table set per (query, probed list); the slice's pairs go in ranges of `ppl` that the budget holds
+    const long long ppl = h->residual ? std::min<long long>(pq_res_pairs_per_launch(slice, maxc, k, m, ksub, budget), (long long)slice * np) : 0;
+    if (maxc > 0) SQ_TRY(h->tables.reserve((size_t)(h->residual ? ppl : slice) * tb));
     if (prof)
         for (int i = 0; i < 3; ++i)
             if (!h->ev[i]) SQ_HIP(hipEventCreate(&h->ev[i]));
     for (int q0 = 0; q0 < nq; q0 += slice) {
         const int ns = nq - q0 < slice ? nq - q0 : slice;
-        if (maxc > 0) {
+        if (maxc > 0 && h->residual) {
+            SQ_TRY(pq_scan_residual(h, q_dev, q0, ns, np, ppl, mc, st));
+        } else if (maxc > 0) {
             // option "profile": 1 = scan_ms is pq_scan_kernel, rerank_ms is pq_tables_kernel; 2 = scan_ms is a launch of
             // pq_scan_kernel that only stages the tables (the real scan follows it, untimed)
             const int prof_mode = h->opt.profile;
@@ -347,12 +502,23 @@ extern "C" int sq_pq_train(const float* x, int64_t n, int d, int m, int ksub, fl
     return SQ_OK;
 }
 
-extern "C" int sq_pq_create(const float* centroids, int nlist, int d, const float* codebooks, int m, int ksub, int64_t id_base,
-                            sq_handle_t* out) {
-    if (!centroids || !codebooks || !out || nlist <= 0 || d <= 0) return fail(SQ_ERR_INVALID, "sq_pq_create: bad argument");
-    SQ_TRY(pq_shape_check("sq_pq_create", d, m, ksub));
-    if (nlist > kIvfMaxLists) return fail(SQ_ERR_UNSUPPORTED, "sq_pq_create: more than %d lists", kIvfMaxLists);
+// [nlist][round_up(d, 4)] float32 on the device, zero padded, from centroids in host memory
+static int pq_upload_centroids(const float* centroids, int nlist, int d, DevBuf& cent, long long* cds) {
+    *cds = ivf_row_stride(d);
+    const size_t bytes = (size_t)nlist * *cds * 4;
+    SQ_TRY(ivf_alloc(cent, bytes));
+    SQ_HIP(hipMemset(cent.p, 0, bytes));
+    SQ_HIP(hipMemcpy2D(cent.p, (size_t)*cds * 4, centroids, (size_t)d * 4, (size_t)d * 4, (size_t)nlist, hipMemcpyHostToDevice));
+    return SQ_OK;
+}
+
+static int pq_create(const char* who, bool residual, const float* centroids, int nlist, int d, const float* codebooks, int m, int ksub,
+                     int64_t id_base, sq_handle_t* out) {
+    if (!centroids || !codebooks || !out || nlist <= 0 || d <= 0) return fail(SQ_ERR_INVALID, "%s: bad argument", who);
+    SQ_TRY(pq_shape_check(who, d, m, ksub));
+    if (nlist > kIvfMaxLists) return fail(SQ_ERR_UNSUPPORTED, "%s: more than %d lists", who, kIvfMaxLists);
     auto h = std::make_unique<PqHandle>();
+    h->residual = residual;
     h->kind = H_PQ;
     h->d = d;
     h->nlist = nlist;
@@ -363,8 +529,9 @@ extern "C" int sq_pq_create(const float* centroids, int nlist, int d, const floa
     h->es = pq_entry_stride(h->dsub);
     h->id_base = id_base;
     h->refresh_options();
-    if (hipGetDevice(&h->device) != hipSuccess) return fail(SQ_ERR_HIP, "sq_pq_create: no HIP device");
+    if (hipGetDevice(&h->device) != hipSuccess) return fail(SQ_ERR_HIP, "%s: no HIP device", who);
     SQ_TRY(ivf_coarse_create(centroids, nlist, d, SQ_MEM_HOST, &h->coarse));
+    if (residual) SQ_TRY(pq_upload_centroids(centroids, nlist, d, h->cent, &h->cds));
     h->sub.assign((size_t)m, 0);
     for (int j = 0; j < m; ++j)
         SQ_TRY(ivf_coarse_create(codebooks + (size_t)j * ksub * h->dsub, ksub, h->dsub, SQ_MEM_HOST, &h->sub[(size_t)j]));
@@ -377,6 +544,48 @@ extern "C" int sq_pq_create(const float* centroids, int nlist, int d, const floa
     SQ_TRY(ivf_alloc(h->list_off, (size_t)(nlist + 1) * 8));
     SQ_HIP(hipMemset(h->list_off.p, 0, (size_t)(nlist + 1) * 8));
     *out = register_handle(h.release());
+    return SQ_OK;
+}
+
+extern "C" int sq_pq_create(const float* centroids, int nlist, int d, const float* codebooks, int m, int ksub, int64_t id_base,
+                            sq_handle_t* out) {
+    return pq_create("sq_pq_create", false, centroids, nlist, d, codebooks, m, ksub, id_base, out);
+}
+
+extern "C" int sq_pq_create_residual(const float* centroids, int nlist, int d, const float* codebooks, int m, int ksub, int64_t id_base,
+                                     sq_handle_t* out) {
+    return pq_create("sq_pq_create_residual", true, centroids, nlist, d, codebooks, m, ksub, id_base, out);
+}
+
+extern "C" int sq_pq_residuals(const float* x, int64_t n, int d, const float* centroids, int nlist, float* out, int mem) {
+    if (!x || !centroids || !out || n <= 0 || d <= 0 || nlist <= 0) return fail(SQ_ERR_INVALID, "sq_pq_residuals: bad argument");
+    if (nlist > kIvfMaxLists) return fail(SQ_ERR_UNSUPPORTED, "sq_pq_residuals: more than %d lists", kIvfMaxLists);
+    if (n > kIvfGroupMax) return fail(SQ_ERR_UNSUPPORTED, "sq_pq_residuals: more than 2^26 rows (train on a sample)");
+    if (mem != SQ_MEM_HOST && mem != SQ_MEM_DEVICE) return fail(SQ_ERR_UNSUPPORTED, "sq_pq_residuals: host or device memory only");
+    struct Coarse {
+        sq_handle_t h = 0;
+        ~Coarse() {
+            if (h) (void)sq_dense_destroy(h);
+        }
+    } coarse;
+    SQ_TRY(ivf_coarse_create(centroids, nlist, d, SQ_MEM_HOST, &coarse.h));
+    hipStream_t st = nullptr;
+    DevBuf cent, up, assign, adist;
+    long long cds = 0;
+    SQ_TRY(pq_upload_centroids(centroids, nlist, d, cent, &cds));
+    const float* src = x;
+    float* dst = out;
+    if (mem == SQ_MEM_HOST) {   // the rows go up, are replaced by their residuals in place, and come back
+        SQ_TRY(ivf_alloc(up, (size_t)n * d * 4));
+        SQ_HIP(hipMemcpy(up.p, x, (size_t)n * d * 4, hipMemcpyHostToDevice));
+        src = dst = up.as<float>();
+    }
+    SQ_TRY(assign.reserve((size_t)n * 8));
+    SQ_TRY(adist.reserve((size_t)n * 4));
+    SQ_TRY(ivf_assign(coarse.h, src, n, d, assign.as<long long>(), adist.as<float>(), st));
+    SQ_TRY(pq_residual_launch(src, n, d, cent.as<float>(), cds, assign.as<long long>(), nlist, dst, st));
+    SQ_HIP(hipStreamSynchronize(st));
+    if (mem == SQ_MEM_HOST) SQ_HIP(hipMemcpy(out, up.p, (size_t)n * d * 4, hipMemcpyDeviceToHost));
     return SQ_OK;
 }
 
@@ -420,7 +629,7 @@ extern "C" int sq_pq_info(sq_handle_t hid, int64_t* out, int n_out) {
     if (!out || n_out < SQ_PQ_INFO_FIELDS) return fail(SQ_ERR_INVALID, "sq_pq_info: room for %d values needed", SQ_PQ_INFO_FIELDS);
     std::lock_guard<std::mutex> lock(h->mu);
     h->refresh_options();
-    int64_t fixed = (int64_t)h->books.cap;
+    int64_t fixed = (int64_t)h->books.cap + (h->residual ? (int64_t)h->cent.cap : 0);
     std::vector<sq_handle_t> dense(h->sub);
     dense.push_back(h->coarse);
     for (sq_handle_t s : dense) {

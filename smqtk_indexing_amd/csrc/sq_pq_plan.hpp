@@ -1,7 +1,8 @@
 // The host's arithmetic around the IVF-PQ index (sq_pq.hip): which (d, m, ksub) an index takes, the stride of a coded
 // row, the LDS a scan workgroup stages a query's tables in, how many workgroups walk one query's candidates, and how
-// many queries of a batch share the scratch once the tables are counted.  Everything in 64-bit.  Plain C++ on top of
-// sq_ivf_plan.hpp, no runtime header: tests/host/pq_plan_main.cpp runs it on the CPU.
+// many queries of a batch share the scratch once the tables are counted; for residual mode, how many (query, probed
+// list) pairs one launch takes and how many launches a search makes.  Everything in 64-bit.  Plain C++ on top of
+// sq_ivf_plan.hpp, no runtime header: tests/host/pq_plan_main.cpp and pq_residual_plan_main.cpp run it on the CPU.
 #pragma once
 #include "sq_ivf_plan.hpp"
 
@@ -53,5 +54,41 @@ inline long long pq_slice_queries(long long nq, long long maxc, long long k, int
     if (s < 1) s = 1;
     return s < nq ? s : nq;
 }
+
+// ---- residual mode: one table set per pair (query of the slice, probe position), so np times the tables per query.
+// The queries per slice are pq_slice_queries' -- each query's keys and ONE pair's tables --; what the budget has left
+// beside the slice's keys holds the tables of `pairs per launch` pairs, and a slice's ns * np pairs are taken in ranges
+// of that many, row-major in (query, position): a range is one tables launch and one scan launch.
+static constexpr long long kPqMaxPairsPerLaunch = 65535;   // the scan grid's second dimension
+
+inline long long pq_res_pairs_per_launch(long long slice, long long maxc, long long k, int m, int ksub, long long budget_bytes) {
+    long long p = (budget_bytes - slice * ivf_query_scratch_bytes(maxc, k)) / pq_table_bytes(m, ksub);
+    if (p < 1) p = 1;
+    return p < kPqMaxPairsPerLaunch ? p : kPqMaxPairsPerLaunch;
+}
+// scratch bytes of a residual search: the slice's keys and the tables of the pairs of one launch
+inline long long pq_res_scratch_bytes(long long slice, long long ppl, long long maxc, long long k, int m, int ksub) {
+    return slice * ivf_query_scratch_bytes(maxc, k) + ppl * pq_table_bytes(m, ksub);
+}
+// launches (ranges) of a residual search of nq queries at np probed lists each: what scan_launches counts
+inline long long pq_res_launches(long long nq, long long np, long long maxc, long long k, int m, int ksub, long long budget_bytes) {
+    if (maxc < 1 || nq < 1 || np < 1) return 0;
+    const long long slice = pq_slice_queries(nq, maxc, k, m, ksub, budget_bytes);
+    long long ppl = pq_res_pairs_per_launch(slice, maxc, k, m, ksub, budget_bytes);
+    if (ppl > slice * np) ppl = slice * np;
+    const long long full = nq / slice, rest = nq % slice;   // whole slices, and the queries of a last shorter one
+    return full * ((slice * np + ppl - 1) / ppl) + (rest * np + ppl - 1) / ppl;
+}
+// rows of the longest list: the chunks a pair's scan workgroups share (pq_scan_groups with a pair in a query's place)
+inline long long pq_longest_list(const long long* list_off, int nlist) {
+    long long mx = 0;
+    for (int l = 0; l < nlist; ++l) {
+        const long long len = list_off[l + 1] - list_off[l];
+        mx = len > mx ? len : mx;
+    }
+    return mx;
+}
+// workgroups of pq_residual_kernel at most: it strides over the elements beyond that
+inline long long pq_residual_blocks_max() { return 1ll << 20; }
 
 }  // namespace sq

@@ -73,13 +73,22 @@ class HipIvfPqNearestNeighborsIndex(_ListIndexHostLogic, NearestNeighborsIndex):
         entries = rs.choice(len(sample), size=min(_lib.SQ_PQ_MAX_KSUB, len(sample)), replace=False)
         return sample, init, entries
 
+    # The two places a subclass that codes something else than the rows themselves differs in.
+    def _coded_rows(self, train: np.ndarray, centroids: np.ndarray) -> np.ndarray:
+        """What the codebooks are trained on, row for row of the training sample: here the sample itself."""
+        return train
+
+    def _new_device_index(self) -> Any:
+        """An empty device index over the centroids and codebooks in hand."""
+        return _lib.PqIndex(self._centroids, self._codebooks)
+
     def _set_lists(self, elements: List[DescriptorElement], matrix: np.ndarray) -> None:
         """The lists over ``matrix`` with centroids and codebooks in hand (the device index is built first: a failure
         leaves the old state).  The matrix is not kept."""
         dev = None
         if matrix.shape[0]:
             assert self._centroids is not None and self._codebooks is not None
-            dev = _lib.PqIndex(self._centroids, self._codebooks)
+            dev = self._new_device_index()
             dev.add(matrix)
         if self._dev is not None:
             self._dev.close()
@@ -106,10 +115,11 @@ class HipIvfPqNearestNeighborsIndex(_ListIndexHostLogic, NearestNeighborsIndex):
             sample, init, entries = self.training_plan(matrix.shape[0])
             train = matrix[sample]
             dsub = matrix.shape[1] // self.m
-            # the same rows serve every sub-quantiser: entry c of codebook j is sub-vector j of sample row entries[c]
-            books0 = np.ascontiguousarray(train[entries].reshape(len(entries), self.m, dsub).transpose(1, 0, 2))
             centroids = _lib.ivf_kmeans(train, train[init], self.train_iters)
-            codebooks = _lib.pq_train(train, books0, self.train_iters)
+            coded = self._coded_rows(train, centroids)
+            # the same rows serve every sub-quantiser: entry c of codebook j is sub-vector j of sample row entries[c]
+            books0 = np.ascontiguousarray(coded[entries].reshape(len(entries), self.m, dsub).transpose(1, 0, 2))
+            codebooks = _lib.pq_train(coded, books0, self.train_iters)
             self._centroids, self._codebooks = centroids, codebooks
             self._set_lists(elements, matrix)
 

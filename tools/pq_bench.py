@@ -14,6 +14,11 @@ for IVF-PQ a second pair around pq_tables_kernel), over the bytes the scan reads
 pass with "profile" = 2 times a launch of pq_scan_kernel on the same grid that only stages the tables and stores one
 word per lane: its share of the scan's time is the share spent staging tables (launch overhead included).  --no-flat / --no-exact
 leave those indexes out (their float32 rows are what limits the row count that fits beside each other).
+--residual adds, for every m, the index in residual mode (sq_pq_create_residual; "rpq<m>" in the table): its codebooks are
+trained on sq_pq_residuals of the same sample from the residuals of the same entry rows, it is timed in the same
+alternating windows, and under each table its call time is given as a ratio to plain PQ and to IVF-Flat at equal nprobe
+(profiles/ivf_pq_residual.txt is the output with this flag).  For a residual index "tables kernel" is
+pq_tables_res_kernel summed over the launches of a call; option "profile" = 2 means 1 there, so no staging-only figure.
 
     python tools/pq_bench.py                      # the full table
     python tools/pq_bench.py --only 32,16 --ms 32 --calls 200 --windows 1 --no-flat --no-exact   # one shape, e.g. under a counter run
@@ -50,6 +55,7 @@ def main():
     ap.add_argument("--only", default="", help="nq,nprobe: time this shape alone")
     ap.add_argument("--no-flat", action="store_true")
     ap.add_argument("--no-exact", action="store_true")
+    ap.add_argument("--residual", action="store_true", help="also the residual-mode index of every m")
     ap.add_argument("--out", default="", help="also write the report here")
     args = ap.parse_args()
 
@@ -85,7 +91,8 @@ def main():
     sample_rows = np.sort(rs.choice(n, size=sm, replace=False))
     sample = db[torch.from_numpy(sample_rows).to(dev)].cpu().numpy()
     init = sample[rs.choice(sm, size=nlist, replace=False)]
-    entries = sample[rs.choice(sm, size=ksub, replace=False)]
+    entry_rows = rs.choice(sm, size=ksub, replace=False)
+    entries = sample[entry_rows]
     t0 = time.perf_counter()
     centroids = _lib.ivf_kmeans(sample, init, args.iters)
     say(f"train: {sm} sample rows, {args.iters} iterations; centroids {time.perf_counter() - t0:.2f} s")
@@ -115,6 +122,23 @@ def main():
             f"{res / matrix_bytes:.4f} x the matrix ({(info['codes_bytes'] + 4 * n) / n:.0f} bytes per row)")
         indexes[f"pq{m}"] = pq
         summary["indexes"][f"pq{m}"] = {"train_s": train_s, "add_s": add_s, "resident_bytes": res}
+    if args.residual:
+        t0 = time.perf_counter()
+        sample_res = _lib.pq_residuals(sample, centroids)
+        say(f"residuals of the sample (sq_pq_residuals, host memory): {time.perf_counter() - t0:.2f} s")
+        for m in ms_:
+            books0 = np.ascontiguousarray(sample_res[entry_rows].reshape(ksub, m, d // m).transpose(1, 0, 2))
+            t0 = time.perf_counter()
+            books = _lib.pq_train(sample_res, books0, args.iters)
+            train_s = time.perf_counter() - t0
+            rpq = _lib.PqIndex(centroids, books, residual=True)
+            add_s = add_all(rpq)
+            info = rpq.info()
+            res = info["codes_bytes"] + info["ids_offsets_bytes"] + info["books_coarse_bytes"]
+            say(f"rpq m={m}: codebooks {train_s:.2f} s, add {add_s:.2f} s; resident (sq_pq_info): codes {info['codes_bytes']}, ids + offsets "
+                f"{info['ids_offsets_bytes']}, codebooks + coarse index + centroids {info['books_coarse_bytes']} = {res} bytes = {res / matrix_bytes:.4f} x the matrix")
+            indexes[f"rpq{m}"] = rpq
+            summary["indexes"][f"rpq{m}"] = {"train_s": train_s, "add_s": add_s, "resident_bytes": res}
     if not args.no_flat:
         flat = _lib.IvfIndex(centroids)
         add_s = add_all(flat)
@@ -172,7 +196,7 @@ def main():
         for name, index in indexes.items():
             for p in nprobes:
                 med = {}
-                for mode in (1, 2) if name != "flat" else (1,):
+                for mode in (1, 2) if name.startswith("pq") else (1,):
                     index.set_option("profile", mode)
                     v, tv, by, cands = [], [], 0, 0
                     for c in range(min(args.calls, 64)):
@@ -200,10 +224,20 @@ def main():
                     f"scan kernel {sms * 1e3:8.1f} us, {cands / nq:9.0f} rows per query, {by / 1e6:8.2f} MB, {gbs:7.1f} GB/s, "
                     f"{cands / (sms * 1e-3) / 1e9 if sms > 0 else float('nan'):6.2f} G rows/s"
                     + (f"   tables kernel {tms * 1e3:6.1f} us, staging-only scan launch {stage_ms * 1e3:6.1f} us = {100 * stage_ms / sms:4.1f} % of the scan"
-                       if name != "flat" and sms > 0 else ""))
+                       if name.startswith("pq") and sms > 0 else
+                       f"   tables kernel {tms * 1e3:6.1f} us" if name.startswith("rpq") else ""))
                 report.append({"queries": nq, "nprobe": p, "index": name, "ms_per_call": t, "ms_fastest": min(times[key]), "ms_slowest": max(times[key]),
                                "recall": recall[key], "scan_kernel_ms": sms, "scan_bytes": by, "candidates": cands,
                                "tables_kernel_ms": tms, "staging_only_ms": stage_ms})
+        if args.residual:
+            say(f"# residual against plain PQ and IVF-Flat at equal nprobe, {nq} quer{'y' if nq == 1 else 'ies'}: call-time ratios, recall, kernel time")
+            for p in nprobes:
+                for m in ms_:
+                    tr, tp = statistics.median(times[(f"rpq{m}", p)]), statistics.median(times[(f"pq{m}", p)])
+                    tf = statistics.median(times[("flat", p)]) if "flat" in indexes else float("nan")
+                    rs_, rp_ = scan[(f"rpq{m}", p)], scan[(f"pq{m}", p)]
+                    say(f"nprobe {p:<3d} m={m:<2d}  rpq / pq {tr / tp:5.2f}   rpq / flat {tr / tf:5.2f}   recall@{k} rpq {recall[(f'rpq{m}', p)]:.3f} pq {recall[(f'pq{m}', p)]:.3f}"
+                        f"   tables + scan kernels: rpq {rs_[3] * 1e3:7.1f} + {rs_[0] * 1e3:7.1f} us, pq {rp_[3] * 1e3:7.1f} + {rp_[0] * 1e3:7.1f} us")
     summary["shapes"] = report
     say()
     say(json.dumps(summary))
