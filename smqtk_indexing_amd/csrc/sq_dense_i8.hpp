@@ -525,6 +525,15 @@ __device__ __forceinline__ void dense8_hist_flush(u32* lds_hist, u32* __restrict
 // The stream of one wave: its share of the launch's ring units through its private LDS ring, the MFMAs of the unit's tiles
 // against the query planes in registers, the score epilogue.  `wcount`: survivors appended (I8_EMIT); `smin`: the lane's
 // running minimum (I8_LANEMIN).
+//
+// The loop's structure.  A wave keeps two units: the one it consumes (`u_cur`, in the ring slot at `slot_off`) and the one
+// in flight behind it (`u_nxt`, other slot), each one unit number; an iteration ends with (u_cur, u_nxt) <- (u_nxt, the unit
+// just issued) and the slots swapped -- no parity selects, nothing recomputed from an iteration count.  Per unit: the counted
+// wait for the landed unit and the fragment reads; then the refill -- a ticket (lds_ticket_take: one LDS atomic by lane 0),
+// ticket -> unit, one compare against the launch's units (the first ticket beyond them ends the wave's stream: the loop is
+// bounded by the tickets, nothing spins), the two source addresses by one multiply-add each, ONE uniform branch on the cache
+// policy (the boundary is one unit number) and the unit's DMAs as one straight-line statement (glds_unit8: M0 written
+// twice, not nine times saved / set / restored); then the tiles' MFMAs and the score epilogue.
 template <int KS, int MODE>
 __device__ __forceinline__ void dense8_stream(const Dense8ScanArgs& a, unsigned char* smem, const i32x4 (&bq)[KS], const i32x4 (&bl)[KS],
                                               float unit_lo, float thr_l, u32& wcount, float& smin, u32* lds_ticket,
@@ -548,62 +557,75 @@ __device__ __forceinline__ void dense8_stream(const Dense8ScanArgs& a, unsigned 
     // would own under a fixed split (wave w: w + it * nwaves), but a wave that runs ahead takes the next one instead of
     // waiting at the end: with the fixed split the eight waves of a workgroup left the stream 20 - 48 us apart (of 200) and
     // the tail -- and the CU -- waited for the last.
-    const long long wg_first = (long long)blockIdx.x * G::WAVES;
-    auto take_unit = [&]() __attribute__((always_inline)) -> long long {
-        u32 t = 0;
-        if (lane == 0) t = __hip_atomic_fetch_add(lds_ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        t = (u32)__builtin_amdgcn_readfirstlane((int)t);
-        const long long u = wg_first + (long long)(t % G::WAVES) + (long long)(t / G::WAVES) * nwaves;
-        return u < a.n_sel ? u : -1ll;   // (u grows with t: the first ticket beyond the launch's units ends the wave's stream)
+    using U = unsigned long long;   // a unit number
+    constexpr U NONE = ~(U)0;
+    static_assert((G::WAVES & (G::WAVES - 1)) == 0, "ticket -> unit by shift and mask");
+    const U wg_first = (U)blockIdx.x * G::WAVES, nwaves_u = (U)nwaves, n_sel = (U)a.n_sel, unit_step = (U)a.unit_step;
+    // (u grows with t: the first ticket beyond the launch's units ends the wave's stream)
+    const u32 ticket_addr = (u32)(uintptr_t)lds_ticket;
+    auto take_unit = [&]() __attribute__((always_inline)) -> U {
+        const u32 t = lds_ticket_take(ticket_addr);
+        const U u = wg_first + (U)(t & (u32)(G::WAVES - 1)) + (U)(t / G::WAVES) * nwaves_u;
+        return u < n_sel ? u : NONE;
     };
     const long long my_units = wave_id < a.n_sel ? (a.n_sel - wave_id + nwaves - 1) / nwaves : 0;   // (the fixed split's share: sizes the flush period)
     // DMA piece j: bytes 1024 j .. 1024 j + 1023 of the unit's LDS image; lane -> 16 bytes at (row, chunk position), read
-    // from the row's source chunk swz(position)
-    u32 voff[G::PIECES];
+    // from the row's source chunk swz(position).  (+ 4096 - 1024 j: glds_unit8's instruction offsets)
+    u32 voff_s[G::PIECES];
 #pragma unroll
     for (int j = 0; j < G::PIECES; ++j) {
         const int lin = j * 1024 + lane * 16;
         const int r = lin / G::ROW_BYTES, cpos = (lin % G::ROW_BYTES) >> 4;
-        voff[j] = (u32)(r * G::ROW_BYTES + i8_swz<KS>(cpos, r) * 16);
+        voff_s[j] = (u32)(r * G::ROW_BYTES + i8_swz<KS>(cpos, r) * 16) + 4096u - (u32)j * 1024u;
     }
     const u32 voff_n = (u32)lane * 4u;
-    static_assert(G::NSTAGE == 2, "two ring slots: the units in flight are sel_even / sel_odd");
-    long long issued = 0, sel_even = -1, sel_odd = -1;   // the selected-unit index in ring slot 0 / 1
-    bool more = true;
-    auto issue_next = [&]() __attribute__((always_inline)) {
-        if (!more) return;
-        const long long sel = take_unit();
-        if (sel < 0) {
-            more = false;
-            return;
+    static_assert(G::NSTAGE == 2, "two ring slots: the unit consumed and the unit in flight");
+    static_assert(G::PIECES == 8 || G::PIECES == 16, "a unit is one or two glds_unit8 statements");
+    // rows from nt_from_row on stream non-temporally: unit_idx * UNIT_ROWS >= nt_from_row <=> unit_idx >= its ceiling
+    U nt_from_unit = NONE;
+    if (a.nt) {
+        const long long f = a.nt_from_row / G::UNIT_ROWS + (a.nt_from_row % G::UNIT_ROWS != 0 ? 1 : 0);
+        nt_from_unit = (U)f;
+    }
+    auto issue_unit = [&](U u, u32 slot_off) __attribute__((always_inline)) {
+        const U unit_idx = u * unit_step;
+        const unsigned char* base = reinterpret_cast<const unsigned char*>(a.scan8) + (unsigned long long)unit_idx * G::UNIT_BYTES;
+        const float* terms = a.nrow + (unsigned long long)unit_idx * G::UNIT_ROWS;   // (64 floats: the unit's, and for 32-row units the next one's as well)
+        const u32 dst = ring_base + slot_off;
+        if (unit_idx >= nt_from_unit) {
+            if constexpr (G::PIECES == 16) glds_unit8<true, false>(base, voff_s, dst);
+            glds_unit8<true, true>(base + (G::PIECES - 8) * 1024, voff_s + (G::PIECES - 8), dst + (G::PIECES - 8) * 1024, terms, voff_n,
+                                   dst + G::UNIT_BYTES);
+        } else {
+            if constexpr (G::PIECES == 16) glds_unit8<false, false>(base, voff_s, dst);
+            glds_unit8<false, true>(base + (G::PIECES - 8) * 1024, voff_s + (G::PIECES - 8), dst + (G::PIECES - 8) * 1024, terms, voff_n,
+                                    dst + G::UNIT_BYTES);
         }
-        if (issued & 1) sel_odd = sel; else sel_even = sel;
-        const long long unit_idx = sel * a.unit_step;
-        const long long row0 = unit_idx * G::UNIT_ROWS;
-        const u32 dst = ring_base + (u32)(issued % G::NSTAGE) * G::SLOT_BYTES;
-        const unsigned char* base = reinterpret_cast<const unsigned char*>(a.scan8) + row0 * G::ROW_BYTES;
-#pragma unroll
-        for (int j = 0; j < G::PIECES; ++j) {
-            if (a.nt && row0 >= a.nt_from_row)
-                glds16<true>(base, voff[j], dst + (u32)j * 1024);
-            else
-                glds16<false>(base, voff[j], dst + (u32)j * 1024);
-        }
-        glds4(a.nrow + row0, voff_n, dst + G::UNIT_BYTES);   // (64 floats: the unit's, and for 32-row units the next one's as well)
-        ++issued;
     };
-    for (int p = 0; p < G::NSTAGE; ++p) issue_next();
+    // the first two units
+    U u_cur = take_unit(), u_nxt = NONE;
+    bool more = u_cur != NONE;
+    if (more) {
+        issue_unit(u_cur, 0u);
+        u_nxt = take_unit();
+        more = u_nxt != NONE;
+        if (more) issue_unit(u_nxt, (u32)G::SLOT_BYTES);
+    }
     // I8_EMIT_H: this wave's share of the workgroup's histogram goes to the global one eight times per pass (and once more
     // from the tail): a workgroup that finishes early then finds at least 7/8 of everybody's entries
     const int flush_every = (int)(my_units >> 3) > 0 ? (int)(my_units >> 3) : 1;
     int to_flush = flush_every;
 
-    for (long long it = 0; it < issued; ++it) {   // (`issued` grows inside: issue_next)
-        const long long sel = (it & 1) ? sel_odd : sel_even;
-        const long long unit_idx = sel * a.unit_step;
-        const long long row0 = unit_idx * G::UNIT_ROWS;
-        wait_units_in_flight<G::NSTAGE, G::PIECES + 1>((int)(issued - it - 1));
-        const unsigned char* sl = ring_ptr + (it % G::NSTAGE) * G::SLOT_BYTES;
+    u32 slot_off = 0u;   // the ring slot of u_cur
+    while (u_cur != NONE) {
+        const U sel = u_cur;
+        const u32 row0 = (u32)(sel * unit_step) * (u32)G::UNIT_ROWS;   // (the entries carry 32-bit rows)
+        if (u_nxt != NONE)
+            wait_vmcnt<G::PIECES + 1>();
+        else
+            wait_vmcnt<0>();
+        const unsigned char* sl = ring_ptr + slot_off;
+        U u_new = NONE;
         // A fragments (lane = row): all of the unit's for rows up to 256 bytes; a 512-byte row in two halves of eight
         // k-steps, the second read while the first half's MFMAs run (its slot is refilled after the second read)
         constexpr int KH = KS == 16 ? 8 : KS;      // k-steps per fragment batch
@@ -620,7 +642,16 @@ __device__ __forceinline__ void dense8_stream(const Dense8ScanArgs& a, unsigned 
             for (int c = 0; c < 4; ++c) nr[t][c] = *reinterpret_cast<const f32x4*>(sl + G::UNIT_BYTES + (32 * t + 8 * c + 4 * h) * 4);
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if constexpr (KS != 16) issue_next();   // the unit is in registers: its slot is free
+        // the unit is in registers: its slot is free
+        auto refill = [&]() __attribute__((always_inline)) {
+            if (!more) return;
+            u_new = take_unit();
+            if (u_new != NONE)
+                issue_unit(u_new, slot_off);
+            else
+                more = false;
+        };
+        if constexpr (KS != 16) refill();
 #pragma unroll
         for (int t = 0; t < G::TILES; ++t) {
             i32x16 acc, acl;
@@ -636,7 +667,7 @@ __device__ __forceinline__ void dense8_stream(const Dense8ScanArgs& a, unsigned 
                 for (int s = 0; s < KH; ++s)
                     av[t][s] = *reinterpret_cast<const i32x4*>(sl + r31 * G::ROW_BYTES + i8_swz<KS>(2 * (KH + s) + h, r31) * 16);
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                issue_next();
+                refill();
 #pragma unroll
                 for (int s = 0; s < KH; ++s) {
                     acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(av[t][s], bq[KH + s], acc, 0, 0, 0);
@@ -648,7 +679,7 @@ __device__ __forceinline__ void dense8_stream(const Dense8ScanArgs& a, unsigned 
                 continue;
             }
             // scores of 32 rows x 32 queries (lane = query, register i = row (i & 3) + 8 (i >> 2) + 4 h)
-            float sc[16];
+            f32x16 sc;
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
                 float nv = nr[t][i >> 2][i & 3];
@@ -663,16 +694,14 @@ __device__ __forceinline__ void dense8_stream(const Dense8ScanArgs& a, unsigned 
             if constexpr (MODE == I8_LANEMIN) {
                 smin = fminf(smin, m);
             } else if constexpr (MODE == I8_SAMPLE) {
-                a.sample_out[(long long)r31 * a.ns + sel * G::SAMPLES_PER_UNIT + t * 2 + h] = m;
+                a.sample_out[(long long)r31 * a.ns + (long long)sel * G::SAMPLES_PER_UNIT + t * 2 + h] = m;
             } else {
+                // the lanes with a survivor: m <= thr_l exactly where a bit of the mask is set
                 const u64 hit = __ballot(m <= thr_l);
                 if (hit != 0) {
-                    u32 mask = 0;
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) mask |= (sc[i] <= thr_l ? 1u : 0u) << i;   // (+inf padding rows never pass)
-                    const u64 bal = __ballot(mask != 0);
+                    const u32 mask = le_mask16(sc, thr_l);   // bit i: sc[i] <= thr_l (+inf padding rows never pass)
                     if (mask) {
-                        const u32 pos = wcount + __builtin_amdgcn_mbcnt_hi((u32)(bal >> 32), __builtin_amdgcn_mbcnt_lo((u32)bal, 0u));
+                        const u32 pos = wcount + __builtin_amdgcn_mbcnt_hi((u32)(hit >> 32), __builtin_amdgcn_mbcnt_lo((u32)hit, 0u));
                         if (pos < a.wave_cap) {
                             wout[pos] = make_uint2((u32)(row0 + 32 * t + 4 * h), (mask << 16) | (u32)r31);
                             if constexpr (MODE == I8_EMIT_H) wsc[pos] = m;
@@ -684,7 +713,7 @@ __device__ __forceinline__ void dense8_stream(const Dense8ScanArgs& a, unsigned 
                             }
                         }
                     }
-                    wcount += (u32)__popcll(bal);
+                    wcount += (u32)__popcll(hit);
                 }
             }
         }
@@ -694,6 +723,9 @@ __device__ __forceinline__ void dense8_stream(const Dense8ScanArgs& a, unsigned 
                 dense8_hist_flush<G::WAVES>(lds_hist, a.hist);
             }
         }
+        u_cur = u_nxt;
+        u_nxt = u_new;
+        slot_off = (u32)G::SLOT_BYTES - slot_off;
     }
 }
 

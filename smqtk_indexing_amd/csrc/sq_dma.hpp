@@ -78,6 +78,75 @@ __device__ __forceinline__ void glds4_m0(const void* gbase_uniform, u32 voff) {
     static_assert(OFF >= -4096 && OFF <= 4095, "13-bit signed instruction offset");
     asm volatile("global_load_lds_dword %0, %1 offset:%2" ::"v"(voff), "s"(uniform_ptr(gbase_uniform)), "n"(OFF) : "memory");
 }
+// A whole ring unit in one statement (the int8 stream, sq_dense_i8.hpp): eight 1 KiB pieces behind ONE write of M0
+// (= lds_dst + 4096: the instruction offsets -4096 .. 3072 reach the eight pieces, and `voff_s[j]` is the lane's source
+// offset of piece j plus 4096 - 1024 j, so that the global address stays where it was), then -- TERMS -- the 256 bytes of
+// row terms behind a second write.  Straight-line: no M0 save / restore (nothing else in these kernels reads M0, and
+// hipcc keeps nothing in it across a statement), one wait state after each M0 write (SALU write of M0 -> LDS-DMA), no
+// branch.  The "s" operands must come from scalar arithmetic, never straight from a v_readfirstlane (VALU write of an
+// SGPR -> VMEM read of it: five wait states nobody would insert here).
+#define SQ_GLDS16X8(NT_)                                              \
+    "s_mov_b32 m0, %9\n\t"                                            \
+    "s_nop 0\n\t"                                                     \
+    "global_load_lds_dwordx4 %0, %8 offset:-4096" NT_ "\n\t"          \
+    "global_load_lds_dwordx4 %1, %8 offset:-3072" NT_ "\n\t"          \
+    "global_load_lds_dwordx4 %2, %8 offset:-2048" NT_ "\n\t"          \
+    "global_load_lds_dwordx4 %3, %8 offset:-1024" NT_ "\n\t"          \
+    "global_load_lds_dwordx4 %4, %8" NT_ "\n\t"                       \
+    "global_load_lds_dwordx4 %5, %8 offset:1024" NT_ "\n\t"           \
+    "global_load_lds_dwordx4 %6, %8 offset:2048" NT_ "\n\t"           \
+    "global_load_lds_dwordx4 %7, %8 offset:3072" NT_
+#define SQ_GLDS4_TERMS           \
+    "\n\ts_mov_b32 m0, %10\n\t"  \
+    "s_nop 0\n\t"                \
+    "global_load_lds_dword %11, %12"
+template <bool NT, bool TERMS>
+__device__ __forceinline__ void glds_unit8(const void* gbase_uniform, const u32* voff_s, u32 lds_dst, const void* terms_uniform = nullptr,
+                                           u32 voff_terms = 0, u32 lds_terms = 0) {
+    const u32 m0a = __builtin_amdgcn_readfirstlane(lds_dst + 4096u), m0b = __builtin_amdgcn_readfirstlane(lds_terms);
+    const void* gb = uniform_ptr(gbase_uniform);
+    if constexpr (TERMS) {
+        const void* tb = uniform_ptr(terms_uniform);
+        if constexpr (NT)
+            asm volatile(SQ_GLDS16X8(" nt") SQ_GLDS4_TERMS ::"v"(voff_s[0]), "v"(voff_s[1]), "v"(voff_s[2]), "v"(voff_s[3]), "v"(voff_s[4]),
+                         "v"(voff_s[5]), "v"(voff_s[6]), "v"(voff_s[7]), "s"(gb), "s"(m0a), "s"(m0b), "v"(voff_terms), "s"(tb)
+                         : "memory");
+        else
+            asm volatile(SQ_GLDS16X8("") SQ_GLDS4_TERMS ::"v"(voff_s[0]), "v"(voff_s[1]), "v"(voff_s[2]), "v"(voff_s[3]), "v"(voff_s[4]),
+                         "v"(voff_s[5]), "v"(voff_s[6]), "v"(voff_s[7]), "s"(gb), "s"(m0a), "s"(m0b), "v"(voff_terms), "s"(tb)
+                         : "memory");
+    } else {
+        if constexpr (NT)
+            asm volatile(SQ_GLDS16X8(" nt")::"v"(voff_s[0]), "v"(voff_s[1]), "v"(voff_s[2]), "v"(voff_s[3]), "v"(voff_s[4]), "v"(voff_s[5]),
+                         "v"(voff_s[6]), "v"(voff_s[7]), "s"(gb), "s"(m0a)
+                         : "memory");
+        else
+            asm volatile(SQ_GLDS16X8("")::"v"(voff_s[0]), "v"(voff_s[1]), "v"(voff_s[2]), "v"(voff_s[3]), "v"(voff_s[4]), "v"(voff_s[5]),
+                         "v"(voff_s[6]), "v"(voff_s[7]), "s"(gb), "s"(m0a)
+                         : "memory");
+    }
+}
+#undef SQ_GLDS16X8
+#undef SQ_GLDS4_TERMS
+
+// A ticket of a workgroup's LDS counter: lane 0 alone adds one (the statement narrows exec itself: every lane of the wave
+// must be active) and the old value comes back wave-uniform.  One statement with its own wait, so nothing reads the
+// register before the value has landed; hipcc's own sequence for `if (lane == 0) atomicAdd` is three times as long.
+__device__ __forceinline__ u32 lds_ticket_take(u32 lds_addr) {
+    u32 tv;
+    u64 keep;
+    asm volatile(
+        "s_mov_b64 %1, exec\n\t"
+        "s_mov_b64 exec, 1\n\t"
+        "ds_add_rtn_u32 %0, %2, %3\n\t"
+        "s_mov_b64 exec, %1\n\t"
+        "s_waitcnt lgkmcnt(0)"
+        : "=&v"(tv), "=&s"(keep)
+        : "v"(lds_addr), "v"(1u)
+        : "memory");
+    return (u32)__builtin_amdgcn_readfirstlane((int)tv);
+}
+
 // call f(integral_constant<int, j>) for the one j in [0, N) that equals the (compile-time foldable) argument
 template <int N, int J = 0, class F>
 __device__ __forceinline__ void static_for_one(int j, F&& f) {
