@@ -104,8 +104,39 @@ extern "C" {
  * regimes of the scan grid, 64 KiB of tables in ranges that begin inside a query, m from 1 to 64, d / m from 1 to 16384,
  * sq_pq_residuals in host and device memory (d = 35 from an unaligned base, in place), and one list with a zero
  * centroid, where the answers are the plain mode's bits.
- * Left out on purpose: OPQ rotations, FAISS's precomputed-table decomposition of the residual distance, code sizes other than one byte, a refine stage over kept float32
- * rows, cosine, asynchronous calls, removal in place, retraining. */
+ *
+ * Packed mode (sq_pq_create_packed): the same index, plain (residual = 0) or residual, with codebooks of at most 16
+ * entries and two codes per byte -- FAISS's "IVFx,PQyx4".  A handle made by the two other entry points is untouched by
+ * it.  List, residual, code, tables, the left-to-right sum of m entries, the correctly rounded root, result order,
+ * padding, ids, k and nprobe are the ones above, restricted to ksub in 1 .. 16; only the storage differs:
+ *   row       byte b holds code[2b] in its low nibble and code[2b + 1] in its high nibble; a missing last code and the
+ *             padding are zero; the row stride is round_up(ceil(m / 2), 4) bytes: 20 bytes per row with the insertion
+ *             number at m = 32, and m = 64 in the 36 bytes m = 32 takes with one byte per code.
+ *   sq_pq_create_packed   sq_pq_create's arguments and `residual`; m in 1 .. 64; ksub outside 1 .. 16: SQ_ERR_INVALID; the
+ *                  other refusals are sq_pq_create's, made before a device is touched.  Codebooks: sq_pq_train, ksub <= 16.
+ *   sq_pq_add      codes sub-quantiser by sub-quantiser as above; pq4_pack_kernel writes nibble j of every new row (a lane
+ *                  owns a row: even j writes the byte, odd j ors into it on the same stream).
+ *   sq_pq_lists    codes unpacked to [rows][m] bytes.  sq_pq_info: word 5 is rows x stride.  bytes_scanned: candidates x stride.
+ *   sq_pq_search   the tables keep the layout [unit][m][ksub].  pq4_tables_kernel -- a workgroup takes one unit (a query of
+ *                  the slice, or a pair) and 16 sub-quantisers, 16 lanes each, the 16 sub-vectors staged in
+ *                  16 * round_up(d / m, 4) * 4 <= 65536 bytes of dynamic LDS -- writes them with pq_tables_kernel's sum
+ *                  and bits; wider sub-vectors go through pq_tables_kernel / pq_tables_res_kernel.  pq4_scan_kernel, on
+ *                  the grids above and writing the same keys, allocates no LDS and has no barrier: a wave keeps its
+ *                  unit's tables in registers (register j of lane L holds T[j][min(L & 15, ksub - 1)]) and a lane fetches
+ *                  entry code[j] from the lane that holds it (ds_bpermute_b32), for j = 0 .. m-1 in order.  A cross-lane
+ *                  read from a lane that is switched off returns garbage, so every lane stays active through the lookups:
+ *                  a lane behind the last row computes on the last valid row and only skips the store.  Option
+ *                  "profile" = 1 as above (scan_ms the scan kernel, rerank_ms the tables kernel); 2 behaves as 1.
+ * Run by the tests (tests/test_hip_pq_packed.py): every row stride and nibble parity (m = 1 .. 17 and the first and last
+ * m of every further stride up to 64) at ksub 13 and 16 with two adds, plain and residual; the 5-row list, empty lists and
+ * a list beyond 1024 rows at nprobe 1 .. beyond nlist, k beyond the rows, 1 and 33 queries, host and device memory, id_base
+ * beyond 2^32; ksub 1, 2, 3; the stride loop in both regimes of the grid; pair ranges that begin inside a query; d / m
+ * of 1, 4, 129, 1024 (pq4_tables_kernel) and 1028 (the two other tables kernels); a query whose tables overflow; three
+ * adds against one; an empty index; and against a one-byte index over the same centroids, codebooks and rows, whose bits
+ * a packed index gives.
+ * Left out on purpose: OPQ rotations, FAISS's precomputed-table decomposition of the residual distance, code sizes other
+ * than one byte and four bits, m beyond 64, a refine stage over kept float32 rows, cosine, asynchronous calls, removal in
+ * place, retraining. */
 #define SQ_PQ_INFO_FIELDS 10
 int sq_pq_train(const float* x, int64_t n, int d, int m, int ksub,
                 float* codebooks /* [m][ksub][d/m]; in: initial, out: trained */, int iters, int mem);
@@ -113,6 +144,8 @@ int sq_pq_create(const float* centroids, int nlist, int d, const float* codebook
                  int64_t id_base, sq_handle_t* out);
 int sq_pq_create_residual(const float* centroids, int nlist, int d, const float* codebooks, int m, int ksub,
                           int64_t id_base, sq_handle_t* out);
+int sq_pq_create_packed(const float* centroids, int nlist, int d, const float* codebooks, int m, int ksub, int residual,
+                        int64_t id_base, sq_handle_t* out);
 int sq_pq_residuals(const float* x, int64_t n, int d, const float* centroids /* [nlist][d], host */, int nlist,
                     float* out /* [n][d], in `mem` as x */, int mem);
 int sq_pq_add(sq_handle_t h, const float* rows, int64_t n_add, int mem);

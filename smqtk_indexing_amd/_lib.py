@@ -67,10 +67,11 @@ IVF_EXPORTS = ("sq_ivf_kmeans", "sq_ivf_create", "sq_ivf_add", "sq_ivf_lists", "
 # The IVF-PQ extension library (include/smqtk_hip_pq.h), beside the other two and built on top of both.
 PQ_LIB_NAME = "libsmqtk_hip_pq.so"
 PQ_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), PQ_LIB_NAME)
-PQ_EXPORTS = ("sq_pq_train", "sq_pq_create", "sq_pq_create_residual", "sq_pq_residuals", "sq_pq_add", "sq_pq_lists", "sq_pq_info", "sq_pq_search", "sq_pq_destroy")
+PQ_EXPORTS = ("sq_pq_train", "sq_pq_create", "sq_pq_create_residual", "sq_pq_create_packed", "sq_pq_residuals", "sq_pq_add", "sq_pq_lists", "sq_pq_info", "sq_pq_search", "sq_pq_destroy")
 SQ_PQ_INFO_FIELDS = 10      # words of sq_pq_info (smqtk_hip_pq.h)
 SQ_PQ_MAX_M = 64            # sub-quantisers of an IVF-PQ index: a query's tables stay within 64 KiB of LDS
 SQ_PQ_MAX_KSUB = 256        # entries per codebook: one byte per code
+SQ_PQ_PACKED_MAX_KSUB = 16  # ... of a packed index (sq_pq_create_packed): two codes per byte
 
 
 class HipError(RuntimeError):
@@ -240,6 +241,7 @@ def load_pq() -> ctypes.CDLL:
             lib.sq_pq_train.argtypes = [c_vp, c_i64, c_int, c_int, c_int, c_vp, c_int, c_int]
             lib.sq_pq_create.argtypes = [c_vp, c_int, c_int, c_vp, c_int, c_int, c_i64, ctypes.POINTER(c_i64)]
             lib.sq_pq_create_residual.argtypes = lib.sq_pq_create.argtypes
+            lib.sq_pq_create_packed.argtypes = [c_vp, c_int, c_int, c_vp, c_int, c_int, c_int, c_i64, ctypes.POINTER(c_i64)]
             lib.sq_pq_residuals.argtypes = [c_vp, c_i64, c_int, c_vp, c_int, c_vp, c_int]
             lib.sq_pq_add.argtypes = [c_i64, c_vp, c_i64, c_int]
             lib.sq_pq_lists.argtypes = [c_i64, c_vp, c_vp, c_vp]
@@ -787,7 +789,9 @@ class PqIndex(_Handle):
     """Inverted lists of product-quantiser codes (``sq_pq_*``): a row is kept as ``m`` bytes in the list of its nearest
     centroid, a search adds ``m`` table entries per row of the ``nprobe`` nearest lists.  ``residual=True``
     (``sq_pq_create_residual``): the rows are coded as residuals against their list's centroid and a query gets one
-    table set per probed list.  L2 only.  Use as a context manager or ``close()`` it."""
+    table set per probed list.  ``packed=True`` (``sq_pq_create_packed``, with either ``residual``): codebooks of at most
+    16 entries, two codes per byte on the device; ``lists()`` still returns one byte per code.  L2 only.  Use as a context
+    manager or ``close()`` it."""
     _destroy_name = "sq_pq_destroy"
     INFO_FIELDS = ("rows", "d", "nlist", "m", "ksub", "codes_bytes", "ids_offsets_bytes", "books_coarse_bytes", "add_us",
                    "key_budget_bytes")
@@ -800,17 +804,21 @@ class PqIndex(_Handle):
             except Exception:
                 pass
 
-    def __init__(self, centroids: np.ndarray, codebooks: np.ndarray, id_base: int = 0, residual: bool = False):
+    def __init__(self, centroids: np.ndarray, codebooks: np.ndarray, id_base: int = 0, residual: bool = False, packed: bool = False):
         super().__init__()
         c = _host(centroids, np.float32)
         b = _host(codebooks, np.float32)
         if c.ndim != 2 or b.ndim != 3 or b.shape[0] * b.shape[2] != c.shape[1]:
             raise ValueError("centroids must be float32[nlist, d] and codebooks float32[m, ksub, d / m]")
         self.nlist, self.d, self.id_base, self.n = int(c.shape[0]), int(c.shape[1]), int(id_base), 0
-        self.m, self.ksub, self.residual = int(b.shape[0]), int(b.shape[1]), bool(residual)
+        self.m, self.ksub, self.residual, self.packed = int(b.shape[0]), int(b.shape[1]), bool(residual), bool(packed)
         h = ctypes.c_int64(0)
-        name = "sq_pq_create_residual" if self.residual else "sq_pq_create"
-        _check(getattr(load_pq(), name)(_ptr(c), self.nlist, self.d, _ptr(b), self.m, self.ksub, self.id_base, ctypes.byref(h)), name)
+        if self.packed:
+            _check(load_pq().sq_pq_create_packed(_ptr(c), self.nlist, self.d, _ptr(b), self.m, self.ksub, int(self.residual), self.id_base,
+                                                 ctypes.byref(h)), "sq_pq_create_packed")
+        else:
+            name = "sq_pq_create_residual" if self.residual else "sq_pq_create"
+            _check(getattr(load_pq(), name)(_ptr(c), self.nlist, self.d, _ptr(b), self.m, self.ksub, self.id_base, ctypes.byref(h)), name)
         self.handle = int(h.value)
 
     def __enter__(self) -> "PqIndex":

@@ -14,6 +14,10 @@
 // (pq_residual_kernel, also behind sq_pq_residuals), a query gets one table set per probed list (pq_tables_res_kernel)
 // and pq_scan_res_kernel walks one (query, probed list) pair's rows per workgroup.  Both scans share pq_stage_tables and
 // pq_row_sum; a handle made by sq_pq_create takes none of the residual branches.
+//
+// Packed mode (sq_pq_create_packed, plain or residual) is the same handle with `packed` set: ksub <= 16, two codes per
+// byte, and kernels of its own (pq4_pack_kernel here; in sq_pq_packed.hpp tables for small codebooks and a scan that keeps the tables
+// in registers).  Handles made by the two other entry points take none of the packed branches.
 #include <algorithm>
 #include <chrono>
 #include <vector>
@@ -40,6 +44,7 @@ struct PqHandle : HandleBase {
     bool residual = false;
     long long cds = 0;                   // floats of a centroid in `cent`
     DevBuf cent;                         // [nlist][cds] float32, zero padded: what the residual and residual-tables kernels read
+    bool packed = false;                 // packed mode (sq_pq_create_packed): two codes per byte, cs = pq_packed_stride(m)
     // scratch of a search
     DevBuf q_dev, probe_dist, probe_idx, pre, cnt, tables, keys, out_keys, out_dist, out_idx, sort_tmp;
     HostPinned totals_host;              // [candidates in total, longest candidate list]
@@ -60,6 +65,23 @@ static __global__ __launch_bounds__(256) void pq_pack_kernel(const long long* __
     long long c = entry[i];
     c = c < 0 ? 0 : (c >= ksub ? ksub - 1 : c);
     codes[i * cs + j] = (unsigned char)c;
+}
+// Packed mode (sq_pq_create_packed): nibble j of the rows of an add, in insertion order.  An even j writes its byte (high nibble zero), the odd j that
+// follows it on the same stream ors into it; a lane owns a row, so no two lanes share a byte.
+static __global__ __launch_bounds__(256) void pq4_pack_kernel(const long long* __restrict__ entry, long long n, int ksub, int j, long long cs,
+                                                               unsigned char* __restrict__ codes) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    long long c = entry[i];
+    c = c < 0 ? 0 : (c >= ksub ? ksub - 1 : c);
+    unsigned char* b = codes + i * cs + (j >> 1);
+    *b = (j & 1) ? (unsigned char)(*b | (c << 4)) : (unsigned char)c;
+}
+
+// [rows][cs] packed bytes -> [rows][m] code bytes (sq_pq_lists), on the host
+static void pq4_unpack_rows(const unsigned char* packed, long long rows, long long cs, int m, unsigned char* out) {
+    for (long long i = 0; i < rows; ++i)
+        for (int j = 0; j < m; ++j) out[i * m + j] = (unsigned char)((packed[i * cs + (j >> 1)] >> (4 * (j & 1))) & 15);
 }
 // Both scatters move a coded row as `w` dwords, one lane per dword.
 // old row s of list l -> new_off[l] + (s - old_off[l])
@@ -147,8 +169,12 @@ static int pq_add_part(PqHandle* h, const float* rows, long long n_add, int mem)
             xj = part.as<float>();
         }
         SQ_TRY(ivf_assign(h->sub[(size_t)j], xj, n_add, dsub, entry.as<long long>(), adist.as<float>(), st));
-        SQ_TRY(launch<pq_pack_kernel>(dim3((unsigned)((n_add + 255) / 256)), dim3(256), 0, st, entry.as<long long>(), n_add, h->ksub, j, cs,
-                                      fresh.as<unsigned char>()));
+        if (h->packed)
+            SQ_TRY(launch<pq4_pack_kernel>(dim3((unsigned)((n_add + 255) / 256)), dim3(256), 0, st, entry.as<long long>(), n_add, h->ksub, j, cs,
+                                           fresh.as<unsigned char>()));
+        else
+            SQ_TRY(launch<pq_pack_kernel>(dim3((unsigned)((n_add + 255) / 256)), dim3(256), 0, st, entry.as<long long>(), n_add, h->ksub, j, cs,
+                                          fresh.as<unsigned char>()));
     }
     SQ_HIP(hipStreamSynchronize(st));
     up.release();
@@ -351,6 +377,24 @@ static __global__ __launch_bounds__(256) void pq_scan_res_kernel(const u32* __re
     }
 }
 
+}  // namespace sq
+
+#include "sq_pq_packed.hpp"   // packed mode: pq4_tables_kernel, pq4_scan_kernel (over PqPair / pq_pair above)
+
+namespace sq {
+
+// Packed mode: the arguments of a tables launch and of a scan launch over the handle's buffers.
+static Pq4Tables pq4_tables_args(const PqHandle* h, const float* q_dev, int q0, long long p0, int np) {
+    return Pq4Tables{h->books.as<float>(), h->es, h->dsub, h->ksub, h->m, h->d, q_dev, h->cent.as<float>(), h->cds, q0, p0, np,
+                     h->probe_idx.as<long long>(), h->list_off.as<long long>(), h->nlist, h->tables.as<float>()};
+}
+static Pq4Scan pq4_scan_args(const PqHandle* h, int q0, long long p0, int np, long long mc) {
+    return Pq4Scan{h->codes.as<u32>(), h->m, h->ksub, h->ids.as<u32>(), h->list_off.as<long long>(), h->nlist, h->tables.as<float>(), q0, p0,
+                   h->probe_idx.as<long long>(), h->pre.as<long long>(), np, mc, h->keys.as<u64>()};
+}
+// codebooks of at most 16 entries get the tables kernel that fills its workgroups, while its LDS is a plain launch's
+static bool pq4_small_tables(const PqHandle* h) { return h->packed && pq_small_tables_fit(h->es); }
+
 // The scan of a slice in residual mode: its ns * np pairs in ranges of `ppl`, each range one tables launch and one scan
 // launch into the slice's keys.
 static int pq_scan_residual(PqHandle* h, const float* q_dev, int q0, int ns, int np, long long ppl, long long mc, hipStream_t st) {
@@ -361,13 +405,18 @@ static int pq_scan_residual(PqHandle* h, const float* q_dev, int q0, int ns, int
     for (long long p0 = 0; p0 < pairs; p0 += ppl) {
         const long long pl = pairs - p0 < ppl ? pairs - p0 : ppl;
         if (prof) SQ_HIP(hipEventRecord(h->ev[0], st));
-        SQ_TRY(launch<pq_tables_res_kernel>(dim3((unsigned)m, (unsigned)pl), dim3(256), (size_t)h->es * 4, st, h->books.as<float>(), h->es,
-                                            h->dsub, ksub, m, q_dev, h->d, h->cent.as<float>(), h->cds, q0, p0, np,
-                                            h->probe_idx.as<long long>(), h->list_off.as<long long>(), h->nlist, h->tables.as<float>()));
+        if (pq4_small_tables(h))
+            SQ_TRY(pq4_tables_launch(true, pq4_tables_args(h, q_dev, q0, p0, np), pl, st));
+        else
+            SQ_TRY(launch<pq_tables_res_kernel>(dim3((unsigned)m, (unsigned)pl), dim3(256), (size_t)h->es * 4, st, h->books.as<float>(), h->es,
+                                                h->dsub, ksub, m, q_dev, h->d, h->cent.as<float>(), h->cds, q0, p0, np,
+                                                h->probe_idx.as<long long>(), h->list_off.as<long long>(), h->nlist, h->tables.as<float>()));
         if (prof) SQ_HIP(hipEventRecord(h->ev[1], st));
         const dim3 grid((unsigned)pq_scan_groups(ivf_chunks(lmax), pl, cu_count(h->device)), (unsigned)pl);
         const int lds_max = (int)pq_table_bytes(kPqMaxM, kPqMaxKsub);
-        if (w % 4 == 0)
+        if (h->packed)
+            SQ_TRY(pq4_scan_launch(true, w, grid, st, pq4_scan_args(h, q0, p0, np, mc)));
+        else if (w % 4 == 0)
             SQ_TRY(launch_lds<pq_scan_res_kernel<true>>(lds_max, grid, dim3(256), tb, st, h->codes.as<u32>(), w, m, ksub, h->ids.as<u32>(),
                                                         h->list_off.as<long long>(), h->nlist, h->tables.as<float>(), q0, p0,
                                                         h->probe_idx.as<long long>(), h->pre.as<long long>(), np, mc, h->keys.as<u64>()));
@@ -430,11 +479,15 @@ static int pq_search_device(PqHandle* h, const float* q_dev, int nq, int k, int 
             // pq_scan_kernel that only stages the tables (the real scan follows it, untimed)
             const int prof_mode = h->opt.profile;
             if (prof) SQ_HIP(hipEventRecord(h->ev[0], st));
-            SQ_TRY(launch<pq_tables_kernel>(dim3((unsigned)m, (unsigned)ns), dim3(256), (size_t)h->es * 4, st, h->books.as<float>(), h->es,
-                                            h->dsub, ksub, m, q_dev + (size_t)q0 * d, d, h->tables.as<float>()));
+            if (pq4_small_tables(h))
+                SQ_TRY(pq4_tables_launch(false, pq4_tables_args(h, q_dev, q0, 0, np), ns, st));
+            else
+                SQ_TRY(launch<pq_tables_kernel>(dim3((unsigned)m, (unsigned)ns), dim3(256), (size_t)h->es * 4, st, h->books.as<float>(), h->es,
+                                                h->dsub, ksub, m, q_dev + (size_t)q0 * d, d, h->tables.as<float>()));
             if (prof) SQ_HIP(hipEventRecord(h->ev[1], st));
             const dim3 grid((unsigned)pq_scan_groups(ivf_chunks(maxc), ns, cu_count(h->device)), (unsigned)ns);
             auto scan = [&](int stage_only) {
+                if (h->packed) return pq4_scan_launch(false, w, grid, st, pq4_scan_args(h, q0, 0, np, mc));   // (nothing is staged: "profile" = 2 is 1)
                 const int lds_max = (int)pq_table_bytes(kPqMaxM, kPqMaxKsub);
                 if (w % 4 == 0)
                     return launch_lds<pq_scan_kernel<true>>(lds_max, grid, dim3(256), tb, st, h->codes.as<u32>(), w, m, ksub, h->ids.as<u32>(),
@@ -444,7 +497,7 @@ static int pq_search_device(PqHandle* h, const float* q_dev, int nq, int k, int 
                                                          h->list_off.as<long long>(), h->tables.as<float>(), q0, h->probe_idx.as<long long>(),
                                                          h->pre.as<long long>(), np, mc, h->keys.as<u64>(), stage_only);
             };
-            SQ_TRY(scan(prof_mode == 2 ? 1 : 0));
+            SQ_TRY(scan(prof_mode == 2 && !h->packed ? 1 : 0));
             if (prof) {
                 SQ_HIP(hipEventRecord(h->ev[2], st));
                 SQ_HIP(hipEventSynchronize(h->ev[2]));
@@ -454,7 +507,7 @@ static int pq_search_device(PqHandle* h, const float* q_dev, int nq, int k, int 
                 SQ_HIP(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
                 h->stats.rerank_ms += ms;
             }
-            if (prof_mode == 2) SQ_TRY(scan(0));
+            if (prof_mode == 2 && !h->packed) SQ_TRY(scan(0));
             h->stats.scan_launches++;
         }
         const IvfFinalize fin{q0, k, h->id_base, od, oi};
@@ -512,20 +565,22 @@ static int pq_upload_centroids(const float* centroids, int nlist, int d, DevBuf&
     return SQ_OK;
 }
 
-static int pq_create(const char* who, bool residual, const float* centroids, int nlist, int d, const float* codebooks, int m, int ksub,
+static int pq_create(const char* who, bool residual, bool packed, const float* centroids, int nlist, int d, const float* codebooks, int m, int ksub,
                      int64_t id_base, sq_handle_t* out) {
     if (!centroids || !codebooks || !out || nlist <= 0 || d <= 0) return fail(SQ_ERR_INVALID, "%s: bad argument", who);
     SQ_TRY(pq_shape_check(who, d, m, ksub));
+    if (packed && ksub > kPqPackedMaxKsub) return fail(SQ_ERR_INVALID, "%s: ksub = %d is outside 1 .. %d", who, ksub, kPqPackedMaxKsub);
     if (nlist > kIvfMaxLists) return fail(SQ_ERR_UNSUPPORTED, "%s: more than %d lists", who, kIvfMaxLists);
     auto h = std::make_unique<PqHandle>();
     h->residual = residual;
+    h->packed = packed;
     h->kind = H_PQ;
     h->d = d;
     h->nlist = nlist;
     h->m = m;
     h->ksub = ksub;
     h->dsub = d / m;
-    h->cs = pq_code_stride(m);
+    h->cs = packed ? pq_packed_stride(m) : pq_code_stride(m);
     h->es = pq_entry_stride(h->dsub);
     h->id_base = id_base;
     h->refresh_options();
@@ -549,12 +604,17 @@ static int pq_create(const char* who, bool residual, const float* centroids, int
 
 extern "C" int sq_pq_create(const float* centroids, int nlist, int d, const float* codebooks, int m, int ksub, int64_t id_base,
                             sq_handle_t* out) {
-    return pq_create("sq_pq_create", false, centroids, nlist, d, codebooks, m, ksub, id_base, out);
+    return pq_create("sq_pq_create", false, false, centroids, nlist, d, codebooks, m, ksub, id_base, out);
 }
 
 extern "C" int sq_pq_create_residual(const float* centroids, int nlist, int d, const float* codebooks, int m, int ksub, int64_t id_base,
                                      sq_handle_t* out) {
-    return pq_create("sq_pq_create_residual", true, centroids, nlist, d, codebooks, m, ksub, id_base, out);
+    return pq_create("sq_pq_create_residual", true, false, centroids, nlist, d, codebooks, m, ksub, id_base, out);
+}
+
+extern "C" int sq_pq_create_packed(const float* centroids, int nlist, int d, const float* codebooks, int m, int ksub, int residual,
+                                   int64_t id_base, sq_handle_t* out) {
+    return pq_create("sq_pq_create_packed", residual != 0, true, centroids, nlist, d, codebooks, m, ksub, id_base, out);
 }
 
 extern "C" int sq_pq_residuals(const float* x, int64_t n, int d, const float* centroids, int nlist, float* out, int mem) {
@@ -618,7 +678,15 @@ extern "C" int sq_pq_lists(sq_handle_t hid, int64_t* list_off, int64_t* ids, uin
         SQ_HIP(hipMemcpy(tmp.data(), h->ids.p, (size_t)h->n * 4, hipMemcpyDeviceToHost));
         for (long long i = 0; i < h->n; ++i) ids[i] = h->id_base + (int64_t)tmp[(size_t)i];
     }
-    if (codes && h->n > 0)   // (the 2-D copy drops the padding of a row)
+    if (codes && h->n > 0 && h->packed) {   // packed rows come down as they are and are unpacked here, a block at a time
+        const long long block = 1ll << 20;
+        std::vector<unsigned char> tmp((size_t)(std::min(block, h->n) * h->cs));
+        for (long long s = 0; s < h->n; s += block) {
+            const long long rows = std::min(block, h->n - s);
+            SQ_HIP(hipMemcpy(tmp.data(), h->codes.as<unsigned char>() + s * h->cs, (size_t)(rows * h->cs), hipMemcpyDeviceToHost));
+            pq4_unpack_rows(tmp.data(), rows, h->cs, h->m, codes + s * h->m);
+        }
+    } else if (codes && h->n > 0)   // (the 2-D copy drops the padding of a row)
         SQ_HIP(hipMemcpy2D(codes, (size_t)h->m, h->codes.p, (size_t)h->cs, (size_t)h->m, (size_t)h->n, hipMemcpyDeviceToHost));
     return SQ_OK;
 }

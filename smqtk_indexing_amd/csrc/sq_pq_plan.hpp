@@ -30,6 +30,19 @@ inline long long pq_codes_bytes(long long n, int m) { return n * pq_code_stride(
 // floats per codebook entry as the tables kernel reads it: whole 16-byte pieces, zero padded (ivf_row_stride's rule)
 inline long long pq_entry_stride(int dsub) { return ivf_row_stride(dsub); }
 
+// ---- packed mode (sq_pq_create_packed): ksub <= 16, two codes per byte -- byte b of a row holds code[2b] in its low
+// nibble and code[2b + 1] in its high nibble, a missing last code and the padding are zero.  A row is w = ceil(m / 8)
+// dwords, 1 .. 8, and the scan is instantiated per w (16-byte loads for w = 4 and 8).
+static constexpr int kPqPackedMaxKsub = 16;      // entries per codebook: a code is a nibble, a table 16 lanes of one register
+static constexpr int kPqPackedMaxDwords = 8;     // dwords of a packed row at m = kPqMaxM
+inline long long pq_packed_stride(int m) { return (((long long)m + 1) / 2 + 3) / 4 * 4; }
+// The tables kernel for small codebooks: a workgroup takes kPqSmallBlock sub-quantisers of one unit, 16 lanes each, and
+// stages their sub-vectors in kPqSmallBlock * es floats of dynamic LDS; it applies while that is what a plain launch takes.
+static constexpr int kPqSmallBlock = 16;
+inline long long pq_small_tables_lds(long long es) { return kPqSmallBlock * es * 4; }
+inline bool pq_small_tables_fit(long long es) { return pq_small_tables_lds(es) <= 65536; }
+inline long long pq_small_tables_blocks(int m) { return ((long long)m + kPqSmallBlock - 1) / kPqSmallBlock; }
+
 // a query's distance tables: [m][ksub] float32, in global memory per query of a slice and in a scan workgroup's LDS
 inline long long pq_table_bytes(int m, int ksub) { return (long long)m * ksub * 4; }
 

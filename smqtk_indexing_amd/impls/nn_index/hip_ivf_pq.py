@@ -31,6 +31,8 @@ from .hip_ivf import _ListIndexHostLogic, training_draws
 class HipIvfPqNearestNeighborsIndex(_ListIndexHostLogic, NearestNeighborsIndex):
     """L2 kNN by product-quantiser codes over the lists of the ``nprobe`` nearest k-means centroids (HIP kernels)."""
 
+    MAX_ENTRIES = _lib.SQ_PQ_MAX_KSUB      # initial codebook entries at most: ksub = min(MAX_ENTRIES, sample rows)
+
     @classmethod
     def is_usable(cls) -> bool:
         return _lib.pq_usable()
@@ -68,9 +70,9 @@ class HipIvfPqNearestNeighborsIndex(_ListIndexHostLogic, NearestNeighborsIndex):
     def training_plan(self, n: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """(sample rows, positions of the initial centroids inside the sample, positions of the initial codebook
         entries inside the sample): the first two are the IVF-Flat class's, the third is one further draw of
-        ``min(256, sample rows)`` distinct sample rows from the same generator."""
+        ``min(MAX_ENTRIES, sample rows)`` distinct sample rows from the same generator (``MAX_ENTRIES`` = 256 here)."""
         sample, init, rs = training_draws(n, self.effective_nlist(n), self.random_seed)
-        entries = rs.choice(len(sample), size=min(_lib.SQ_PQ_MAX_KSUB, len(sample)), replace=False)
+        entries = rs.choice(len(sample), size=min(self.MAX_ENTRIES, len(sample)), replace=False)
         return sample, init, entries
 
     # The two places a subclass that codes something else than the rows themselves differs in.

@@ -20,6 +20,12 @@ alternating windows, and under each table its call time is given as a ratio to p
 (profiles/ivf_pq_residual.txt is the output with this flag).  For a residual index "tables kernel" is
 pq_tables_res_kernel summed over the launches of a call; option "profile" = 2 means 1 there, so no staging-only figure.
 
+--packed adds the packed 4-bit index (sq_pq_create_packed) of every m of --packed-ms, plain ("p4_<m>") and residual
+("rp4_<m>"): 16-entry codebooks trained on the same sample (its residuals) from the first 16 entry rows.  Beside them, at
+the largest of those m, the one-byte index over the SAME 16-entry codebooks ("w<m>", "rw<m>"): it must return identical
+answers, which is asserted on every warm-up call, and its scan at equal rows and equal m is what the packed scan's time
+is given as a ratio to.  profiles/ivf_pq_packed.txt is the output of --ms 32 --residual --packed --no-flat.
+
     python tools/pq_bench.py                      # the full table
     python tools/pq_bench.py --only 32,16 --ms 32 --calls 200 --windows 1 --no-flat --no-exact   # one shape, e.g. under a counter run
 """
@@ -56,6 +62,8 @@ def main():
     ap.add_argument("--no-flat", action="store_true")
     ap.add_argument("--no-exact", action="store_true")
     ap.add_argument("--residual", action="store_true", help="also the residual-mode index of every m")
+    ap.add_argument("--packed", action="store_true", help="also the packed 4-bit indexes and their one-byte twin")
+    ap.add_argument("--packed-ms", default="32,64")
     ap.add_argument("--out", default="", help="also write the report here")
     args = ap.parse_args()
 
@@ -122,11 +130,11 @@ def main():
             f"{res / matrix_bytes:.4f} x the matrix ({(info['codes_bytes'] + 4 * n) / n:.0f} bytes per row)")
         indexes[f"pq{m}"] = pq
         summary["indexes"][f"pq{m}"] = {"train_s": train_s, "add_s": add_s, "resident_bytes": res}
-    if args.residual:
+    if args.residual or args.packed:
         t0 = time.perf_counter()
         sample_res = _lib.pq_residuals(sample, centroids)
         say(f"residuals of the sample (sq_pq_residuals, host memory): {time.perf_counter() - t0:.2f} s")
-        for m in ms_:
+        for m in ms_ if args.residual else []:
             books0 = np.ascontiguousarray(sample_res[entry_rows].reshape(ksub, m, d // m).transpose(1, 0, 2))
             t0 = time.perf_counter()
             books = _lib.pq_train(sample_res, books0, args.iters)
@@ -139,6 +147,30 @@ def main():
                 f"{info['ids_offsets_bytes']}, codebooks + coarse index + centroids {info['books_coarse_bytes']} = {res} bytes = {res / matrix_bytes:.4f} x the matrix")
             indexes[f"rpq{m}"] = rpq
             summary["indexes"][f"rpq{m}"] = {"train_s": train_s, "add_s": add_s, "resident_bytes": res}
+    twins = {}      # packed index -> the one-byte index over the same codebooks
+    packed_names = set()
+    if args.packed:
+        pms = [int(v) for v in args.packed_ms.split(",")]
+        for m in pms:
+            for res_mode, src, tag in ((False, sample, ""), (True, sample_res, "r")):
+                books0 = np.ascontiguousarray(src[entry_rows[:16]].reshape(16, m, d // m).transpose(1, 0, 2))
+                t0 = time.perf_counter()
+                books = _lib.pq_train(src, books0, args.iters)
+                train_s = time.perf_counter() - t0
+                made = [(f"{tag}p4_{m}", True)] + ([(f"{tag}w{m}", False)] if m == max(pms) else [])
+                for name, packed in made:
+                    ix = _lib.PqIndex(centroids, books, residual=res_mode, packed=packed)
+                    add_s = add_all(ix)
+                    info = ix.info()
+                    res = info["codes_bytes"] + info["ids_offsets_bytes"] + info["books_coarse_bytes"]
+                    say(f"{name} m={m} ksub=16 ({'packed' if packed else 'one byte per code'}{', residual' if res_mode else ''}): codebooks {train_s:.2f} s, "
+                        f"add {add_s:.2f} s; resident (sq_pq_info): codes {info['codes_bytes']}, ids + offsets {info['ids_offsets_bytes']}, "
+                        f"rest {info['books_coarse_bytes']} = {res} bytes = {res / matrix_bytes:.4f} x the matrix ({(info['codes_bytes'] + 4 * n) / n:.0f} bytes per row)")
+                    indexes[name] = ix
+                    packed_names.add(name)
+                    summary["indexes"][name] = {"train_s": train_s, "add_s": add_s, "resident_bytes": res}
+                if len(made) == 2:
+                    twins[made[0][0]] = made[1][0]
     if not args.no_flat:
         flat = _lib.IvfIndex(centroids)
         add_s = add_all(flat)
@@ -175,18 +207,26 @@ def main():
                 shapes[(name, p)] = (lambda ix, p_: lambda q, od_, oi_: ix.search_device(q.data_ptr(), nq, k, p_, od_.data_ptr(), oi_.data_ptr(),
                                                                                         stream))(index, p)
         # answers once: recall against the exact ids, and the warm-up of every shape
-        truth, recall = [], {}
+        truth, recall, kept = [], {}, {}
         for name, call in shapes.items():
             hits = 0
             for j in range(nbatch):
                 call(qs[j], od, oi)
                 got = oi.cpu().numpy()
+                if name != "exact" and (name[0] in twins or name[0] in twins.values()):
+                    kept[(name, j)] = (got, od.cpu().numpy().view(np.uint32))
                 if name == "exact":
                     truth.append(got)
                 elif truth:
                     hits += sum(len(np.intersect1d(got[i], truth[j][i])) for i in range(nq))
             if name != "exact":
                 recall[name] = hits / (nbatch * nq * k) if truth else float("nan")
+        for (name, j), (ids_p, bits_p) in kept.items():   # the one-byte index over the same codebooks answers with the same bits
+            if name[0] in twins:
+                ids_w, bits_w = kept[((twins[name[0]], name[1]), j)]
+                assert np.array_equal(ids_p, ids_w) and np.array_equal(bits_p, bits_w), f"{name}: packed and one-byte answers differ (batch {j})"
+        if twins:
+            say(f"# {nq} quer{'y' if nq == 1 else 'ies'}: {' / '.join(f'{a} = {b}' for a, b in twins.items())}: identical ids and distance bits on all {nbatch} batches at every nprobe (asserted)")
         times = {name: [] for name in shapes}
         for _ in range(args.windows):
             for name, call in shapes.items():
@@ -225,7 +265,7 @@ def main():
                     f"{cands / (sms * 1e-3) / 1e9 if sms > 0 else float('nan'):6.2f} G rows/s"
                     + (f"   tables kernel {tms * 1e3:6.1f} us, staging-only scan launch {stage_ms * 1e3:6.1f} us = {100 * stage_ms / sms:4.1f} % of the scan"
                        if name.startswith("pq") and sms > 0 else
-                       f"   tables kernel {tms * 1e3:6.1f} us" if name.startswith("rpq") else ""))
+                       f"   tables kernel {tms * 1e3:6.1f} us" if name.startswith("rpq") or name in packed_names else ""))
                 report.append({"queries": nq, "nprobe": p, "index": name, "ms_per_call": t, "ms_fastest": min(times[key]), "ms_slowest": max(times[key]),
                                "recall": recall[key], "scan_kernel_ms": sms, "scan_bytes": by, "candidates": cands,
                                "tables_kernel_ms": tms, "staging_only_ms": stage_ms})
@@ -238,6 +278,13 @@ def main():
                     rs_, rp_ = scan[(f"rpq{m}", p)], scan[(f"pq{m}", p)]
                     say(f"nprobe {p:<3d} m={m:<2d}  rpq / pq {tr / tp:5.2f}   rpq / flat {tr / tf:5.2f}   recall@{k} rpq {recall[(f'rpq{m}', p)]:.3f} pq {recall[(f'pq{m}', p)]:.3f}"
                         f"   tables + scan kernels: rpq {rs_[3] * 1e3:7.1f} + {rs_[0] * 1e3:7.1f} us, pq {rp_[3] * 1e3:7.1f} + {rp_[0] * 1e3:7.1f} us")
+        if twins:
+            say(f"# packed against one byte per code over the same 16-entry codebooks (equal rows, equal m), {nq} quer{'y' if nq == 1 else 'ies'}: time ratios packed / one-byte")
+            for p in nprobes:
+                for a, b in twins.items():
+                    sa, sb = scan[(a, p)], scan[(b, p)]
+                    say(f"nprobe {p:<3d} {a} / {b}: call {statistics.median(times[(a, p)]) / statistics.median(times[(b, p)]):5.2f}   scan kernel {sa[0] / sb[0]:5.2f} "
+                        f"({sa[0] * 1e3:7.1f} / {sb[0] * 1e3:7.1f} us)   tables kernel {sa[3] / sb[3]:5.2f} ({sa[3] * 1e3:6.1f} / {sb[3] * 1e3:6.1f} us)")
     summary["shapes"] = report
     say()
     say(json.dumps(summary))
