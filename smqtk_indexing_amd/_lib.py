@@ -72,6 +72,12 @@ SQ_PQ_INFO_FIELDS = 10      # words of sq_pq_info (smqtk_hip_pq.h)
 SQ_PQ_MAX_M = 64            # sub-quantisers of an IVF-PQ index: a query's tables stay within 64 KiB of LDS
 SQ_PQ_MAX_KSUB = 256        # entries per codebook: one byte per code
 SQ_PQ_PACKED_MAX_KSUB = 16  # ... of a packed index (sq_pq_create_packed): two codes per byte
+# The IVF-SQ extension library (include/smqtk_hip_isq.h): built and found beside the main and the IVF-Flat library.
+ISQ_LIB_NAME = "libsmqtk_hip_isq.so"
+ISQ_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), ISQ_LIB_NAME)
+ISQ_EXPORTS = ("sq_isq_train", "sq_isq_create", "sq_isq_add", "sq_isq_lists", "sq_isq_info", "sq_isq_search", "sq_isq_destroy")
+SQ_ISQ_SQ8, SQ_ISQ_F16 = 0, 1   # kinds of an IVF-SQ index: one byte per dimension with trained ranges, or float16
+SQ_ISQ_INFO_FIELDS = 12     # words of sq_isq_info (smqtk_hip_isq.h)
 
 
 class HipError(RuntimeError):
@@ -254,6 +260,36 @@ def load_pq() -> ctypes.CDLL:
         return _pq_lib
 
 
+_isq_lib: Optional[ctypes.CDLL] = None
+
+
+def load_isq() -> ctypes.CDLL:
+    """Load the IVF-SQ extension library (once), after the two libraries it is built on.  Raises HipError when it is
+    missing: there is no fallback."""
+    global _isq_lib
+    load_ivf()
+    with _lock:
+        if _isq_lib is None:
+            if not os.path.isfile(ISQ_LIB_PATH):
+                raise HipError(f"{ISQ_LIB_NAME} not found at {ISQ_LIB_PATH}; build it with `make -C smqtk_indexing_amd/csrc`")
+            try:
+                lib = ctypes.CDLL(ISQ_LIB_PATH)
+            except OSError as ex:
+                raise HipError(f"cannot load {ISQ_LIB_PATH}: {ex}") from ex
+            c_int, c_i64, c_vp = ctypes.c_int, ctypes.c_int64, ctypes.c_void_p
+            lib.sq_isq_train.argtypes = [c_vp, c_i64, c_int, c_vp, c_vp, c_int]
+            lib.sq_isq_create.argtypes = [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_int, c_i64, ctypes.POINTER(c_i64)]
+            lib.sq_isq_add.argtypes = [c_i64, c_vp, c_i64, c_int]
+            lib.sq_isq_lists.argtypes = [c_i64, c_vp, c_vp, c_vp]
+            lib.sq_isq_info.argtypes = [c_i64, ctypes.POINTER(c_i64), c_int]
+            lib.sq_isq_search.argtypes = [c_i64, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_int, c_vp]
+            lib.sq_isq_destroy.argtypes = [c_i64]
+            for name in ISQ_EXPORTS:
+                getattr(lib, name).restype = c_int
+            _isq_lib = lib
+        return _isq_lib
+
+
 def _check(rc: int, what: str) -> None:
     if rc != SQ_OK:
         msg = load().sq_last_error()
@@ -289,6 +325,11 @@ def ivf_usable() -> bool:
 def pq_usable() -> bool:
     """A GPU, the main library and both extension libraries beside it."""
     return ivf_usable() and os.path.isfile(PQ_LIB_PATH)
+
+
+def isq_usable() -> bool:
+    """A GPU, the main library, the IVF-Flat extension and the IVF-SQ extension beside them."""
+    return ivf_usable() and os.path.isfile(ISQ_LIB_PATH)
 
 
 def device_name(device: int = 0) -> Tuple[str, int, int]:
@@ -874,6 +915,106 @@ class PqIndex(_Handle):
     def info(self) -> dict:
         out = (ctypes.c_int64 * SQ_PQ_INFO_FIELDS)()
         _check(load_pq().sq_pq_info(self.handle, out, SQ_PQ_INFO_FIELDS), "sq_pq_info")
+        return dict(zip(self.INFO_FIELDS, (int(v) for v in out)))
+
+
+def isq_train(x: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    """``sq_isq_train``: (``vmin``, ``step``) of an 8-bit scalar quantiser over the rows of ``x`` (``[n, d]`` float32,
+    host): the column minima and ``(max - min) / 255`` in float32."""
+    x = _host(x, np.float32)
+    if x.ndim != 2 or x.shape[0] == 0:
+        raise ValueError("x must be a non-empty [n, d]")
+    vmin, step = np.empty(x.shape[1], dtype=np.float32), np.empty(x.shape[1], dtype=np.float32)
+    _check(load_isq().sq_isq_train(_ptr(x), int(x.shape[0]), int(x.shape[1]), _ptr(vmin), _ptr(step), SQ_MEM_HOST), "sq_isq_train")
+    return vmin, step
+
+
+class IsqIndex(_Handle):
+    """Inverted lists of scalar-quantised rows (``sq_isq_*``): a row is kept in the list of its nearest centroid as one
+    byte per dimension (``kind=SQ_ISQ_SQ8``, with ``vmin`` / ``step`` from :func:`isq_train`) or as float16
+    (``kind=SQ_ISQ_F16``); a search decodes the rows of the ``nprobe`` nearest lists and ranks them by the decoded
+    distance.  L2 only.  Use as a context manager or ``close()`` it."""
+    _destroy_name = "sq_isq_destroy"
+    INFO_FIELDS = ("rows", "d", "nlist", "longest_list", "empty_lists", "codes_bytes", "ids_offsets_bytes", "coarse_params_bytes",
+                   "add_us", "key_budget_bytes", "kind", "row_stride_bytes")
+
+    def close(self) -> None:
+        if self.handle:
+            h, self.handle = self.handle, 0
+            try:
+                load_isq().sq_isq_destroy(h)
+            except Exception:
+                pass
+
+    def __init__(self, centroids: np.ndarray, kind: int = SQ_ISQ_SQ8, vmin: Optional[np.ndarray] = None,
+                 step: Optional[np.ndarray] = None, id_base: int = 0, metric: int = SQ_METRIC_L2):
+        super().__init__()
+        c = _host(centroids, np.float32)
+        if c.ndim != 2:
+            raise ValueError("centroids must be float32[nlist, d]")
+        self.nlist, self.d, self.id_base, self.n, self.kind = int(c.shape[0]), int(c.shape[1]), int(id_base), 0, int(kind)
+        par = [None if p is None else _host(p, np.float32) for p in (vmin, step)]
+        if any(p is not None and p.shape != (self.d,) for p in par):
+            raise ValueError("vmin and step must be float32[d]")
+        h = ctypes.c_int64(0)
+        _check(load_isq().sq_isq_create(_ptr(c), self.nlist, self.d, self.kind, *(None if p is None else _ptr(p) for p in par),
+                                        int(metric), self.id_base, ctypes.byref(h)), "sq_isq_create")
+        self.handle = int(h.value)
+
+    def __enter__(self) -> "IsqIndex":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+    def add(self, rows, n: Optional[int] = None, device_ptr: bool = False) -> None:
+        """Rows (``[r, d]`` float32 host array, or a device pointer + ``n``) are coded into their lists; they get the
+        next insertion numbers (``sq_isq_add``).  The rows themselves are not kept."""
+        if device_ptr:
+            assert n is not None
+            ptr, mem, r = _ptr(rows), SQ_MEM_DEVICE, int(n)
+        else:
+            rows = _host(rows, np.float32)
+            if rows.ndim != 2 or rows.shape[1] != self.d:
+                raise ValueError("rows must be float32[r, d]")
+            ptr, mem, r = _ptr(rows), SQ_MEM_HOST, int(rows.shape[0])
+        if r == 0:
+            return
+        _check(load_isq().sq_isq_add(self.handle, ptr, r, mem), "sq_isq_add")
+        self.n += r
+
+    def search(self, queries: np.ndarray, k: int, nprobe: int = 1) -> Tuple[np.ndarray, np.ndarray]:
+        """(decoded dist float32 ``[nq, k]``, ids int64 ``[nq, k]``) of the ``k`` nearest rows among the lists of the
+        ``nprobe`` nearest centroids; ``-1`` / ``+inf`` behind the last candidate."""
+        q = _host(queries, np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        if q.shape[1] != self.d:
+            raise ValueError("query dimension does not match the index")
+        nq = q.shape[0]
+        dist = np.empty((nq, k), dtype=np.float32)
+        idx = np.empty((nq, k), dtype=np.int64)
+        _check(load_isq().sq_isq_search(self.handle, _ptr(q), nq, int(k), int(nprobe), _ptr(dist), _ptr(idx), SQ_MEM_HOST, None),
+               "sq_isq_search")
+        return dist, idx
+
+    def search_device(self, q_ptr: int, nq: int, k: int, nprobe: int, out_dist_ptr: int, out_idx_ptr: int, stream: int = 0) -> None:
+        """Device pointers throughout; blocking, as :meth:`search`."""
+        _check(load_isq().sq_isq_search(self.handle, _ptr(q_ptr), int(nq), int(k), int(nprobe), _ptr(out_dist_ptr), _ptr(out_idx_ptr),
+                                        SQ_MEM_DEVICE, ctypes.c_void_p(stream or None)), "sq_isq_search")
+
+    def lists(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(``list_off[nlist + 1]``, ids of all rows, their codes ``[rows, d]`` -- uint8, or for ``SQ_ISQ_F16`` the
+        halves' bits as uint16), list by list -- ``sq_isq_lists``."""
+        off = np.empty(self.nlist + 1, dtype=np.int64)
+        ids = np.empty(self.n, dtype=np.int64)
+        codes = np.empty((self.n, self.d), dtype=np.uint16 if self.kind == SQ_ISQ_F16 else np.uint8)
+        _check(load_isq().sq_isq_lists(self.handle, _ptr(off), _ptr(ids) if self.n else None, _ptr(codes) if self.n else None), "sq_isq_lists")
+        return off, ids, codes
+
+    def info(self) -> dict:
+        out = (ctypes.c_int64 * SQ_ISQ_INFO_FIELDS)()
+        _check(load_isq().sq_isq_info(self.handle, out, SQ_ISQ_INFO_FIELDS), "sq_isq_info")
         return dict(zip(self.INFO_FIELDS, (int(v) for v in out)))
 
 
