@@ -65,8 +65,8 @@ extern "C" {
  * than the two blocking ones, and a d whose staging -- 3 round_up(d, 4) * 4 bytes (SQ8), round_up(d, 4) * 4 bytes (F16) --
  * exceeds a workgroup's 160 KiB of LDS (d beyond 13652, or 40960): SQ_ERR_UNSUPPORTED.
  * Left out on purpose: residual coding, other bit widths (4, 6, bfloat16), cosine and inner product, asynchronous calls,
- * removal in place, a layout interleaved across rows for fully coalesced wave loads, a device refine stage that would use
- * this store behind IVF-PQ. */
+ * removal in place, a layout interleaved across rows for fully coalesced wave loads.  (The device refine stage that uses
+ * these codecs behind IVF-PQ is smqtk_hip_refine.h.) */
 #define SQ_ISQ_SQ8 0
 #define SQ_ISQ_F16 1
 #define SQ_ISQ_INFO_FIELDS 12

@@ -135,8 +135,8 @@ extern "C" {
  * adds against one; an empty index; and against a one-byte index over the same centroids, codebooks and rows, whose bits
  * a packed index gives.
  * Left out on purpose: OPQ rotations, FAISS's precomputed-table decomposition of the residual distance, code sizes other
- * than one byte and four bits, m beyond 64, a refine stage over kept float32 rows, cosine, asynchronous calls, removal in
- * place, retraining. */
+ * than one byte and four bits, m beyond 64, cosine, asynchronous calls, removal in place, retraining.  (The refine stage
+ * over a second store of the rows is smqtk_hip_refine.h.) */
 #define SQ_PQ_INFO_FIELDS 10
 int sq_pq_train(const float* x, int64_t n, int d, int m, int ksub,
                 float* codebooks /* [m][ksub][d/m]; in: initial, out: trained */, int iters, int mem);

@@ -78,6 +78,13 @@ ISQ_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), ISQ_LIB_NAME)
 ISQ_EXPORTS = ("sq_isq_train", "sq_isq_create", "sq_isq_add", "sq_isq_lists", "sq_isq_info", "sq_isq_search", "sq_isq_destroy")
 SQ_ISQ_SQ8, SQ_ISQ_F16 = 0, 1   # kinds of an IVF-SQ index: one byte per dimension with trained ranges, or float16
 SQ_ISQ_INFO_FIELDS = 12     # words of sq_isq_info (smqtk_hip_isq.h)
+# the refine stage: built on all four
+REFINE_LIB_NAME = "libsmqtk_hip_refine.so"
+REFINE_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), REFINE_LIB_NAME)
+REFINE_EXPORTS = ("sq_refine_create", "sq_refine_add", "sq_refine_rows", "sq_refine_info", "sq_refine_rerank", "sq_refine_search",
+                  "sq_refine_destroy")
+SQ_REFINE_SQ8, SQ_REFINE_F16, SQ_REFINE_F32 = 0, 1, 2   # kinds of a refine store: the IVF-SQ codes, or the float32 row itself
+SQ_REFINE_INFO_FIELDS = 7   # words of sq_refine_info (smqtk_hip_refine.h)
 
 
 class HipError(RuntimeError):
@@ -290,6 +297,37 @@ def load_isq() -> ctypes.CDLL:
         return _isq_lib
 
 
+_refine_lib: Optional[ctypes.CDLL] = None
+
+
+def load_refine() -> ctypes.CDLL:
+    """Load the refine-stage extension library (once), after the four libraries it is built on.  Raises HipError when it
+    is missing: there is no fallback."""
+    global _refine_lib
+    load_pq()
+    load_isq()
+    with _lock:
+        if _refine_lib is None:
+            if not os.path.isfile(REFINE_LIB_PATH):
+                raise HipError(f"{REFINE_LIB_NAME} not found at {REFINE_LIB_PATH}; build it with `make -C smqtk_indexing_amd/csrc`")
+            try:
+                lib = ctypes.CDLL(REFINE_LIB_PATH)
+            except OSError as ex:
+                raise HipError(f"cannot load {REFINE_LIB_PATH}: {ex}") from ex
+            c_int, c_i64, c_vp = ctypes.c_int, ctypes.c_int64, ctypes.c_void_p
+            lib.sq_refine_create.argtypes = [c_int, c_int, c_vp, c_vp, c_i64, ctypes.POINTER(c_i64)]
+            lib.sq_refine_add.argtypes = [c_i64, c_vp, c_i64, c_int]
+            lib.sq_refine_rows.argtypes = [c_i64, c_i64, c_i64, c_vp]
+            lib.sq_refine_info.argtypes = [c_i64, ctypes.POINTER(c_i64), c_int]
+            lib.sq_refine_rerank.argtypes = [c_i64, c_vp, c_int, c_vp, c_int, c_int, c_vp, c_vp, c_int, c_vp]
+            lib.sq_refine_search.argtypes = [c_i64, c_i64, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_int, c_vp]
+            lib.sq_refine_destroy.argtypes = [c_i64]
+            for name in REFINE_EXPORTS:
+                getattr(lib, name).restype = c_int
+            _refine_lib = lib
+        return _refine_lib
+
+
 def _check(rc: int, what: str) -> None:
     if rc != SQ_OK:
         msg = load().sq_last_error()
@@ -330,6 +368,11 @@ def pq_usable() -> bool:
 def isq_usable() -> bool:
     """A GPU, the main library, the IVF-Flat extension and the IVF-SQ extension beside them."""
     return ivf_usable() and os.path.isfile(ISQ_LIB_PATH)
+
+
+def refine_usable() -> bool:
+    """A GPU, the main library, the three list-index extensions and the refine-stage extension beside them."""
+    return pq_usable() and isq_usable() and os.path.isfile(REFINE_LIB_PATH)
 
 
 def device_name(device: int = 0) -> Tuple[str, int, int]:
@@ -1016,6 +1059,117 @@ class IsqIndex(_Handle):
         out = (ctypes.c_int64 * SQ_ISQ_INFO_FIELDS)()
         _check(load_isq().sq_isq_info(self.handle, out, SQ_ISQ_INFO_FIELDS), "sq_isq_info")
         return dict(zip(self.INFO_FIELDS, (int(v) for v in out)))
+
+
+class RefineStore(_Handle):
+    """All rows of an inverted-list index once more, in id order and in a wider code (``sq_refine_*``): one byte per
+    dimension (``kind=SQ_REFINE_SQ8``, with ``vmin`` / ``step`` from :func:`isq_train`), float16 (``SQ_REFINE_F16``) or the
+    float32 row (``SQ_REFINE_F32``).  :meth:`rerank` ranks given candidate ids by the decoded distance, :meth:`search` lets
+    a base index (:class:`IvfIndex`, :class:`PqIndex`, :class:`IsqIndex`) choose them on the device first.  L2 only.  Use
+    as a context manager or ``close()`` it."""
+    _destroy_name = "sq_refine_destroy"
+    INFO_FIELDS = ("rows", "d", "kind", "row_stride_bytes", "codes_bytes", "params_bytes", "add_us")
+    CODE_DTYPES = {SQ_REFINE_SQ8: np.uint8, SQ_REFINE_F16: np.uint16, SQ_REFINE_F32: np.float32}
+
+    def close(self) -> None:
+        if self.handle:
+            h, self.handle = self.handle, 0
+            try:
+                load_refine().sq_refine_destroy(h)
+            except Exception:
+                pass
+
+    def __init__(self, d: int, kind: int = SQ_REFINE_F16, vmin: Optional[np.ndarray] = None, step: Optional[np.ndarray] = None,
+                 id_base: int = 0):
+        super().__init__()
+        self.d, self.id_base, self.n, self.kind = int(d), int(id_base), 0, int(kind)
+        par = [None if p is None else _host(p, np.float32) for p in (vmin, step)]
+        if any(p is not None and p.shape != (self.d,) for p in par):
+            raise ValueError("vmin and step must be float32[d]")
+        h = ctypes.c_int64(0)
+        _check(load_refine().sq_refine_create(self.d, self.kind, *(None if p is None else _ptr(p) for p in par), self.id_base,
+                                              ctypes.byref(h)), "sq_refine_create")
+        self.handle = int(h.value)
+
+    def __enter__(self) -> "RefineStore":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+    def add(self, rows, n: Optional[int] = None, device_ptr: bool = False) -> None:
+        """Rows (``[r, d]`` float32 host array, or a device pointer + ``n``) are coded behind the rows already there
+        (``sq_refine_add``); they get the next insertion numbers."""
+        if device_ptr:
+            assert n is not None
+            ptr, mem, r = _ptr(rows), SQ_MEM_DEVICE, int(n)
+        else:
+            rows = _host(rows, np.float32)
+            if rows.ndim != 2 or rows.shape[1] != self.d:
+                raise ValueError("rows must be float32[r, d]")
+            ptr, mem, r = _ptr(rows), SQ_MEM_HOST, int(rows.shape[0])
+        if r == 0:
+            return
+        _check(load_refine().sq_refine_add(self.handle, ptr, r, mem), "sq_refine_add")
+        self.n += r
+
+    def rows(self, first: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """The codes of rows ``[first, first + n)`` (``[n, d]`` of uint8, the halves' bits as uint16, or float32) --
+        ``sq_refine_rows``."""
+        n = self.n - first if n is None else int(n)
+        codes = np.empty((n, self.d), dtype=self.CODE_DTYPES[self.kind])
+        _check(load_refine().sq_refine_rows(self.handle, int(first), n, _ptr(codes) if n else None), "sq_refine_rows")
+        return codes
+
+    def info(self) -> dict:
+        out = (ctypes.c_int64 * SQ_REFINE_INFO_FIELDS)()
+        _check(load_refine().sq_refine_info(self.handle, out, SQ_REFINE_INFO_FIELDS), "sq_refine_info")
+        return dict(zip(self.INFO_FIELDS, (int(v) for v in out)))
+
+    def _queries(self, queries: np.ndarray) -> np.ndarray:
+        q = _host(queries, np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        if q.shape[1] != self.d:
+            raise ValueError("query dimension does not match the store")
+        return q
+
+    def rerank(self, queries: np.ndarray, cand: np.ndarray, k: int) -> Tuple[np.ndarray, np.ndarray]:
+        """(decoded dist float32 ``[nq, k]``, ids int64 ``[nq, k]``) of the ``k`` nearest among each query's candidate
+        ids ``cand[nq, kb]``; ids outside the store are skipped, ``-1`` / ``+inf`` behind the last candidate."""
+        q = self._queries(queries)
+        cand = _host(cand, np.int64)
+        nq = q.shape[0]
+        if cand.ndim != 2 or cand.shape[0] != nq:
+            raise ValueError("cand must be int64[nq, kb]")
+        dist = np.empty((nq, k), dtype=np.float32)
+        idx = np.empty((nq, k), dtype=np.int64)
+        _check(load_refine().sq_refine_rerank(self.handle, _ptr(q), nq, _ptr(cand), int(cand.shape[1]), int(k), _ptr(dist), _ptr(idx),
+                                              SQ_MEM_HOST, None), "sq_refine_rerank")
+        return dist, idx
+
+    def rerank_device(self, q_ptr: int, nq: int, cand_ptr: int, kb: int, k: int, out_dist_ptr: int, out_idx_ptr: int, stream: int = 0) -> None:
+        """Device pointers throughout; blocking, as :meth:`rerank`."""
+        _check(load_refine().sq_refine_rerank(self.handle, _ptr(q_ptr), int(nq), _ptr(cand_ptr), int(kb), int(k), _ptr(out_dist_ptr),
+                                              _ptr(out_idx_ptr), SQ_MEM_DEVICE, ctypes.c_void_p(stream or None)), "sq_refine_rerank")
+
+    def search(self, base: _Handle, queries: np.ndarray, k: int, kb: int, nprobe: int = 1) -> Tuple[np.ndarray, np.ndarray]:
+        """``base`` answers ``kb`` candidates per query at ``nprobe`` on the device, the store re-ranks them: (decoded
+        dist float32 ``[nq, k]``, ids int64 ``[nq, k]``)."""
+        q = self._queries(queries)
+        nq = q.shape[0]
+        dist = np.empty((nq, k), dtype=np.float32)
+        idx = np.empty((nq, k), dtype=np.int64)
+        _check(load_refine().sq_refine_search(self.handle, base.handle, _ptr(q), nq, int(k), int(kb), int(nprobe), _ptr(dist), _ptr(idx),
+                                              SQ_MEM_HOST, None), "sq_refine_search")
+        return dist, idx
+
+    def search_device(self, base: _Handle, q_ptr: int, nq: int, k: int, kb: int, nprobe: int, out_dist_ptr: int, out_idx_ptr: int,
+                      stream: int = 0) -> None:
+        """Device pointers throughout; blocking, as :meth:`search`."""
+        _check(load_refine().sq_refine_search(self.handle, base.handle, _ptr(q_ptr), int(nq), int(k), int(kb), int(nprobe),
+                                              _ptr(out_dist_ptr), _ptr(out_idx_ptr), SQ_MEM_DEVICE, ctypes.c_void_p(stream or None)),
+               "sq_refine_search")
 
 
 def dense_distances(query: np.ndarray, rows: np.ndarray, metric: int = SQ_METRIC_L2) -> np.ndarray:

@@ -64,6 +64,7 @@ struct Options {
     int hamming_ring = -1;       // Hamming stream kernel: -1 = automatic (LDS-DMA ring for arrays beyond the MALL), 0 = register loads, 1 = ring (1 .. 7, 8, 16 words, 16-byte aligned arrays; the register kernel otherwise)
     int hamming_tighten = 1;     // fused Hamming searches: stream threshold from a lower sample rank than k (far fewer candidates); a bet the pick kernel checks -- a lost one redoes the call with the safe rule; 0 = the safe rank-k rule
     int ivf_key_budget_mb = 0;   // IVF search: MB of key scratch a call may hold -- a batch runs in query slices under it (0 = 256; sq_ivf_plan.hpp)
+    int refine_direct = -1;      // refine store (sq_refine.hip): 1 = the re-rank reads its candidates' code rows straight from global memory, 0 = it gathers a tile of them into LDS first, -1 = automatic: by what profiles/ivf_refine.txt measured on gathers that miss the caches, the LDS gather for float16 and float32 stores (0.85 - 0.96 x the direct variant's time) and direct loads for 8-bit stores (the gather: 1.01 - 1.11 x); the bits are the same
     int hamming_fused = 1;       // Hamming searches of up to 32 queries (64 .. 448-bit codes, k <= 2048) as three launches (head: sampled histogram + thresholds by the last workgroup; stream; pick: exact k-th distance + gather + sort per query) instead of a memset and five; 0 = the general chain
 };
 extern Options g_opt;   // process-wide defaults (sq_set_option); a handle may override any of them (sq_handle_set_option)
@@ -100,7 +101,7 @@ inline hipError_t event_wait(hipEvent_t ev) {
 namespace sq {
 
 // ------------------------------------------------------------------ handles
-enum HandleKind { H_HAMMING = 1, H_DENSE = 2, H_ROWS = 3, H_FIT = 4, H_ITQ = 5, H_IVF = 6, H_PQ = 7, H_ISQ = 8 };
+enum HandleKind { H_HAMMING = 1, H_DENSE = 2, H_ROWS = 3, H_FIT = 4, H_ITQ = 5, H_IVF = 6, H_PQ = 7, H_ISQ = 8, H_REFINE = 9 };
 
 struct HandleBase {
     int kind = 0;
@@ -118,6 +119,9 @@ struct HandleBase {
         opt = g_opt;
         for (const auto& o : overrides) opt.*(o.first) = o.second;
     }
+    // an inverted-list index (IVF-Flat, IVF-PQ, IVF-SQ) reports what a refine store behind it must match: row width,
+    // rows and id_base (sq_refine_search); every other kind: false
+    virtual bool list_shape(int*, long long*, long long*) const { return false; }
     virtual ~HandleBase() {
         for (auto& e : ev)
             if (e) (void)hipEventDestroy(e);

@@ -6,28 +6,25 @@
 // metrics.euclidean_distance over the decoded row in numpy's order -- so a search returns the bits sq_ivf_search returns
 // over the decoded matrix.  The coarse index, the counting sort, the probed lists' prefix and the select's post-op are
 // sq_ivf_group.hpp's, the host arithmetic sq_ivf_plan.hpp's, the tree walk sq_pairwise.hpp's.  New device code: the column
-// ranges (training), the encoder, the scatter of code rows, and the decoding scan.
+// ranges (training), the scatter of code rows, and the decoding scan; the codecs and the encoder are sq_isq_codec.hpp's.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <vector>
 
 #include "../../include/smqtk_hip_isq.h"
+#include "sq_isq_codec.hpp"
 #include "sq_ivf_group.hpp"
 
 namespace sq {
 
-typedef unsigned char u8;
-typedef unsigned short u16;
 typedef u32 u32x2 __attribute__((ext_vector_type(2)));
 typedef u32 u32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 static constexpr int kIsqStageMax = 160 * 1024;   // dynamic LDS a scan workgroup may ask for
 
-// bytes of one code, of a stored row (whole 16-byte pieces, zero padded) and of the scan's LDS staging
-inline int isq_code_bytes(int kind) { return kind == SQ_ISQ_F16 ? 2 : 1; }
-inline long long isq_row_stride(int d, int kind) { return ((long long)d * isq_code_bytes(kind) + 15) / 16 * 16; }
+// bytes of the scan's LDS staging (a code's and a stored row's bytes: sq_isq_codec.hpp)
 inline long long isq_stage_bytes(int d, int kind) { return (kind == SQ_ISQ_SQ8 ? 3 : 1) * ivf_row_stride(d) * 4; }
 
 struct IsqHandle : HandleBase {
@@ -41,21 +38,16 @@ struct IsqHandle : HandleBase {
     DevBuf q_dev, probe_dist, probe_idx, pre, cnt, keys, out_keys, out_dist, out_idx, sort_tmp;
     HostPinned totals_host;
     PinnedStage stage;
+    bool list_shape(int* d_out, long long* n_out, long long* id_base_out) const override {
+        *d_out = d;
+        *n_out = n;
+        *id_base_out = id_base;
+        return true;
+    }
     ~IsqHandle() override {
         if (coarse) (void)sq_dense_destroy(coarse);
     }
 };
-
-// ------------------------------------------------------------------ the two codecs
-__device__ __forceinline__ u32 isq_encode_sq8(float x, float vmin, float step) {
-    const float t = __fdiv_rn(__fsub_rn(x, vmin), step);
-    return (step != 0.f && t > 0.f) ? (u32)fminf(rintf(t), 255.f) : 0u;   // NaN compares false: code 0
-}
-__device__ __forceinline__ float isq_decode_sq8(float code, float vmin, float step) { return __fadd_rn(vmin, __fmul_rn(step, code)); }
-__device__ __forceinline__ u32 isq_encode_f16(float x) {
-    const _Float16 h = (_Float16)x;   // v_cvt_f16_f32: nearest even, subnormal halves kept, overflow to inf
-    return (u32)__builtin_bit_cast(u16, h);
-}
 
 // ------------------------------------------------------------------ training: the column ranges
 // numpy's min / max: a NaN in the column makes the result NaN
@@ -98,32 +90,6 @@ static __global__ __launch_bounds__(256) void isq_range_final_kernel(const float
     }
     vmin[col] = mn;
     step[col] = __fdiv_rn(__fsub_rn(mx, mn), 255.f);
-}
-
-// ------------------------------------------------------------------ the encoder
-// Float32 rows (stride d, any alignment) -> padded code rows in the order of the add.  A lane writes one dword of a
-// code row -- four 8-bit codes or two halves -- so a wave's stores are contiguous; the padding behind d is zero.
-template <int KIND>
-static __global__ __launch_bounds__(256) void isq_encode_kernel(const float* __restrict__ src, int d, long long n,
-                                                                 const float* __restrict__ vmin, const float* __restrict__ step,
-                                                                 long long wpr /* dwords per code row */, u32* __restrict__ out) {
-    constexpr int PER = KIND == SQ_ISQ_SQ8 ? 4 : 2;
-    const long long total = n * wpr;
-    for (long long idx = (long long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long long)gridDim.x * 256) {
-        const long long r = idx / wpr;
-        const int i0 = (int)(idx - r * wpr) * PER;
-        u32 word = 0;
-#pragma unroll
-        for (int j = 0; j < PER; ++j) {
-            const int i = i0 + j;
-            if (i < d) {
-                const float v = src[r * d + i];
-                if constexpr (KIND == SQ_ISQ_SQ8) word |= isq_encode_sq8(v, vmin[i], step[i]) << (8 * j);
-                else word |= isq_encode_f16(v) << (16 * j);
-            }
-        }
-        out[idx] = word;
-    }
 }
 
 // ------------------------------------------------------------------ the counting sort's scatter, in 16-byte pieces

@@ -22,6 +22,12 @@ namespace sq {
 struct IvfHandle : HandleBase {
     int d = 0, nlist = 0;
     long long ld = 0, n = 0, id_base = 0;
+    bool list_shape(int* d_out, long long* n_out, long long* id_base_out) const override {
+        *d_out = d;
+        *n_out = n;
+        *id_base_out = id_base;
+        return true;
+    }
     sq_handle_t coarse = 0;              // dense index over the centroids: assignment and probing
     DevBuf rows, ids, list_off;          // [n][ld] float32 list-major, [n] insertion numbers, [nlist + 1]
     std::vector<long long> off_host;     // list_off on the host

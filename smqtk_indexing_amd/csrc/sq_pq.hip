@@ -34,6 +34,12 @@ struct PqHandle : HandleBase {
     int d = 0, nlist = 0, m = 0, ksub = 0, dsub = 0;
     long long cs = 0, es = 0;            // bytes of a coded row; floats of a codebook entry in `books`
     long long n = 0, id_base = 0;
+    bool list_shape(int* d_out, long long* n_out, long long* id_base_out) const override {
+        *d_out = d;
+        *n_out = n;
+        *id_base_out = id_base;
+        return true;
+    }
     sq_handle_t coarse = 0;              // dense index over the centroids: assignment and probing
     std::vector<sq_handle_t> sub;        // dense index over codebook j: the code of a sub-vector
     DevBuf books;                        // [m][ksub][es] float32, zero padded: what the tables kernel reads
