@@ -85,6 +85,12 @@ REFINE_EXPORTS = ("sq_refine_create", "sq_refine_add", "sq_refine_rows", "sq_ref
                   "sq_refine_destroy")
 SQ_REFINE_SQ8, SQ_REFINE_F16, SQ_REFINE_F32 = 0, 1, 2   # kinds of a refine store: the IVF-SQ codes, or the float32 row itself
 SQ_REFINE_INFO_FIELDS = 7   # words of sq_refine_info (smqtk_hip_refine.h)
+# the OPQ transform: built on the main library alone
+OPQ_LIB_NAME = "libsmqtk_hip_opq.so"
+OPQ_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), OPQ_LIB_NAME)
+OPQ_EXPORTS = ("sq_opq_create", "sq_opq_apply", "sq_opq_info", "sq_opq_destroy")
+SQ_OPQ_MAX_D = 4096         # widest row of an OPQ transform (smqtk_hip_opq.h)
+SQ_OPQ_INFO_FIELDS = 4      # words of sq_opq_info
 
 
 class HipError(RuntimeError):
@@ -328,6 +334,33 @@ def load_refine() -> ctypes.CDLL:
         return _refine_lib
 
 
+_opq_lib: Optional[ctypes.CDLL] = None
+
+
+def load_opq() -> ctypes.CDLL:
+    """Load the OPQ-transform extension library (once), after the main library it is built on.  Raises HipError when it is
+    missing: there is no fallback."""
+    global _opq_lib
+    load()
+    with _lock:
+        if _opq_lib is None:
+            if not os.path.isfile(OPQ_LIB_PATH):
+                raise HipError(f"{OPQ_LIB_NAME} not found at {OPQ_LIB_PATH}; build it with `make -C smqtk_indexing_amd/csrc`")
+            try:
+                lib = ctypes.CDLL(OPQ_LIB_PATH)
+            except OSError as ex:
+                raise HipError(f"cannot load {OPQ_LIB_PATH}: {ex}") from ex
+            c_int, c_i64, c_vp = ctypes.c_int, ctypes.c_int64, ctypes.c_void_p
+            lib.sq_opq_create.argtypes = [c_vp, c_int, ctypes.POINTER(c_i64)]
+            lib.sq_opq_apply.argtypes = [c_i64, c_vp, c_i64, c_vp, c_int, c_vp]
+            lib.sq_opq_info.argtypes = [c_i64, ctypes.POINTER(c_i64), c_int]
+            lib.sq_opq_destroy.argtypes = [c_i64]
+            for name in OPQ_EXPORTS:
+                getattr(lib, name).restype = c_int
+            _opq_lib = lib
+        return _opq_lib
+
+
 def _check(rc: int, what: str) -> None:
     if rc != SQ_OK:
         msg = load().sq_last_error()
@@ -373,6 +406,11 @@ def isq_usable() -> bool:
 def refine_usable() -> bool:
     """A GPU, the main library, the three list-index extensions and the refine-stage extension beside them."""
     return pq_usable() and isq_usable() and os.path.isfile(REFINE_LIB_PATH)
+
+
+def opq_usable() -> bool:
+    """A GPU, the main library, the IVF-Flat and IVF-PQ extensions and the OPQ-transform extension beside them."""
+    return pq_usable() and os.path.isfile(OPQ_LIB_PATH)
 
 
 def device_name(device: int = 0) -> Tuple[str, int, int]:
@@ -1170,6 +1208,57 @@ class RefineStore(_Handle):
         _check(load_refine().sq_refine_search(self.handle, base.handle, _ptr(q_ptr), int(nq), int(k), int(kb), int(nprobe),
                                               _ptr(out_dist_ptr), _ptr(out_idx_ptr), SQ_MEM_DEVICE, ctypes.c_void_p(stream or None)),
                "sq_refine_search")
+
+
+class OpqTransform(_Handle):
+    """A ``d x d`` float32 matrix resident on the device (``sq_opq_*``): :meth:`apply` returns ``x @ A.T`` in float32,
+    within ``gamma_d * |x| @ |A|.T`` of the float64 product (include/smqtk_hip_opq.h) -- not bit for bit.  Use as a context
+    manager or ``close()`` it."""
+    _destroy_name = "sq_opq_destroy"
+    INFO_FIELDS = ("d", "resident_bytes", "last_rows", "last_us")
+
+    def close(self) -> None:
+        if self.handle:
+            h, self.handle = self.handle, 0
+            try:
+                load_opq().sq_opq_destroy(h)
+            except Exception:
+                pass
+
+    def __init__(self, matrix: np.ndarray):
+        super().__init__()
+        a = _host(matrix, np.float32)
+        if a.ndim != 2 or a.shape[0] != a.shape[1]:
+            raise ValueError("matrix must be float32[d, d]")
+        self.d = int(a.shape[0])
+        h = ctypes.c_int64(0)
+        _check(load_opq().sq_opq_create(_ptr(a), self.d, ctypes.byref(h)), "sq_opq_create")
+        self.handle = int(h.value)
+
+    def __enter__(self) -> "OpqTransform":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+    def apply(self, x: np.ndarray) -> np.ndarray:
+        """``[n, d]`` float32 host rows -> ``x @ A.T`` (a new host array; blocking)."""
+        x = _host(x, np.float32)
+        if x.ndim != 2 or x.shape[1] != self.d:
+            raise ValueError("x must be float32[n, d]")
+        y = np.empty_like(x)
+        _check(load_opq().sq_opq_apply(self.handle, _ptr(x), int(x.shape[0]), _ptr(y), SQ_MEM_HOST, None), "sq_opq_apply")
+        return y
+
+    def apply_device(self, x_ptr: int, n: int, y_ptr: int, stream: int = 0) -> None:
+        """Device pointers; enqueued on ``stream``, final when the stream is."""
+        _check(load_opq().sq_opq_apply(self.handle, _ptr(x_ptr), int(n), _ptr(y_ptr), SQ_MEM_DEVICE, ctypes.c_void_p(stream or None)),
+               "sq_opq_apply")
+
+    def info(self) -> dict:
+        out = (ctypes.c_int64 * SQ_OPQ_INFO_FIELDS)()
+        _check(load_opq().sq_opq_info(self.handle, out, SQ_OPQ_INFO_FIELDS), "sq_opq_info")
+        return dict(zip(self.INFO_FIELDS, (int(v) for v in out)))
 
 
 def dense_distances(query: np.ndarray, rows: np.ndarray, metric: int = SQ_METRIC_L2) -> np.ndarray:
