@@ -44,7 +44,8 @@ extern "C" {
  *                  device (min and max do not depend on the order).  x, vmin and step all in `mem` (host or device).
  *   sq_isq_create  an empty index over `centroids` ([nlist][d]) -- and `vmin`, `step` ([d] each) for SQ_ISQ_SQ8, which must be
  *                  NULL for SQ_ISQ_F16 -- all in host memory; metric must be SQ_METRIC_L2.
- *   sq_isq_add     assigns the new rows (host or device memory; any alignment), codes them (isq_encode_kernel) and
+ *   sq_isq_add     assigns the new rows (host or device memory; any alignment) as sq_ivf_add does (option "ivf_assign"; after an
+ *                  add sq_get_stats holds scan_launches, candidates, fallback_queries and, with option "profile", scan_ms), codes them (isq_encode_kernel) and
  *                  scatters old and new code rows into a new buffer by IVF-Flat's stable counting sort, 16 bytes at a time,
  *                  then swaps buffers.  Three adds leave the bytes one add of the same rows leaves.  A failed allocation
  *                  leaves the index as it was (SQ_ERR_NOMEM).

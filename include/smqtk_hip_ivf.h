@@ -32,13 +32,19 @@ extern "C" {
  * inside a list, a uint32 insertion number per row and list_off[nlist + 1]: 1.0 x the matrix + 4 bytes per row; no scan
  * copy of any kind.  Up to 2^32-1 rows (keys carry a 32-bit row number); more give SQ_ERR_UNSUPPORTED.
  *   sq_ivf_kmeans  Lloyd iterations from the caller's initial centroids (in: initial, out: trained; x and centroids both
- *                  in `mem`, host or device).  Assign: the dense search, k = 1, over a temporary index of the
- *                  iteration's centroids.  Update: the float64 sum of each list's rows in insertion order by a fixed
+ *                  in `mem`, host or device).  Assign: as sq_ivf_add, over a temporary index of the iteration's centroids
+ *                  (no handle: the process-wide option "ivf_assign").  Update: the float64 sum of each list's rows in insertion order by a fixed
  *                  reduction tree (no floating-point atomics: the same input gives the same bits), divided by the
  *                  count, rounded to float32 once; an empty list keeps its centroid.  n < nlist: SQ_ERR_INVALID; at most
  *                  2^26 training rows (train on a sample).
  *   sq_ivf_create  an empty index over `centroids` ([nlist][d], host memory); metric must be SQ_METRIC_L2.
- *   sq_ivf_add     assigns the new rows (host or device memory) in slices of 1024, and scatters old and new rows into a
+ *   sq_ivf_add     assigns the new rows (host or device memory) to their nearest centroid -- option "ivf_assign" = 1 (handle
+ *                  or process-wide): ivf_assign_kernel scores float32 rows of up to 1024 elements on the float32 matrix
+ *                  cores and decides a row only when its best-to-second gap clears a derived rounding bound; the rows it
+ *                  leaves undecided, and with "ivf_assign" = 0 or wider rows all of them, go through the dense search,
+ *                  k = 1, in slices of 1024: the assignment is that search's for every input.  sq_get_stats after an add:
+ *                  scan_launches (launches of ivf_assign_kernel), candidates (rows it decided), fallback_queries (rows the
+ *                  dense search assigned), with option "profile" scan_ms (the kernel's time).  It then scatters old and new rows into a
  *                  new buffer by a stable counting sort on the device, then swaps buffers: what add_with_ids does
  *                  (faiss.py:561-640).  Three adds leave the lists one add of the same rows leaves.  A failed allocation
  *                  leaves the index as it was (SQ_ERR_NOMEM); an add of more than 2^26 rows is several such sorts, each

@@ -41,7 +41,9 @@ extern "C" {
  *                  caller's initial entries, so the same input gives the same bits; x and codebooks both in `mem` (host
  *                  or device).  n < ksub: SQ_ERR_INVALID; at most 2^26 training rows.
  *   sq_pq_create   an empty index over `centroids` ([nlist][d]) and `codebooks` ([m][ksub][dsub]), both in host memory.
- *   sq_pq_add      assigns and codes the new rows (host or device memory) and scatters old and new codes into a new buffer
+ *   sq_pq_add      assigns and codes the new rows (host or device memory) -- the list and each of the m codes are nearest-
+ *                  centroid assignments as sq_ivf_add's (option "ivf_assign"; sq_get_stats after an add sums
+ *                  scan_launches, candidates, fallback_queries and, with option "profile", scan_ms over the m + 1 of them) -- and scatters old and new codes into a new buffer
  *                  by IVF-Flat's stable counting sort, then swaps buffers.  Three adds leave the bytes one add of the same
  *                  rows leaves.  A failed allocation leaves the index as it was (SQ_ERR_NOMEM).
  *   sq_pq_lists    list_off[nlist + 1], the ids of all rows and their codes ([rows][m], without the padding), list by

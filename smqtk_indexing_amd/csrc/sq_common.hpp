@@ -65,6 +65,7 @@ struct Options {
     int hamming_tighten = 1;     // fused Hamming searches: stream threshold from a lower sample rank than k (far fewer candidates); a bet the pick kernel checks -- a lost one redoes the call with the safe rule; 0 = the safe rank-k rule
     int ivf_key_budget_mb = 0;   // IVF search: MB of key scratch a call may hold -- a batch runs in query slices under it (0 = 256; sq_ivf_plan.hpp)
     int refine_direct = -1;      // refine store (sq_refine.hip): 1 = the re-rank reads its candidates' code rows straight from global memory, 0 = it gathers a tile of them into LDS first, -1 = automatic: by what profiles/ivf_refine.txt measured on gathers that miss the caches, the LDS gather for float16 and float32 stores (0.85 - 0.96 x the direct variant's time) and direct loads for 8-bit stores (the gather: 1.01 - 1.11 x); the bits are the same
+    int ivf_assign = 1;          // inverted-list builds (sq_ivf_assign.hpp): 1 = rows are assigned to their nearest centroid by ivf_assign_kernel (float32 MFMA scores, a certified gap) wherever ivf_assign_route covers the call, and only the rows it leaves undecided by the exact dense search; 0 = the exact dense search for every row, in slices of 1024; the assignment is the same bits
     int hamming_fused = 1;       // Hamming searches of up to 32 queries (64 .. 448-bit codes, k <= 2048) as three launches (head: sampled histogram + thresholds by the last workgroup; stream; pick: exact k-th distance + gather + sort per query) instead of a memset and five; 0 = the general chain
 };
 extern Options g_opt;   // process-wide defaults (sq_set_option); a handle may override any of them (sq_handle_set_option)
@@ -122,6 +123,9 @@ struct HandleBase {
     // an inverted-list index (IVF-Flat, IVF-PQ, IVF-SQ) reports what a refine store behind it must match: row width,
     // rows and id_base (sq_refine_search); every other kind: false
     virtual bool list_shape(int*, long long*, long long*) const { return false; }
+    // a dense L2 index with every row live reports its float32 matrix on the device: pointer, row stride in floats, rows
+    // and row width (ivf_assign reads the centroids of its coarse index here); every other handle: false
+    virtual bool dense_matrix(const float**, long long*, long long*, int*) const { return false; }
     virtual ~HandleBase() {
         for (auto& e : ev)
             if (e) (void)hipEventDestroy(e);

@@ -116,6 +116,7 @@ int Options::*option_member(const char* name) {
         {"hamming_tighten", &Options::hamming_tighten},
         {"ivf_key_budget_mb", &Options::ivf_key_budget_mb},
         {"refine_direct", &Options::refine_direct},
+        {"ivf_assign", &Options::ivf_assign},
     };
     if (!name) return nullptr;
     for (const auto& f : kFields)

@@ -141,6 +141,11 @@ struct DenseHandle : HandleBase {
     long long dead_words = 0;   // 32-bit words of `dead` in use (zero behind the rows)
     long long n_live = 0;       // rows not removed: what k is clamped to
     const u32* deadp() const { return dead.as<u32>(); }
+    bool dense_matrix(const float** p, long long* ld_out, long long* n_out, int* d_out) const override {
+        if (metric != SQ_METRIC_L2 || dead.p || !db) return false;
+        *p = db, *ld_out = ld, *n_out = n, *d_out = d;
+        return true;
+    }
     DevBuf zeros;   // cosine: the 32 zero "norms" every tile of an AGPR-configuration scan starts from (norm_step 0)
     static constexpr int kMaxDepth = 6;
     CallRing<DenseSlot, kMaxDepth> ring;   // the call slots (option dense_async_depth: 2 .. kMaxDepth in flight)

@@ -144,17 +144,19 @@ static int isq_add_part(IsqHandle* h, const float* rows, long long n_add, int me
         SQ_HIP(hipMemcpy(up.p, rows, (size_t)n_add * d * 4, hipMemcpyHostToDevice));
         src = up.as<float>();
     }
-    DevBuf assign, adist, enc;
+    DevBuf assign, enc;
     SQ_TRY(assign.reserve((size_t)n_add * 8));
-    SQ_TRY(adist.reserve((size_t)n_add * 4));
-    SQ_TRY(ivf_assign(h->coarse, src, n_add, d, assign.as<long long>(), adist.as<float>(), st));
+    IvfAssignStats as;
+    IvfAssignScratch aw;   // (ivf_group below waits for the stream)
+    as.timed = h->opt.profile != 0;
+    SQ_TRY(ivf_assign(h->coarse, src, n_add, d, assign.as<long long>(), st, h->opt.ivf_assign, aw, &as));
+    as.into(h->stats);
     SQ_TRY(ivf_alloc(enc, (size_t)n_add * h->stride));
     SQ_TRY(isq_encode(h, src, n_add, enc.as<u32>(), st));
     IvfGroup g;
     SQ_TRY(ivf_group(assign.as<long long>(), n_add, nlist, g, st));   // (waits for the stream: the float32 rows are done with)
     up.release();
     assign.release();
-    adist.release();
     g.keys.release();
     g.scratch.release();
     std::vector<long long> add_cnt((size_t)nlist), plan((size_t)3 * nlist + 1);
@@ -448,6 +450,7 @@ extern "C" int sq_isq_add(sq_handle_t hid, const float* rows, int64_t n_add, int
     if (!ivf_rows_ok(h->n + n_add)) return fail(SQ_ERR_UNSUPPORTED, "sq_isq_add: more than 2^32-1 rows");
     SQ_HIP(hipSetDevice(h->device));
     const auto t0 = std::chrono::steady_clock::now();
+    h->stats = sq_stats_t{};   // what the assignment did: launches of ivf_assign_kernel, rows it decided, rows of the exact path
     for (long long s = 0; s < n_add; s += kIvfGroupMax)
         SQ_TRY(isq_add_part(h, rows + s * h->d, std::min<long long>(kIvfGroupMax, n_add - s), mem));
     h->add_us = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();

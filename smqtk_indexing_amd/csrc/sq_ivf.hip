@@ -92,14 +92,16 @@ static int ivf_add_part(IvfHandle* h, const float* rows, long long n_add, int me
         SQ_HIP(hipMemcpy(up.p, rows, (size_t)n_add * d * 4, hipMemcpyHostToDevice));
         src = up.as<float>();
     }
-    DevBuf assign, adist;
+    DevBuf assign;
     SQ_TRY(assign.reserve((size_t)n_add * 8));
-    SQ_TRY(adist.reserve((size_t)n_add * 4));
-    SQ_TRY(ivf_assign(h->coarse, src, n_add, d, assign.as<long long>(), adist.as<float>(), st));
+    IvfAssignStats as;
+    IvfAssignScratch aw;   // (ivf_group below waits for the stream)
+    as.timed = h->opt.profile != 0;
+    SQ_TRY(ivf_assign(h->coarse, src, n_add, d, assign.as<long long>(), st, h->opt.ivf_assign, aw, &as));
+    as.into(h->stats);
     IvfGroup g;
     SQ_TRY(ivf_group(assign.as<long long>(), n_add, nlist, g, st));
     assign.release();
-    adist.release();
     g.keys.release();
     g.scratch.release();
     std::vector<long long> add_cnt((size_t)nlist), plan((size_t)3 * nlist + 1);
@@ -278,6 +280,7 @@ extern "C" int sq_ivf_add(sq_handle_t hid, const float* rows, int64_t n_add, int
     if (!ivf_rows_ok(h->n + n_add)) return fail(SQ_ERR_UNSUPPORTED, "sq_ivf_add: more than 2^32-1 rows");
     SQ_HIP(hipSetDevice(h->device));
     const auto t0 = std::chrono::steady_clock::now();
+    h->stats = sq_stats_t{};   // what the assignment did: launches of ivf_assign_kernel, rows it decided, rows of the exact path
     // (an add beyond 2^26 rows is several counting sorts; each leaves a complete index)
     for (long long s = 0; s < n_add; s += kIvfGroupMax)
         SQ_TRY(ivf_add_part(h, rows + s * h->d, std::min<long long>(kIvfGroupMax, n_add - s), mem));
@@ -376,7 +379,7 @@ extern "C" int sq_ivf_kmeans(const float* x, int64_t n, int d, float* centroids,
     std::vector<float> c_host((size_t)nlist * d);
     SQ_HIP(hipMemcpy(c_host.data(), centroids, cb, in));
     const float* x_dev = x;
-    DevBuf up, c_dev, assign, adist;
+    DevBuf up, c_dev, assign;
     if (mem != SQ_MEM_DEVICE) {
         SQ_TRY(ivf_alloc(up, (size_t)n * d * 4));
         SQ_HIP(hipMemcpy(up.p, x, (size_t)n * d * 4, hipMemcpyHostToDevice));
@@ -384,13 +387,13 @@ extern "C" int sq_ivf_kmeans(const float* x, int64_t n, int d, float* centroids,
     }
     SQ_TRY(c_dev.reserve(cb));
     SQ_TRY(assign.reserve((size_t)n * 8));
-    SQ_TRY(adist.reserve((size_t)n * 4));
     IvfGroup g;
+    IvfAssignScratch aw;   // (every iteration ends with a wait for the stream)
     for (int it = 0; it < iters; ++it) {
-        // assign: the dense search over a temporary index of this iteration's centroids
+        // assign: over a temporary coarse index of this iteration's centroids (process-wide option "ivf_assign")
         sq_handle_t coarse = 0;
         SQ_TRY(ivf_coarse_create(c_host.data(), nlist, d, SQ_MEM_HOST, &coarse));
-        const int rc = ivf_assign(coarse, x_dev, n, d, assign.as<long long>(), adist.as<float>(), st);
+        const int rc = ivf_assign(coarse, x_dev, n, d, assign.as<long long>(), st, g_opt.ivf_assign, aw);
         (void)sq_dense_destroy(coarse);
         if (rc != SQ_OK) return rc;
         // update: list-major sums after the same counting sort

@@ -8,6 +8,7 @@
 
 #include "sq_dense_exact.hpp"
 #include "sq_ivf_plan.hpp"
+#include "sq_ivf_assign.hpp"   // ivf_assign: the MFMA assignment kernel, its certificate and the exact path behind it
 
 namespace sq {
 
@@ -24,14 +25,7 @@ static int ivf_coarse_create(const float* centroids, int nlist, int d, int mem, 
     return sq_dense_create_opts(centroids, nlist, d, SQ_METRIC_L2, mem, 0, names, values, 6, out);
 }
 
-// nearest centroid of n rows (device, row stride d), kIvfAssignSlice rows per call
-static int ivf_assign(sq_handle_t coarse, const float* x, long long n, int d, long long* assign, float* dist, hipStream_t st) {
-    for (long long s = 0; s < n; s += kIvfAssignSlice) {
-        const int m = (int)std::min<long long>(kIvfAssignSlice, n - s);
-        SQ_TRY(sq_dense_search(coarse, x + s * d, m, 1, dist + s, reinterpret_cast<int64_t*>(assign + s), SQ_MEM_DEVICE, st));
-    }
-    return SQ_OK;
-}
+// (nearest centroid of n rows: ivf_assign, sq_ivf_assign.hpp)
 
 // ------------------------------------------------------------------ the counting sort
 // Rows grouped by list, insertion order inside a list: the keys (list, row) are unique, so their ascending order is

@@ -152,10 +152,12 @@ static int pq_add_part(PqHandle* h, const float* rows, long long n_add, int mem)
         SQ_HIP(hipMemcpy(up.p, rows, (size_t)n_add * d * 4, hipMemcpyHostToDevice));
         src = up.as<float>();
     }
-    DevBuf assign, adist, entry, part, fresh;
+    DevBuf assign, entry, part, fresh;
     SQ_TRY(assign.reserve((size_t)n_add * 8));
-    SQ_TRY(adist.reserve((size_t)n_add * 4));
-    SQ_TRY(ivf_assign(h->coarse, src, n_add, d, assign.as<long long>(), adist.as<float>(), st));
+    IvfAssignStats as;   // of the coarse assignment and of the m sub-quantisers' together
+    IvfAssignScratch aw;   // shared by the m + 1 assignments; the stream is waited for before it goes
+    as.timed = h->opt.profile != 0;
+    SQ_TRY(ivf_assign(h->coarse, src, n_add, d, assign.as<long long>(), st, h->opt.ivf_assign, aw, &as));
     DevBuf resid;
     if (h->residual) {   // what is coded is the row's residual against its list's centroid
         SQ_TRY(ivf_alloc(resid, (size_t)n_add * d * 4));
@@ -174,7 +176,7 @@ static int pq_add_part(PqHandle* h, const float* rows, long long n_add, int mem)
                                     hipMemcpyDeviceToDevice, st));
             xj = part.as<float>();
         }
-        SQ_TRY(ivf_assign(h->sub[(size_t)j], xj, n_add, dsub, entry.as<long long>(), adist.as<float>(), st));
+        SQ_TRY(ivf_assign(h->sub[(size_t)j], xj, n_add, dsub, entry.as<long long>(), st, h->opt.ivf_assign, aw, &as));
         if (h->packed)
             SQ_TRY(launch<pq4_pack_kernel>(dim3((unsigned)((n_add + 255) / 256)), dim3(256), 0, st, entry.as<long long>(), n_add, h->ksub, j, cs,
                                            fresh.as<unsigned char>()));
@@ -183,6 +185,7 @@ static int pq_add_part(PqHandle* h, const float* rows, long long n_add, int mem)
                                           fresh.as<unsigned char>()));
     }
     SQ_HIP(hipStreamSynchronize(st));
+    as.into(h->stats);
     up.release();
     resid.release();
     part.release();
@@ -190,7 +193,6 @@ static int pq_add_part(PqHandle* h, const float* rows, long long n_add, int mem)
     IvfGroup g;
     SQ_TRY(ivf_group(assign.as<long long>(), n_add, nlist, g, st));
     assign.release();
-    adist.release();
     g.keys.release();
     g.scratch.release();
     std::vector<long long> add_cnt((size_t)nlist), plan((size_t)3 * nlist + 1);
@@ -636,7 +638,7 @@ extern "C" int sq_pq_residuals(const float* x, int64_t n, int d, const float* ce
     } coarse;
     SQ_TRY(ivf_coarse_create(centroids, nlist, d, SQ_MEM_HOST, &coarse.h));
     hipStream_t st = nullptr;
-    DevBuf cent, up, assign, adist;
+    DevBuf cent, up, assign;
     long long cds = 0;
     SQ_TRY(pq_upload_centroids(centroids, nlist, d, cent, &cds));
     const float* src = x;
@@ -647,8 +649,8 @@ extern "C" int sq_pq_residuals(const float* x, int64_t n, int d, const float* ce
         src = dst = up.as<float>();
     }
     SQ_TRY(assign.reserve((size_t)n * 8));
-    SQ_TRY(adist.reserve((size_t)n * 4));
-    SQ_TRY(ivf_assign(coarse.h, src, n, d, assign.as<long long>(), adist.as<float>(), st));
+    IvfAssignScratch aw;   // (the wait below comes before it goes)
+    SQ_TRY(ivf_assign(coarse.h, src, n, d, assign.as<long long>(), st, g_opt.ivf_assign, aw));
     SQ_TRY(pq_residual_launch(src, n, d, cent.as<float>(), cds, assign.as<long long>(), nlist, dst, st));
     SQ_HIP(hipStreamSynchronize(st));
     if (mem == SQ_MEM_HOST) SQ_HIP(hipMemcpy(out, up.p, (size_t)n * d * 4, hipMemcpyDeviceToHost));
@@ -665,6 +667,7 @@ extern "C" int sq_pq_add(sq_handle_t hid, const float* rows, int64_t n_add, int 
     if (!ivf_rows_ok(h->n + n_add)) return fail(SQ_ERR_UNSUPPORTED, "sq_pq_add: more than 2^32-1 rows");
     SQ_HIP(hipSetDevice(h->device));
     const auto t0 = std::chrono::steady_clock::now();
+    h->stats = sq_stats_t{};   // what the assignments did: launches of ivf_assign_kernel, rows it decided, rows of the exact path
     // (an add beyond 2^26 rows is several counting sorts; each leaves a complete index)
     for (long long s = 0; s < n_add; s += kIvfGroupMax)
         SQ_TRY(pq_add_part(h, rows + s * h->d, std::min<long long>(kIvfGroupMax, n_add - s), mem));
