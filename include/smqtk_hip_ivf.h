@@ -67,6 +67,19 @@ extern "C" {
  *                  sq_get_stats: scan_launches (slices scanned), candidates (rows scanned, summed over queries),
  *                  bytes_scanned (candidates x row stride x 4), and with option "profile" scan_ms / total_ms.
  *                  An index with no rows answers with padding only.
+ *                  Option "ivf_scan" (handle or process-wide) chooses the scan of a slice: 0 = ivf_scan_kernel as above,
+ *                  which reads a probed list once per query that probes it; 1 = the list-major scan wherever it can
+ *                  run -- the slice's (query, probe rank) pairs are sorted by list on the device and cut into groups of
+ *                  up to 8 queries of one list, and ivf_scan_shared_kernel reads 256 rows of the list once per group,
+ *                  scores each against the group's queries staged in LDS and stores every key in the slot the
+ *                  per-query scan fills, so the select and every bit of the answer are the same; it takes rows of up to
+ *                  5112 floats (eight staged queries in the LDS) and slices of up to 2^24 pairs, the rest runs the
+ *                  per-query scan; -1 (default) = list-major for slices with at least as many pairs as the index has lists
+ *                  (queries of the slice x min(nprobe, nlist) >= nlist), where the sort pays.  bytes_scanned stays
+ *                  the algorithmic figure for either scan.  sq_get_stats' mid_tier_queries, which an IVF search left
+ *                  at 0, is the number of (query, list) pairs of non-empty lists the list-major scan served in the
+ *                  last search: 0 when every slice ran the per-query scan.  sq_refine_search over an IVF-Flat base
+ *                  calls this function and takes the scan by the base handle's option.
  *                  Limits, as run on an MI355X under ROCm's HIP runtime: the scan stages a query in round_up(d, 4) * 4
  *                  bytes of dynamic LDS, so a row of more than 40960 floats (160 KiB) cannot be searched; the widest row
  *                  tested is 16389 floats (65568 bytes, which a plain launch takes).  The queries of a slice are the

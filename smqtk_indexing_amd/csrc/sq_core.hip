@@ -117,6 +117,7 @@ int Options::*option_member(const char* name) {
         {"ivf_key_budget_mb", &Options::ivf_key_budget_mb},
         {"refine_direct", &Options::refine_direct},
         {"ivf_assign", &Options::ivf_assign},
+        {"ivf_scan", &Options::ivf_scan},
     };
     if (!name) return nullptr;
     for (const auto& f : kFields)

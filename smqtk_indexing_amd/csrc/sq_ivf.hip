@@ -19,6 +19,8 @@
 
 namespace sq {
 
+static_assert(kIvfSharedDepth == EXACT_GROUP_DEPTH && kIvfSharedGroup == EXACT_GROUP, "the list-major scan walks rows as dense_exact_group_kernel does");
+
 struct IvfHandle : HandleBase {
     int d = 0, nlist = 0;
     long long ld = 0, n = 0, id_base = 0;
@@ -34,7 +36,8 @@ struct IvfHandle : HandleBase {
     long long add_us = 0;
     // scratch of a search
     DevBuf q_dev, probe_dist, probe_idx, pre, cnt, keys, out_keys, out_dist, out_idx, sort_tmp;
-    HostPinned totals_host;              // [candidates in total, longest candidate list]
+    HostPinned totals_host;              // [candidates in total, longest candidate list, pairs the list-major scan served]
+    IvfPairGroups pairs;                 // the list-major scan's groups of a slice
     PinnedStage stage;
     ~IvfHandle() override {
         if (coarse) (void)sq_dense_destroy(coarse);
@@ -164,6 +167,57 @@ static __global__ __launch_bounds__(256) void ivf_scan_kernel(const float* __res
     const float dist = sqrt_rn_f32(w.sum(d));
     keys[(long long)ql * key_stride + p] = ((u64)ordered_f32(dist) << 32) | (u64)ids[s];
 }
+// (3b) The list-major scan (option "ivf_scan").  Work item blockIdx.x: one group of ivf_pair_group -- one list and up to
+// G of the slice's queries that probe it -- x one chunk of 256 rows of that list, found in the groups' prefix of chunks
+// with the walk the per-query scan makes (ivf_locate).  The group's queries are staged in LDS as G x round_up(d, 4) floats
+// (an unused slot repeats the first and stores nothing).  A lane owns one row: it holds a leaf of it in registers,
+// scores it against the G queries (SqLeafGroup, pw_tree_multi, sqrt_rn_f32: the per-query scan's arithmetic), reads its
+// id once and stores G keys -- the key of row r of the list of pair (q, j) at keys[ql * key_stride + pre[q][j] + r], the
+// slot the per-query scan fills.  So a list is read once per group, nothing downstream changes, and there are no
+// atomics.  Blocks beyond the device-side count of work items return at once.  Dynamic LDS: G * round_up(d, 4) floats.
+template <int G>
+static __global__ __launch_bounds__(256) void ivf_scan_shared_kernel(const float* __restrict__ rows, long long ld, int d,
+                                                                      const u32* __restrict__ ids, const long long* __restrict__ list_off,
+                                                                      const float* __restrict__ queries, int q0,
+                                                                      const long long* __restrict__ pre, int np,
+                                                                      const u64* __restrict__ sorted, const uint2* __restrict__ groups,
+                                                                      const long long* __restrict__ item, const long long* __restrict__ counts,
+                                                                      long long key_stride, u64* __restrict__ keys) {
+    extern __shared__ __attribute__((aligned(16))) float s_qg[];
+    __shared__ long long s_key[G];   // where a slot's keys of this list start
+    __shared__ int s_query[G];
+    const long long b = blockIdx.x;
+    if (b >= counts[1]) return;
+    const int grp = ivf_locate(item, (int)counts[0], b);
+    const long long chunk = b - item[grp];
+    const uint2 gd = groups[grp];   // (first pair in `sorted`, pairs)
+    const int live = (int)gd.y;
+    const long long l = (long long)(sorted[gd.x] >> 32);
+    const long long lo = list_off[l], len = list_off[l + 1] - lo;
+    if (threadIdx.x < G) {
+        const int slot = threadIdx.x;
+        const long long pi = (long long)(sorted[gd.x + (slot < live ? slot : 0)] & 0xffffffffull);
+        const long long ql = pi / np, j = pi - ql * np;
+        s_query[slot] = q0 + (int)ql;
+        s_key[slot] = ql * key_stride + pre[(q0 + ql) * (np + 1) + j];
+    }
+    __syncthreads();
+    const int dq = (d + 3) / 4 * 4;
+    for (int g = 0; g < G; ++g) {
+        const float* src = queries + (long long)s_query[g] * d;
+        for (int c = threadIdx.x; c < dq; c += 256) s_qg[g * dq + c] = c < d ? src[c] : 0.f;
+    }
+    __syncthreads();
+    const long long r = chunk * kIvfChunk + threadIdx.x;
+    if (r >= len) return;
+    const long long s = lo + r;
+    float acc[G];
+    pw_tree_multi<float, G, kIvfSharedDepth>(SqLeafGroup<G>{rows + s * ld, s_qg, dq, live}, d, acc);
+    const u64 id = (u64)ids[s];
+#pragma unroll
+    for (int g = 0; g < G; ++g)
+        if (g < live) keys[s_key[g] + r] = ((u64)ordered_f32(sqrt_rn_f32(acc[g])) << 32) | id;
+}
 // (4) the select's post-op, IvfFinalize: sq_ivf_group.hpp.
 
 // ------------------------------------------------------------------ k-means update
@@ -203,7 +257,7 @@ static int ivf_search_device(IvfHandle* h, const float* q_dev, int nq, int k, in
     // candidate offsets; only [total, longest] visit the host
     SQ_TRY(h->pre.reserve((size_t)nq * (np + 1) * 8));
     SQ_TRY(h->cnt.reserve((size_t)nq * 4));
-    SQ_TRY(h->totals_host.reserve(16));
+    SQ_TRY(h->totals_host.reserve(32));
     void* th_dev = nullptr;
     SQ_TRY(h->totals_host.device_ptr(&th_dev));
     SQ_TRY(launch<ivf_probe_sizes_kernel>(dim3(nq), dim3(256), 0, st, h->probe_idx.as<long long>(), np, h->list_off.as<long long>(), nlist,
@@ -212,6 +266,8 @@ static int ivf_search_device(IvfHandle* h, const float* q_dev, int nq, int k, in
     SQ_HIP(stream_wait(st));
     const long long* th = reinterpret_cast<const long long*>(h->totals_host.p);
     const long long total = th[0], maxc = th[1];
+    long long* served = static_cast<long long*>(th_dev) + 2;   // added to by ivf_pair_groups_kernel, read by sq_ivf_search after its wait
+    reinterpret_cast<long long*>(h->totals_host.p)[2] = 0;
     if (maxc > kIvfMaxRows) return fail(SQ_ERR_INTERNAL, "sq_ivf_search: a query has more candidates than the index has rows");
     const long long mc = maxc > 0 ? maxc : 1;
     const int k_sel = (int)ivf_select_k(maxc, k);
@@ -225,10 +281,22 @@ static int ivf_search_device(IvfHandle* h, const float* q_dev, int nq, int k, in
     for (int q0 = 0; q0 < nq; q0 += slice) {
         const int m = nq - q0 < slice ? nq - q0 : slice;
         if (maxc > 0) {
+            // the slice's candidates: no more than the batch's, nor than m times the longest list of candidates
+            const long long cands = std::min(total, (long long)m * maxc), pairs = (long long)m * np;
+            const bool shared = ivf_scan_route(h->opt.ivf_scan, d, pw_tree_depth(d), m, np, nlist, cands);
+            if (shared)
+                SQ_TRY(ivf_pair_group<kIvfSharedGroup>(h->probe_idx.as<long long>(), q0, m, np, h->list_off.as<long long>(), nlist, h->pairs, served, st));
             if (prof) SQ_HIP(hipEventRecord(h->ev[0], st));
-            SQ_TRY(launch<ivf_scan_kernel>(dim3((unsigned)ivf_chunks(maxc), (unsigned)m), dim3(256), (size_t)h->ld * 4, st, h->rows.as<float>(),
-                                           h->ld, d, h->ids.as<u32>(), h->list_off.as<long long>(), q_dev, q0, h->probe_idx.as<long long>(),
-                                           h->pre.as<long long>(), np, mc, h->keys.as<u64>()));
+            if (shared)
+                SQ_TRY(launch_lds<ivf_scan_shared_kernel<kIvfSharedGroup>>(
+                    (int)kIvfSharedLdsBytes, dim3((unsigned)ivf_shared_items_bound(cands, pairs)), dim3(256), (size_t)kIvfSharedGroup * h->ld * 4, st,
+                    h->rows.as<float>(), h->ld, d, h->ids.as<u32>(), h->list_off.as<long long>(), q_dev, q0, h->pre.as<long long>(), np,
+                    h->pairs.sorted.as<u64>(), h->pairs.groups.as<uint2>(), h->pairs.item.as<long long>(), h->pairs.counts.as<long long>(), mc,
+                    h->keys.as<u64>()));
+            else
+                SQ_TRY(launch<ivf_scan_kernel>(dim3((unsigned)ivf_chunks(maxc), (unsigned)m), dim3(256), (size_t)h->ld * 4, st, h->rows.as<float>(),
+                                               h->ld, d, h->ids.as<u32>(), h->list_off.as<long long>(), q_dev, q0, h->probe_idx.as<long long>(),
+                                               h->pre.as<long long>(), np, mc, h->keys.as<u64>()));
             if (prof) {
                 SQ_HIP(hipEventRecord(h->ev[1], st));
                 SQ_HIP(hipEventSynchronize(h->ev[1]));
@@ -353,6 +421,7 @@ extern "C" int sq_ivf_search(sq_handle_t hid, const float* queries, int nq, int 
         SQ_TRY(ivf_search_device(h, queries, nq, k, nprobe, out_dist, reinterpret_cast<long long*>(out_idx), st));
         SQ_HIP(stream_wait(st));
     }
+    h->stats.mid_tier_queries = reinterpret_cast<const long long*>(h->totals_host.p)[2];   // (query, list) pairs of the list-major scan
     if (h->opt.profile != 0) h->stats.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
     return SQ_OK;
 }

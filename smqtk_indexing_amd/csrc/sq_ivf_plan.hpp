@@ -84,4 +84,39 @@ inline long long ivf_slice_queries(long long nq, long long maxc, long long k, lo
     return s < nq ? s : nq;
 }
 
+// ------------------------------------------------------------------ the list-major scan (ivf_scan_shared_kernel, sq_ivf.hip)
+// A slice of m queries has m * np (query, probe rank) pairs.  Sorted by list, the run of a list probed by c pairs is cut
+// into ceil(c / G) groups of at most G pairs; a work item is one group x one chunk of kIvfChunk rows of that list, and
+// the items of all groups are numbered by an exclusive prefix over the groups in (list, group) order.
+static constexpr int kIvfSharedGroup = 8;                         // G: queries a row is scored against once it is in registers
+static constexpr long long kIvfSharedLdsBytes = 160 * 1024 - 256; // the G staged queries of round_up(d, 4) floats each
+static constexpr int kIvfSharedDepth = 6;                         // levels of the fixed-depth tree walk (EXACT_GROUP_DEPTH)
+static constexpr long long kIvfSharedMaxPairs = 1ll << 24;        // pairs one slice may sort (the index rides in a key's low 32 bits; 256 MB of sort scratch)
+static constexpr long long kIvfSharedMaxItems = 0x7fffffffll;     // the scan's grid is one-dimensional
+static constexpr long long kIvfSharedAutoRatio = 1;               // option "ivf_scan" = -1: pairs per list of the index from which the sort pays (profiles/ivf_shared_scan.txt)
+
+SQ_IVF_HD inline long long ivf_pair_groups(long long c, int G) { return (c + G - 1) / G; }
+// pairs of group g of a run of c
+SQ_IVF_HD inline int ivf_pair_group_size(long long c, long long g, int G) {
+    const long long left = c - g * G;
+    return (int)(left < G ? left : G);
+}
+SQ_IVF_HD inline long long ivf_row_chunks(long long len) { return (len + kIvfChunk - 1) / kIvfChunk; }
+// The grid of the scan, from what the host has after its one visit: every pair of the slice scans ceil(len / 256) chunks
+// at the most (a group scans them once for all its pairs), and the sum of ceil(len / 256) over the pairs is no more than
+// floor(sum of len / 256) + pairs.  `cands`: an upper bound of the slice's candidates.
+inline long long ivf_shared_items_bound(long long cands, long long pairs) { return cands / kIvfChunk + pairs; }
+
+// Which scan a slice of m queries x np probes runs: true = the list-major scan.  `mode` is option "ivf_scan" (0 = the
+// per-query scan, 1 = list-major wherever it can run, -1 = list-major where the slice has kIvfSharedAutoRatio pairs per
+// list of the index: the pairs per DISTINCT probed list -- the queries a row is scored against per read -- are at least
+// that, and the host knows both numbers without a visit to the device).  `tree_depth` is pw_tree_depth(d).
+inline bool ivf_scan_route(int mode, int d, int tree_depth, long long m, long long np, long long nlist, long long cands) {
+    if (mode == 0) return false;
+    if (ivf_row_stride(d) * 4 * kIvfSharedGroup > kIvfSharedLdsBytes || tree_depth > kIvfSharedDepth) return false;
+    const long long pairs = m * np;
+    if (pairs < 1 || pairs > kIvfSharedMaxPairs || ivf_shared_items_bound(cands, pairs) > kIvfSharedMaxItems) return false;
+    return mode > 0 || pairs >= kIvfSharedAutoRatio * nlist;
+}
+
 }  // namespace sq
