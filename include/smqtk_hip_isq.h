@@ -61,6 +61,19 @@ extern "C" {
  *                  reads its code row 8 or 16 bytes at a time, decodes in registers and sums in numpy's order.
  *                  sq_get_stats: scan_launches (slices scanned), candidates, bytes_scanned (candidates x row stride), and
  *                  with option "profile" scan_ms / total_ms.  An index with no rows answers with padding only.
+ *                  Option "isq_scan" (handle or process-wide) chooses the scan of a slice: 0 = isq_scan_kernel as above,
+ *                  1 = the list-major scan wherever it can run, -1 (the default) = list-major for slices with at least R
+ *                  (query, list) pairs per list of the index, R per kind as profiles/ivf_sq_shared_scan.txt measured it
+ *                  (sq_isq_plan.hpp).  List-major: the slice's pairs are sorted by list on the device (sq_ivf_search's
+ *                  grouping: no atomics, no host visit) and cut into groups of up to 8 queries of one list;
+ *                  isq_scan_shared_kernel decodes 256 code rows of the list once per group -- a leaf of up to 128
+ *                  elements in registers at a time, the ranges staged once beside the group's queries in LDS -- scores them
+ *                  against the group's queries in the same order of sums and stores every key where isq_scan_kernel stores
+ *                  it: the results are the same bits.  It takes rows whose staging -- (2 + 8) round_up(d, 4) * 4 bytes
+ *                  (SQ8), 8 round_up(d, 4) * 4 bytes (F16) -- fits 160 KiB - 256 bytes (d up to 4088, or 5112) and slices
+ *                  of up to 2^24 pairs; everything else runs isq_scan_kernel.  sq_get_stats: mid_tier_queries = the pairs
+ *                  of non-empty lists the list-major scan served (0: every slice ran per query); the other fields are
+ *                  unchanged.  sq_refine_search over an IVF-SQ base takes the scan by the base handle's option.
  * Limits, refused before a device is touched: a kind other than the two, SQ8 without vmin / step or F16 with them, a
  * non-finite vmin or step or a negative step: SQ_ERR_INVALID; a metric other than L2, nlist > 65536, a search mode other
  * than the two blocking ones, and a d whose staging -- 3 round_up(d, 4) * 4 bytes (SQ8), round_up(d, 4) * 4 bytes (F16) --

@@ -67,7 +67,8 @@ struct Options {
     int refine_direct = -1;      // refine store (sq_refine.hip): 1 = the re-rank reads its candidates' code rows straight from global memory, 0 = it gathers a tile of them into LDS first, -1 = automatic: by what profiles/ivf_refine.txt measured on gathers that miss the caches, the LDS gather for float16 and float32 stores (0.85 - 0.96 x the direct variant's time) and direct loads for 8-bit stores (the gather: 1.01 - 1.11 x); the bits are the same
     int ivf_assign = 1;          // inverted-list builds (sq_ivf_assign.hpp): 1 = rows are assigned to their nearest centroid by ivf_assign_kernel (float32 MFMA scores, a certified gap) wherever ivf_assign_route covers the call, and only the rows it leaves undecided by the exact dense search; 0 = the exact dense search for every row, in slices of 1024; the assignment is the same bits
     int ivf_scan = -1;           // IVF-Flat search (sq_ivf.hip): 0 = the per-query scan (ivf_scan_kernel: a probed list is read once per query that probes it); 1 = the list-major scan (ivf_scan_shared_kernel: the slice's (query, list) pairs sorted by list, a list read once per group of 8 queries) wherever ivf_scan_route takes the slice; -1 = automatic: list-major for slices with at least as many pairs as the index has lists (profiles/ivf_shared_scan.txt); the bits are the same
-    int hamming_fused = 1;       // Hamming searches of up to 32 queries (64 .. 448-bit codes, k <= 2048) as three launches (head: sampled histogram + thresholds by the last workgroup; stream; pick: exact k-th distance + gather + sort per query) instead of a memset and five; 0 = the general chain
+    int isq_scan = -1;           // IVF-SQ search (sq_isq.hip): 0 = the per-query scan (isq_scan_kernel: a probed code row is read and decoded once per query that probes it); 1 = the list-major scan (isq_scan_shared_kernel: a row decoded once per group of 8 queries of its list) wherever isq_scan_route takes the slice; -1 = automatic: list-major for slices with at least isq_shared_auto_ratio(kind) pairs per list of the index (sq_isq_plan.hpp, profiles/ivf_sq_shared_scan.txt); the bits are the same
+    int hamming_fused = 1;      // Hamming searches of up to 32 queries (64 .. 448-bit codes, k <= 2048) as three launches (head: sampled histogram + thresholds by the last workgroup; stream; pick: exact k-th distance + gather + sort per query) instead of a memset and five; 0 = the general chain
 };
 extern Options g_opt;   // process-wide defaults (sq_set_option); a handle may override any of them (sq_handle_set_option)
 // name -> member, shared by sq_set_option and sq_handle_set_option (sq_core.hip)

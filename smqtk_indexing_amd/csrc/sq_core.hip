@@ -118,6 +118,7 @@ int Options::*option_member(const char* name) {
         {"refine_direct", &Options::refine_direct},
         {"ivf_assign", &Options::ivf_assign},
         {"ivf_scan", &Options::ivf_scan},
+        {"isq_scan", &Options::isq_scan},
     };
     if (!name) return nullptr;
     for (const auto& f : kFields)

@@ -6,7 +6,8 @@
 // metrics.euclidean_distance over the decoded row in numpy's order -- so a search returns the bits sq_ivf_search returns
 // over the decoded matrix.  The coarse index, the counting sort, the probed lists' prefix and the select's post-op are
 // sq_ivf_group.hpp's, the host arithmetic sq_ivf_plan.hpp's, the tree walk sq_pairwise.hpp's.  New device code: the column
-// ranges (training), the scatter of code rows, and the decoding scan; the codecs and the encoder are sq_isq_codec.hpp's.
+// ranges (training), the scatter of code rows, and the decoding scans -- per query here, list-major in sq_isq_shared.hpp;
+// the codecs and the encoder are sq_isq_codec.hpp's, the scans' LDS sizes and their route sq_isq_plan.hpp's.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -14,18 +15,12 @@
 
 #include "../../include/smqtk_hip_isq.h"
 #include "sq_isq_codec.hpp"
+#include "sq_isq_shared.hpp"   // the list-major scan; the LDS sizes and the route: sq_isq_plan.hpp
 #include "sq_ivf_group.hpp"
 
 namespace sq {
 
-typedef u32 u32x2 __attribute__((ext_vector_type(2)));
-typedef u32 u32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-static constexpr int kIsqStageMax = 160 * 1024;   // dynamic LDS a scan workgroup may ask for
-
-// bytes of the scan's LDS staging (a code's and a stored row's bytes: sq_isq_codec.hpp)
-inline long long isq_stage_bytes(int d, int kind) { return (kind == SQ_ISQ_SQ8 ? 3 : 1) * ivf_row_stride(d) * 4; }
+static_assert(kIsqSq8 == SQ_ISQ_SQ8 && kIsqF16 == SQ_ISQ_F16, "sq_isq_plan.hpp names the kinds of smqtk_hip_isq.h");
 
 struct IsqHandle : HandleBase {
     int d = 0, nlist = 0, code_kind = SQ_ISQ_SQ8;
@@ -36,7 +31,8 @@ struct IsqHandle : HandleBase {
     long long add_us = 0;
     // scratch of a search
     DevBuf q_dev, probe_dist, probe_idx, pre, cnt, keys, out_keys, out_dist, out_idx, sort_tmp;
-    HostPinned totals_host;
+    HostPinned totals_host;              // [candidates in total, longest candidate list, pairs the list-major scan served]
+    IvfPairGroups pairs;                 // the list-major scan's groups of a slice
     PinnedStage stage;
     bool list_shape(int* d_out, long long* n_out, long long* id_base_out) const override {
         *d_out = d;
@@ -311,7 +307,9 @@ static __global__ __launch_bounds__(256) void isq_scan_kernel(const u8* __restri
 }
 
 // The search with queries and outputs in device memory, enqueued on `st`; the last select is not waited for.
-// ivf_search_device (sq_ivf.hip) with the decoding scan: the same probe, offsets, slice rule, select and stats.
+// ivf_search_device (sq_ivf.hip) with the decoding scans: the same probe, offsets, slice rule, select and stats.  A slice
+// that isq_scan_route takes (option "isq_scan") is grouped by ivf_pair_group and scanned list-major by
+// isq_scan_shared_kernel (sq_isq_shared.hpp); every other slice runs isq_scan_kernel.  The keys are the same bits.
 static int isq_search_device(IsqHandle* h, const float* q_dev, int nq, int k, int nprobe, float* od, long long* oi, hipStream_t st) {
     const int d = h->d, nlist = h->nlist, np = nprobe < nlist ? nprobe : nlist;
     const bool prof = h->opt.profile != 0;
@@ -320,7 +318,7 @@ static int isq_search_device(IsqHandle* h, const float* q_dev, int nq, int k, in
     SQ_TRY(sq_dense_search(h->coarse, q_dev, nq, np, h->probe_dist.p, h->probe_idx.as<int64_t>(), SQ_MEM_DEVICE, st));
     SQ_TRY(h->pre.reserve((size_t)nq * (np + 1) * 8));
     SQ_TRY(h->cnt.reserve((size_t)nq * 4));
-    SQ_TRY(h->totals_host.reserve(16));
+    SQ_TRY(h->totals_host.reserve(32));
     void* th_dev = nullptr;
     SQ_TRY(h->totals_host.device_ptr(&th_dev));
     SQ_TRY(launch<ivf_probe_sizes_kernel>(dim3(nq), dim3(256), 0, st, h->probe_idx.as<long long>(), np, h->list_off.as<long long>(), nlist,
@@ -329,6 +327,8 @@ static int isq_search_device(IsqHandle* h, const float* q_dev, int nq, int k, in
     SQ_HIP(stream_wait(st));
     const long long* th = reinterpret_cast<const long long*>(h->totals_host.p);
     const long long total = th[0], maxc = th[1];
+    long long* served = static_cast<long long*>(th_dev) + 2;   // added to by ivf_pair_groups_kernel, read by sq_isq_search after its wait
+    reinterpret_cast<long long*>(h->totals_host.p)[2] = 0;
     if (maxc > kIvfMaxRows) return fail(SQ_ERR_INTERNAL, "sq_isq_search: a query has more candidates than the index has rows");
     const long long mc = maxc > 0 ? maxc : 1;
     const int k_sel = (int)ivf_select_k(maxc, k);
@@ -343,9 +343,25 @@ static int isq_search_device(IsqHandle* h, const float* q_dev, int nq, int k, in
     for (int q0 = 0; q0 < nq; q0 += slice) {
         const int m = nq - q0 < slice ? nq - q0 : slice;
         if (maxc > 0) {
+            // the slice's candidates: no more than the batch's, nor than m times the longest list of candidates
+            const long long cands = std::min(total, (long long)m * maxc), pairs = (long long)m * np;
+            const bool shared = isq_scan_route(h->opt.isq_scan, h->code_kind, d, pw_tree_depth(d), m, np, nlist, cands);
+            if (shared)
+                SQ_TRY(ivf_pair_group<kIvfSharedGroup>(h->probe_idx.as<long long>(), q0, m, np, h->list_off.as<long long>(), nlist, h->pairs, served, st));
             if (prof) SQ_HIP(hipEventRecord(h->ev[0], st));
-            const dim3 grid((unsigned)ivf_chunks(maxc), (unsigned)m);
-            if (h->code_kind == SQ_ISQ_SQ8)
+            const dim3 grid((unsigned)ivf_chunks(maxc), (unsigned)m), items((unsigned)ivf_shared_items_bound(cands, pairs));
+            const size_t lds_shared = (size_t)isq_shared_lds_bytes(d, h->code_kind);
+            if (shared && h->code_kind == SQ_ISQ_SQ8)
+                SQ_TRY(launch_lds<isq_scan_shared_kernel<SQ_ISQ_SQ8, kIvfSharedGroup>>(
+                    (int)kIvfSharedLdsBytes, items, dim3(256), lds_shared, st, h->codes.as<u8>(), h->stride, d, h->params.as<float>(), h->ids.as<u32>(),
+                    h->list_off.as<long long>(), q_dev, q0, h->pre.as<long long>(), np, h->pairs.sorted.as<u64>(), h->pairs.groups.as<uint2>(),
+                    h->pairs.item.as<long long>(), h->pairs.counts.as<long long>(), mc, h->keys.as<u64>()));
+            else if (shared)
+                SQ_TRY(launch_lds<isq_scan_shared_kernel<SQ_ISQ_F16, kIvfSharedGroup>>(
+                    (int)kIvfSharedLdsBytes, items, dim3(256), lds_shared, st, h->codes.as<u8>(), h->stride, d, h->params.as<float>(), h->ids.as<u32>(),
+                    h->list_off.as<long long>(), q_dev, q0, h->pre.as<long long>(), np, h->pairs.sorted.as<u64>(), h->pairs.groups.as<uint2>(),
+                    h->pairs.item.as<long long>(), h->pairs.counts.as<long long>(), mc, h->keys.as<u64>()));
+            else if (h->code_kind == SQ_ISQ_SQ8)
                 SQ_TRY(launch_lds<isq_scan_kernel<SQ_ISQ_SQ8>>(kIsqStageMax, grid, dim3(256), lds, st, h->codes.as<u8>(), h->stride, d, h->ld,
                                                                h->params.as<float>(), h->ids.as<u32>(), h->list_off.as<long long>(), q_dev, q0,
                                                                h->probe_idx.as<long long>(), h->pre.as<long long>(), np, mc, h->keys.as<u64>()));
@@ -530,6 +546,7 @@ extern "C" int sq_isq_search(sq_handle_t hid, const float* queries, int nq, int 
         SQ_TRY(isq_search_device(h, queries, nq, k, nprobe, out_dist, reinterpret_cast<long long*>(out_idx), st));
         SQ_HIP(stream_wait(st));
     }
+    h->stats.mid_tier_queries = reinterpret_cast<const long long*>(h->totals_host.p)[2];   // (query, list) pairs of the list-major scan
     if (h->opt.profile != 0) h->stats.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
     return SQ_OK;
 }

@@ -16,6 +16,19 @@ against --hbm-peak.  Under each table: the SQ8 and F16 scans as a ratio to ivf_s
 
     python tools/isq_bench.py --out profiles/ivf_sq.txt
     python tools/isq_bench.py --only 32,64 --calls 200 --windows 1 --no-pq --no-exact    # one shape, e.g. under a counter run
+
+--shared: the two scans of the IVF-SQ index against each other (profiles/ivf_sq_shared_scan.txt): handle option
+"isq_scan" = 0 (isq_scan_kernel: a probed code row is read and decoded once per query) and 1 (isq_scan_shared_kernel: a
+row decoded once per group of 8 queries of its list) for both kinds, batches of 1 / 32 / 256 / 1024 queries at nprobe 16
+and 64, with IVF-Flat's list-major call ("ivf_scan" = 1) on the same batch beside them.  The options alternate window by
+window in one process (a window is this much time of the slowest option, 3 .. 100 blocking device calls over 8 rotating
+query batches, on the host clock; median of --windows windows with the fastest and slowest beside it); the scan kernel's
+own time is a pass of its own under option "profile" (the list-major path's sort and grouping are outside those events and
+inside the call's time).  The answers of the two options are compared bit for bit before anything is timed.  Last, per
+kind, the R of the automatic rule: the smallest of 1, 2, 4, 8 pairs per list at which option 1 is no slower than option 0
+on every measured batch with at least that many.
+
+    python tools/isq_bench.py --shared --out profiles/ivf_sq_shared_scan.txt
 """
 import argparse
 import json
@@ -38,8 +51,10 @@ def main():
     ap.add_argument("--m", type=int, default=32, help="sub-quantisers of the residual IVF-PQ index")
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--k", type=int, default=100)
-    ap.add_argument("--nprobes", default="1,4,16,64")
-    ap.add_argument("--batches", default="1,32")
+    ap.add_argument("--nprobes", default="", help="default 1,4,16,64; with --shared 16,64")
+    ap.add_argument("--batches", default="", help="default 1,32; with --shared 1,32,256,1024")
+    ap.add_argument("--shared", action="store_true", help="the per-query scan against the list-major scan (option \"isq_scan\" 0 / 1)")
+    ap.add_argument("--window-ms", type=float, default=60.0, help="--shared: a window is this much time of the slowest option, 3 .. 100 calls")
     ap.add_argument("--calls", type=int, default=200, help="calls per timed window")
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--add-block", type=int, default=2_000_000)
@@ -64,8 +79,8 @@ def main():
         lines.append(s)
 
     n, d, k, nlist = args.rows, args.dim, args.k, args.nlist
-    nprobes = [int(v) for v in args.nprobes.split(",")]
-    batches = [int(v) for v in args.batches.split(",")]
+    nprobes = [int(v) for v in (args.nprobes or ("16,64" if args.shared else "1,4,16,64")).split(",")]
+    batches = [int(v) for v in (args.batches or ("1,32,256,1024" if args.shared else "1,32")).split(",")]
     if args.only:
         only = tuple(int(v) for v in args.only.split(","))
         batches, nprobes = [only[0]], [only[1]]
@@ -74,7 +89,7 @@ def main():
     all_q = bench.make_rows(torch, args.data, max(batches) * nbatch, d, dev, 1234)
     torch.cuda.synchronize()
     stream = torch.cuda.current_stream().cuda_stream
-    say(f"# IVF-SQ vs IVF-Flat vs residual IVF-PQ vs exact, {_lib.device_name(0)[0]}: {n} x {d} float32 rows ({args.data}), nlist {nlist}, k {k}")
+    say(f"# {'IVF-SQ scans: per query (isq_scan 0) vs list-major (isq_scan 1), beside IVF-Flat list-major' if args.shared else 'IVF-SQ vs IVF-Flat vs residual IVF-PQ vs exact'}, {_lib.device_name(0)[0]}: {n} x {d} float32 rows ({args.data}), nlist {nlist}, k {k}")
 
     rs = np.random.RandomState(0)
     sm = min(n, 256 * nlist)
@@ -110,6 +125,10 @@ def main():
     made("sq8", _lib.IsqIndex(centroids, _lib.SQ_ISQ_SQ8, vmin, step), ("codes_bytes", "ids_offsets_bytes", "coarse_params_bytes"))
     made("f16", _lib.IsqIndex(centroids, _lib.SQ_ISQ_F16), ("codes_bytes", "ids_offsets_bytes", "coarse_params_bytes"))
     made("flat", _lib.IvfIndex(centroids), ("rows_bytes", "ids_offsets_bytes", "coarse_bytes"))
+    if args.shared:
+        shared_scans(args, torch, _lib, indexes, all_q, batches, nprobes, nbatch, stream, say)
+        finish(args, lines, indexes.values())
+        return
     if not args.no_pq:
         m = args.m
         sample_res = _lib.pq_residuals(sample, centroids)
@@ -195,15 +214,92 @@ def main():
     summary["shapes"] = report
     say()
     say(json.dumps(summary))
-    say()
+    finish(args, lines, list(indexes.values()) + ([dense] if dense is not None else []))
+
+
+def finish(args, lines, indexes):
+    print(flush=True)
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "a") as f:
-            f.write("\n".join(lines) + "\n")
-    for index in indexes.values():
+            f.write("\n".join(lines) + "\n\n")
+    for index in indexes:
         index.close()
-    if dense is not None:
-        dense.close()
+
+
+def shared_scans(args, torch, _lib, indexes, all_q, batches, nprobes, nbatch, stream, say):
+    """--shared: see the module's docstring."""
+    k, nlist, dev = args.k, args.nlist, all_q.device
+    flat = indexes["flat"]
+    flat.set_option("ivf_scan", 1)
+    say("ms per blocking call, median [fastest .. slowest] of %d alternating windows; scan = the scan kernel alone, us" % args.windows)
+    say("kind queries nprobe pairs/nlist |  option 0 ms              scan us |  option 1 ms              scan us  served |  call 0/1  scan 0/1 | flat list-major ms   scan us")
+
+    def window(call, qs, calls):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        for c in range(calls):
+            call(qs[c % nbatch])
+        return (time.perf_counter() - t) / calls * 1e3
+
+    def scan_us(index, call, qs, calls):
+        index.set_option("profile", 1)
+        ms = []
+        for c in range(calls):
+            call(qs[c % nbatch])
+            ms.append(index.stats()["scan_ms"])
+        index.set_option("profile", 0)
+        return statistics.median(ms) * 1e3
+
+    ratio = {"sq8": [], "f16": []}      # (pairs per list, option 0 ms / option 1 ms)
+    for nq in batches:
+        qs = [all_q[j * nq:(j + 1) * nq].contiguous() for j in range(nbatch)]
+        od = torch.empty((nq, k), dtype=torch.float32, device=dev)
+        oi = torch.empty((nq, k), dtype=torch.int64, device=dev)
+        for p in nprobes:
+            calls_of = {name: (lambda ix: lambda q: ix.search_device(q.data_ptr(), nq, k, p, od.data_ptr(), oi.data_ptr(), stream))(ix)
+                        for name, ix in indexes.items()}
+            # warm-up, the answers' equality, the calls per window
+            first, served = [], {}
+            for name in ("sq8", "f16"):
+                answers = {}
+                for opt in (0, 1):
+                    indexes[name].set_option("isq_scan", opt)
+                    calls_of[name](qs[0])
+                    t = time.perf_counter()
+                    calls_of[name](qs[0])
+                    first.append((time.perf_counter() - t) * 1e3)
+                    if opt:
+                        served[name] = indexes[name].stats()["mid_tier_queries"]
+                    answers[opt] = (od.cpu().numpy().view(np.uint32).copy(), oi.cpu().numpy().copy())
+                assert np.array_equal(answers[1][0], answers[0][0]) and np.array_equal(answers[1][1], answers[0][1]), "the scans disagree"
+            calls_of["flat"](qs[0])
+            calls = int(min(100, max(3, args.window_ms / max(first))))
+            times = {key: [] for key in (("sq8", 0), ("sq8", 1), ("f16", 0), ("f16", 1), "flat")}
+            for _ in range(args.windows):
+                for key in times:
+                    if key != "flat":
+                        indexes[key[0]].set_option("isq_scan", key[1])
+                    times[key].append(window(calls_of["flat" if key == "flat" else key[0]], qs, calls))
+            scan = {"flat": scan_us(flat, calls_of["flat"], qs, calls)}
+            for name in ("sq8", "f16"):
+                for opt in (0, 1):
+                    indexes[name].set_option("isq_scan", opt)
+                    scan[(name, opt)] = scan_us(indexes[name], calls_of[name], qs, calls)
+
+            def fig(key):
+                return f"{statistics.median(times[key]):8.3f} [{min(times[key]):7.3f} .. {max(times[key]):7.3f}]"
+
+            for name in ("sq8", "f16"):
+                t0, t1 = statistics.median(times[(name, 0)]), statistics.median(times[(name, 1)])
+                ratio[name].append((nq * min(p, nlist) / nlist, t0 / t1))
+                say(f"{name:4s} {nq:7d} {p:6d} {nq * min(p, nlist) / nlist:11.2f} | {fig((name, 0))} {scan[(name, 0)]:9.1f} | {fig((name, 1))} {scan[(name, 1)]:9.1f} "
+                    f"{served[name]:7d} | {t0 / t1:7.2f} x {scan[(name, 0)] / scan[(name, 1)]:7.2f} x | {statistics.median(times['flat']):8.3f} "
+                    f"{scan['flat']:14.1f}   ({calls} calls per window)")
+    say()
+    for name, rows in ratio.items():
+        fits = [R for R in (1, 2, 4, 8) if any(ppl >= R for ppl, _ in rows) and all(gain >= 1.0 for ppl, gain in rows if ppl >= R)]
+        say(f"# {name}: R = {fits[0] if fits else 0} (option 1 no slower than option 0 on every measured batch of at least R pairs per list; 0 = never)")
 
 
 if __name__ == "__main__":
