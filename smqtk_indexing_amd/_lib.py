@@ -91,6 +91,14 @@ OPQ_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), OPQ_LIB_NAME)
 OPQ_EXPORTS = ("sq_opq_create", "sq_opq_apply", "sq_opq_info", "sq_opq_destroy")
 SQ_OPQ_MAX_D = 4096         # widest row of an OPQ transform (smqtk_hip_opq.h)
 SQ_OPQ_INFO_FIELDS = 4      # words of sq_opq_info
+# the PCA front stage: built on the main library alone
+PCA_LIB_NAME = "libsmqtk_hip_pca.so"
+PCA_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), PCA_LIB_NAME)
+PCA_EXPORTS = ("sq_pca_moments", "sq_pca_create", "sq_pca_apply", "sq_pca_info", "sq_pca_destroy")
+SQ_PCA_MAX_D_IN = 8192      # widest input row of a PCA transform and of sq_pca_moments (smqtk_hip_pca.h)
+SQ_PCA_MAX_D_OUT = 512      # widest output row
+SQ_PCA_RUN = 1024           # rows a float32 accumulator of sq_pca_moments runs for before it is folded into float64
+SQ_PCA_INFO_FIELDS = 7      # words of sq_pca_info
 
 
 class HipError(RuntimeError):
@@ -361,6 +369,34 @@ def load_opq() -> ctypes.CDLL:
         return _opq_lib
 
 
+_pca_lib: Optional[ctypes.CDLL] = None
+
+
+def load_pca() -> ctypes.CDLL:
+    """Load the PCA extension library (once), after the main library it is built on.  Raises HipError when it is missing:
+    there is no fallback."""
+    global _pca_lib
+    load()
+    with _lock:
+        if _pca_lib is None:
+            if not os.path.isfile(PCA_LIB_PATH):
+                raise HipError(f"{PCA_LIB_NAME} not found at {PCA_LIB_PATH}; build it with `make -C smqtk_indexing_amd/csrc`")
+            try:
+                lib = ctypes.CDLL(PCA_LIB_PATH)
+            except OSError as ex:
+                raise HipError(f"cannot load {PCA_LIB_PATH}: {ex}") from ex
+            c_int, c_i64, c_vp = ctypes.c_int, ctypes.c_int64, ctypes.c_void_p
+            lib.sq_pca_moments.argtypes = [c_vp, c_i64, c_int, c_vp, c_vp, c_int]
+            lib.sq_pca_create.argtypes = [c_vp, c_vp, c_int, c_int, ctypes.POINTER(c_i64)]
+            lib.sq_pca_apply.argtypes = [c_i64, c_vp, c_i64, c_vp, c_int, c_vp]
+            lib.sq_pca_info.argtypes = [c_i64, ctypes.POINTER(c_i64), c_int]
+            lib.sq_pca_destroy.argtypes = [c_i64]
+            for name in PCA_EXPORTS:
+                getattr(lib, name).restype = c_int
+            _pca_lib = lib
+        return _pca_lib
+
+
 def _check(rc: int, what: str) -> None:
     if rc != SQ_OK:
         msg = load().sq_last_error()
@@ -411,6 +447,12 @@ def refine_usable() -> bool:
 def opq_usable() -> bool:
     """A GPU, the main library, the IVF-Flat and IVF-PQ extensions and the OPQ-transform extension beside them."""
     return pq_usable() and os.path.isfile(OPQ_LIB_PATH)
+
+
+def pca_usable() -> bool:
+    """A GPU, the main library, the IVF-Flat and IVF-PQ extensions (the indexes behind the projection) and the PCA
+    extension beside them."""
+    return pq_usable() and os.path.isfile(PCA_LIB_PATH)
 
 
 def device_name(device: int = 0) -> Tuple[str, int, int]:
@@ -1259,6 +1301,73 @@ class OpqTransform(_Handle):
         out = (ctypes.c_int64 * SQ_OPQ_INFO_FIELDS)()
         _check(load_opq().sq_opq_info(self.handle, out, SQ_OPQ_INFO_FIELDS), "sq_opq_info")
         return dict(zip(self.INFO_FIELDS, (int(v) for v in out)))
+
+
+class PcaTransform(_Handle):
+    """A ``d_out x d_in`` float32 matrix and a float32 mean resident on the device (``sq_pca_*``): :meth:`apply` returns
+    ``(x - mean) @ A.T`` in float32, within ``gamma_(d_in + 1) * |x - mean| @ |A|.T`` of the float64 evaluation
+    (include/smqtk_hip_pca.h) -- not bit for bit.  Use as a context manager or ``close()`` it."""
+    _destroy_name = "sq_pca_destroy"
+    INFO_FIELDS = ("d_in", "d_out", "resident_bytes", "last_rows", "last_us", "tile_rows", "blocks_per_cu")
+
+    def close(self) -> None:
+        if self.handle:
+            h, self.handle = self.handle, 0
+            try:
+                load_pca().sq_pca_destroy(h)
+            except Exception:
+                pass
+
+    def __init__(self, matrix: np.ndarray, mean: Optional[np.ndarray] = None):
+        super().__init__()
+        a = _host(matrix, np.float32)
+        if a.ndim != 2:
+            raise ValueError("matrix must be float32[d_out, d_in]")
+        self.d_out, self.d_in = int(a.shape[0]), int(a.shape[1])
+        m = None if mean is None else _host(mean, np.float32).reshape(-1)
+        if m is not None and m.shape[0] != self.d_in:
+            raise ValueError("mean must be float32[d_in]")
+        h = ctypes.c_int64(0)
+        _check(load_pca().sq_pca_create(_ptr(a), None if m is None else _ptr(m), self.d_in, self.d_out, ctypes.byref(h)), "sq_pca_create")
+        self.handle = int(h.value)
+
+    def __enter__(self) -> "PcaTransform":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+    def apply(self, x: np.ndarray) -> np.ndarray:
+        """``[n, d_in]`` float32 host rows -> ``[n, d_out]`` (a new host array; blocking)."""
+        x = _host(x, np.float32)
+        if x.ndim != 2 or x.shape[1] != self.d_in:
+            raise ValueError("x must be float32[n, %d]" % self.d_in)
+        y = np.empty((x.shape[0], self.d_out), dtype=np.float32)
+        _check(load_pca().sq_pca_apply(self.handle, _ptr(x), int(x.shape[0]), _ptr(y), SQ_MEM_HOST, None), "sq_pca_apply")
+        return y
+
+    def apply_device(self, x_ptr: int, n: int, y_ptr: int, stream: int = 0) -> None:
+        """Device pointers; enqueued on ``stream``, final when the stream is."""
+        _check(load_pca().sq_pca_apply(self.handle, _ptr(x_ptr), int(n), _ptr(y_ptr), SQ_MEM_DEVICE, ctypes.c_void_p(stream or None)),
+               "sq_pca_apply")
+
+    def info(self) -> dict:
+        out = (ctypes.c_int64 * SQ_PCA_INFO_FIELDS)()
+        _check(load_pca().sq_pca_info(self.handle, out, SQ_PCA_INFO_FIELDS), "sq_pca_info")
+        return dict(zip(self.INFO_FIELDS, (int(v) for v in out)))
+
+
+def pca_moments(x: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    """(mean float32 ``[d]``, scatter float64 ``[d, d]``) of the host rows ``x`` (float32 ``[n, d]``, ``n >= 2``) by
+    ``sq_pca_moments``: the scatter is about the float32 mean returned (include/smqtk_hip_pca.h)."""
+    x = _host(x, np.float32)
+    if x.ndim != 2:
+        raise ValueError("x must be float32[n, d]")
+    n, d = x.shape
+    mean = np.empty(d, dtype=np.float32)
+    scatter = np.empty((d, d), dtype=np.float64)
+    _check(load_pca().sq_pca_moments(_ptr(x), int(n), int(d), _ptr(mean), _ptr(scatter), SQ_MEM_HOST), "sq_pca_moments")
+    return mean, scatter
 
 
 def dense_distances(query: np.ndarray, rows: np.ndarray, metric: int = SQ_METRIC_L2) -> np.ndarray:

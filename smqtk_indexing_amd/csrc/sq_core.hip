@@ -136,7 +136,7 @@ extern "C" int sq_set_option(const char* name, int64_t value) {
 }
 
 static HandleBase* any_handle(sq_handle_t hid) {
-    for (int kind : {H_DENSE, H_HAMMING, H_ROWS, H_FIT, H_ITQ, H_IVF, H_PQ, H_ISQ, H_REFINE, H_OPQ})
+    for (int kind : {H_DENSE, H_HAMMING, H_ROWS, H_FIT, H_ITQ, H_IVF, H_PQ, H_ISQ, H_REFINE, H_OPQ, H_PCA})
         if (HandleBase* h = lookup_handle(hid, kind)) return h;
     return nullptr;
 }
@@ -183,6 +183,7 @@ extern "C" int sq_get_stats(sq_handle_t hid, sq_stats_t* out) {
     if (!h) h = lookup_handle(hid, H_ISQ);   // (the last sq_isq_search: slices, rows and code bytes scanned)
     if (!h) h = lookup_handle(hid, H_REFINE);   // (the last sq_refine_rerank / sq_refine_search: valid candidates and code bytes gathered)
     if (!h) h = lookup_handle(hid, H_OPQ);      // (the last sq_opq_apply: one launch, the bytes of the rows read)
+    if (!h) h = lookup_handle(hid, H_PCA);      // (the last sq_pca_apply: likewise)
     if (!h) return fail(SQ_ERR_INVALID, "sq_get_stats: unknown handle");
     std::lock_guard<std::mutex> l(h->mu);
     *out = h->stats;
